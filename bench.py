@@ -116,6 +116,25 @@ def interactive(pkg, r, dev, frames=600):
             "ms_per_frame": round(dt * 1e3, 4), "value": round(w * h * 4 * samps / dt / 1e6, 1), "unit": "Msamples/s"}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, img, st):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the image as float32 (image.npy; an image
+    above the 64 MB cap is cut to a fixed seeded sample of its rows, whose indices go to image_rows.npy) and the step's exact
+    counters samples, bounces, max_depth_kills as float64 (stats.npy)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    img = img.detach().cpu().numpy().astype(np.float32, copy=False)
+    if img.nbytes > DUMP_CAP_BYTES:
+        keep = (DUMP_CAP_BYTES - 4096) // (img[0].nbytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(img.shape[0], keep, replace=False))
+        img = img[rows]
+        np.save(os.path.join(directory, "image_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(directory, "image.npy"), np.ascontiguousarray(img))
+    np.save(os.path.join(directory, "stats.npy"), np.array([st["samples"], st["bounces"], st["max_depth_kills"]], dtype=np.float64))
+
+
 KERNEL_NAMES = {"pool": "spt::poolkernel<144,3>", "mega": "spt::megakernel", "grid": "spt::gridkernel<false>", "gpool": "spt::gpoolkernel<false>", "mesh": "spt::meshkernel<0>",
                 "sbvh": "spt::meshkernel<2>"}
 
@@ -300,7 +319,10 @@ def main():
     ap.add_argument("--only-extra", choices=EXTRAS, help="run one of the extra configurations alone and print its JSON (profiling runs)")
     ap.add_argument("--samps", type=int, default=SAMPS, help=argparse.SUPPRESS)   # dev only; default = config
     ap.add_argument("--variant", type=lambda v: int(v, 0), default=0, help=argparse.SUPPRESS)   # dev only: kernel A/B (csrc/spt_internal.h)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last timed step's image and counters to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")    # the host driver of this pool only supports dmabuf IPC (RCCL needs it)
     import torch
@@ -410,11 +432,13 @@ def main():
     t0 = time.perf_counter()
     kms, fms, bounces, samples = [], [], 0, 0
     for _ in range(args.steps):
-        _, st = step()
+        img, st = step()
         kms.append(st["kernel_ms"]); fms.append(st["finalize_ms"])
         bounces += st["bounces"]; samples += st["samples"]
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img, st)     # before the re-renders below overwrite the framebuffer
     # N > 1: what every rank spent where, for rank 0's line (the first hardware run of the exchange should be readable from one line)
     per_rank = None
     if world > 1:

@@ -4,15 +4,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
-def test_bench_json_line_contract():
+def test_bench_json_line_contract(pkg, oracle, tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--samps", "8", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                          "--samps", "8", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -33,6 +35,12 @@ def test_bench_json_line_contract():
     rr = j["rerender_same_seed"]
     assert len(rr["kernel_ms_per_launch"]) == 5 and rr["value"] > 100     # static, static + recording, three ordered launches
     assert "from_committed_profile" in r and "kernel_ms_per_step" in r and len(r["kernel_ms_per_step"]) == 2
+    # --dump-outputs: the last timed step (seed = warmup + steps - 1 = 2), not the same-seed re-renders after it, bit for bit the oracle's
+    img = np.load(tmp_path / "dump" / "image.npy")
+    counts = np.load(tmp_path / "dump" / "stats.npy")
+    ref, rst = oracle.render(pkg.cornell9(), 1024, 768, 8, seed=2, normalise=True)
+    assert img.dtype == np.float32 and np.array_equal(img, ref)
+    assert counts.tolist() == [rst["samples"], rst["bounces"], rst["max_depth_kills"]]
 
 
 @pytest.mark.gpu
