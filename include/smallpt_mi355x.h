@@ -16,6 +16,9 @@
  *   Intersector::traceRays + shadePaths per bounce              inside the kernels; the triangle seam itself
  *     (smallpt.cpp:553-587,154-267)                               (addTriangleMesh/build/traceRays, :427-473) is
  *                                                                 spt_set_meshes() / spt_trace_rays()
+ *   cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits)      spt_trace_spheres() (host buffers),
+ *     (smallpt.cpp:144-152; intersectGlobalSpheres :54-70 +     spt_trace_spheres_device() (device buffers, async)
+ *     Sphere::makeHit scene.cpp:118-127)
  *   accumBuffer += outImage under accumBufferMutex and the      spt_progressive_begin / _frame / _snapshot / _end
  *     GL thread's copy of it (smallpt.cpp:881-883,924-940,       (accumulation buffer resident in HBM)
  *     955-959)
@@ -182,6 +185,20 @@ int  spt_trace_rays(spt_ctx* ctx, const spt_ray* rays, uint64_t n, spt_hit* hits
  * buffers are to the reference's intersector, smallpt.cpp:571-575): enqueued on `hip_stream` (NULL = the context's stream), returns
  * without waiting.  No bytes cross the host link. */
 int  spt_trace_rays_device(spt_ctx* ctx, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream);
+/* cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits) (smallpt.cpp:144-152): closest hit of n rays against the current SPHERE
+ * table -- intersectGlobalSpheres (:54-70) followed by Sphere::makeHit (scene.cpp:118-127) per ray, the Hit that cpuRender's loop (:342-361)
+ * hands to its shading: dist = the root intersectAnalytic chooses (eps = 1e-4), instId = the sphere's index (the lowest among equal dist),
+ * x = o + d * dist, n = normalize(x - centre), triId = 0, uv = (0, 0); a miss is dist = 1e20 with every other field 0, as spt_trace_rays
+ * writes it.  Bit-identical to that arithmetic for every ray with finite components, whatever the direction's length or the origin's
+ * distance, and for every table spt_set_scene accepts.  The structure is the one spt_set_sphere_accel selects for renders (SPT_ACCEL_GRID:
+ * the grid if the table has one, else the hierarchy if built, else the exhaustive loop; SPT_ACCEL_BVH: the hierarchy; SPT_ACCEL_EXHAUSTIVE);
+ * rays outside a structure's proven range -- non-finite components, a zero direction, far origins -- take the exhaustive loop
+ * (csrc/spt_query.h).  Fails with "no sphere scene" while no sphere table is current (never set, or a mesh scene).  Host buffers, blocking:
+ * waits for a pending render first.  A query changes no render state. */
+int  spt_trace_spheres(spt_ctx* ctx, const spt_ray* rays, uint64_t n, spt_hit* hits);
+/* The same query on DEVICE buffers of this context's device (n spt_ray in, n spt_hit out), enqueued on `hip_stream` (NULL = the context's
+ * stream), returns without waiting.  Queries of one context run one after another, whatever their streams (they share a work list). */
+int  spt_trace_spheres_device(spt_ctx* ctx, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream);
 /* Host-only helper: makeSphereTriMesh(origin, radius, subdivLongitude) (scene.cpp:3-48): fills (L+1)(2L+1) positions and
  * normals and 4L^2 triangles (L = subdiv_longitude, default 32 at scene.h:17); returns the triangle count. */
 uint32_t spt_make_sphere_trimesh(const float origin[3], float radius, uint32_t subdiv_longitude,

@@ -50,6 +50,8 @@ SYMBOLS = {
     "spt_set_sphere_accel": (C.c_int, [_P, C.c_int]),
     "spt_trace_rays": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "spt_trace_rays_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    "spt_trace_spheres": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "spt_trace_spheres_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "spt_make_sphere_trimesh": (C.c_uint32, [C.c_float * 3, C.c_float, C.c_uint32, _P, _P, _P]),
     "spt_camera_smallpt": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(SptCamera)]),
     "spt_camera_pinhole": (C.c_int, [C.c_float * 3, C.c_float * 3, C.c_float * 3, C.c_float * 3, C.c_float, C.POINTER(SptCamera)]),
@@ -85,6 +87,8 @@ INTERNAL_SYMBOLS = {
     "spt_selftest_range": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "spt_set_watchdog": (C.c_int, [_P, C.c_double]),
     "spt_last_kernel": (C.c_int, [_P]),
+    "spt_last_query_path": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "spt_selftest_query_route": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P]),
     "spt_chunk_order_snapshot": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
 }
 

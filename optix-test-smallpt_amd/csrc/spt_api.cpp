@@ -5,6 +5,7 @@
 #include "spt_bvh.h"
 #include "spt_grid.h"
 #include "spt_kernel.h"
+#include "spt_query.h"
 
 #include <chrono>
 #include <cmath>
@@ -59,6 +60,10 @@ struct spt_ctx {
     bool mesh_specular = false;            // a mesh material is SPEC or REFR: long mirror / glass chains are possible (task dealing of the hierarchy kernel)
     float4* d_tris = nullptr; uint4* d_tri_index = nullptr; float4* d_verts = nullptr; uint32_t* d_inst_first = nullptr; float4* d_mesh_mats = nullptr;
     float* d_trace_rays = nullptr; float* d_trace_hits = nullptr; uint64_t trace_cap = 0;   // spt_trace_rays staging (rays)
+    // spt_trace_spheres*: the rays a walk hands to the exhaustive loop (one launch's worth), {count of the launch, pad, total of the query}, the
+    // query's completion (a query waits for its predecessor: they share these), what the last query ran through (-1: none yet)
+    uint32_t* d_qlist = nullptr; uint64_t qlist_cap = 0; uint32_t* d_qcount = nullptr;
+    hipEvent_t ev_query = nullptr; bool query_pending = false; int query_path = -1;
     std::vector<float4> h_geom;      // host copy of the sphere table {centre, r*r} and the radii: its hierarchy is built on demand
     std::vector<float> h_radius;
     int sphere_accel = SPT_ACCEL_GRID;
@@ -213,6 +218,9 @@ void spt_destroy(spt_ctx* c)
     if (c->d_tri_index) (void)hipFree(c->d_tri_index);
     if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
     if (c->d_trace_hits) (void)hipFree(c->d_trace_hits);
+    if (c->d_qlist) (void)hipFree(c->d_qlist);
+    if (c->d_qcount) (void)hipFree(c->d_qcount);
+    if (c->ev_query) (void)hipEventDestroy(c->ev_query);
     if (c->d_grid_cells) (void)hipFree(c->d_grid_cells);
     if (c->d_grid_refs) (void)hipFree(c->d_grid_refs);
     if (c->d_grid_always) (void)hipFree(c->d_grid_always);
@@ -496,6 +504,30 @@ int spt_selftest_sphere_grid(const spt_sphere* s, uint32_t n, uint32_t cells_per
     }
 }
 
+// Host-only evaluation of the query routing (spt_query.h query_ray_route, the function the query kernels call; no device call): route[i] of
+// ray i under `structure` (spt::kQueryGrid: the grid over the table at the default resolution; kQueryBvh; kQueryExhaustive).
+int spt_selftest_query_route(const spt_sphere* s, uint32_t n, uint32_t structure, const spt_ray* rays, uint64_t nrays, uint32_t* route, float* t_ok)
+{
+    try {
+        spt::SphereGrid g;
+        if (structure == spt::kQueryGrid) {
+            std::vector<float4> geom(n);
+            std::vector<float> radius(n);
+            for (uint32_t i = 0; i < n; ++i) { geom[i] = make_float4(s[i].center[0], s[i].center[1], s[i].center[2], s[i].radius * s[i].radius); radius[i] = s[i].radius; }
+            spt::build_sphere_grid(geom.data(), radius.data(), n, 4.0, (size_t)256 << 20, g);
+            if (!g.usable) return 2;
+        }
+        for (uint64_t i = 0; i < nrays; ++i) {
+            float tk = 0.f;
+            route[i] = spt::query_ray_route(structure, g.P, rays[i].o[0], rays[i].o[1], rays[i].o[2], rays[i].d[0], rays[i].d[1], rays[i].d[2], tk);
+            if (t_ok) t_ok[i] = tk;
+        }
+        return 0;
+    } catch (const std::exception&) {
+        return 1;
+    }
+}
+
 // Host-only self-test of the sphere hierarchy builder (no device call).  out4 = {nodes, leaves, depth, always-tested spheres}.
 int spt_selftest_sphere_bvh(const spt_sphere* s, uint32_t n, uint32_t* out4, char* why, uint32_t why_len)
 {
@@ -766,6 +798,22 @@ int spt_trace_rays_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hi
     return 0;
 }
 
+// ray / hit staging buffers of the host-buffer queries (spt_trace_rays, spt_trace_spheres), kept between calls (traceRays is called once per
+// bounce by the reference's render loop)
+static hipError_t ensure_trace_staging(spt_ctx* c, uint64_t n)
+{
+    hipError_t e = hipSuccess;
+    if (n > c->trace_cap) {
+        if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
+        if (c->d_trace_hits) (void)hipFree(c->d_trace_hits);
+        c->d_trace_rays = c->d_trace_hits = nullptr; c->trace_cap = 0;
+        e = hipMalloc(reinterpret_cast<void**>(&c->d_trace_rays), n * sizeof(spt_ray));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_trace_hits), n * sizeof(spt_hit));
+        if (e == hipSuccess) c->trace_cap = n;
+    }
+    return e;
+}
+
 int spt_trace_rays(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
 {
     if (!c) return 1;
@@ -776,16 +824,7 @@ int spt_trace_rays(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
     static_assert(sizeof(spt_ray) == 24 && sizeof(spt_hit) == 44, "Ray / Hit layouts of scene.h");
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
-    // ray / hit staging buffers are kept between calls (traceRays is called once per bounce by the reference's render loop)
-    hipError_t e = hipSuccess;
-    if (n > c->trace_cap) {
-        if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
-        if (c->d_trace_hits) (void)hipFree(c->d_trace_hits);
-        c->d_trace_rays = c->d_trace_hits = nullptr; c->trace_cap = 0;
-        e = hipMalloc(reinterpret_cast<void**>(&c->d_trace_rays), n * sizeof(spt_ray));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_trace_hits), n * sizeof(spt_hit));
-        if (e == hipSuccess) c->trace_cap = n;
-    }
+    hipError_t e = ensure_trace_staging(c, n);
     float* const d_rays = c->d_trace_rays;
     float* const d_hits = c->d_trace_hits;
     c->last_mesh_mode = mesh_mode(c, false);
@@ -799,6 +838,117 @@ int spt_trace_rays(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return c->fail("spt_trace_rays: %s", hipGetErrorString(e));
     return 0;
+}
+
+// ---- cpuIntersectGlobalSpheres (smallpt.cpp:144-152): closest hit of n rays against the current sphere table (spt_query.h) ----
+// Structure: the one spt_set_sphere_accel selects for renders -- SPT_ACCEL_GRID: the grid if the scene has one, else the hierarchy if built,
+// else the exhaustive loop; SPT_ACCEL_BVH: the hierarchy if built, else the exhaustive loop; SPT_ACCEL_EXHAUSTIVE: the exhaustive loop.
+// (Tables that need the guarded square root never walk: the grid refuses them at build time, the query keeps them off the hierarchy.)
+// Enqueued on `st`; touches no render state.
+static int trace_spheres_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, float* d_hits, hipStream_t st)
+{
+    uint32_t path = spt::kQueryExhaustive;
+    if (c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready) path = spt::kQueryGrid;
+    else if (c->sphere_accel != SPT_ACCEL_EXHAUSTIVE && c->sbvh_ready && !c->needs_guard) path = spt::kQueryBvh;
+    if (!c->ev_query) SPT_HIP(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+    if (!c->d_qcount) SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_qcount), 16));
+    const uint64_t slice_cap = n < spt::kQuerySlice ? n : spt::kQuerySlice;
+    if (path != spt::kQueryExhaustive && slice_cap > c->qlist_cap) {
+        if (c->d_qlist) (void)hipFree(c->d_qlist);           // (hipFree waits for the device: no launch still reads the old list)
+        c->d_qlist = nullptr; c->qlist_cap = 0;
+        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_qlist), slice_cap * sizeof(uint32_t)));
+        c->qlist_cap = slice_cap;
+    }
+    if (c->query_pending) SPT_HIP(c, hipStreamWaitEvent(st, c->ev_query, 0));   // the previous query (any stream) has released the list
+    SPT_HIP(c, hipMemsetAsync(c->d_qcount, 0, 16, st));
+    const int guard_all = c->needs_guard ? 1 : 0;
+    const uint32_t list_blocks = (uint32_t)(c->cu_count > 0 ? c->cu_count : 1) * 8u;
+    uint32_t grid_blocks = 0;
+    int where = c->grid_global;
+    if (path == spt::kQueryGrid) {
+        const size_t lds = where == 1 ? 0 : (where == 2 ? spt_grid_lds_bytes_tables(&c->grid) : spt_grid_lds_bytes(&c->grid));
+        const uint32_t per_cu = lds == 0 ? 2u : (lds * 2 <= (size_t)160 * 1024 ? 2u : 1u);   // 1024-thread workgroups, 160 KB of LDS per CU
+        grid_blocks = (uint32_t)(c->cu_count > 0 ? c->cu_count : 1) * per_cu;
+    }
+    spt::KParams K{};
+    spt::MParams M{};
+    if (path == spt::kQueryBvh) {
+        K.geom = c->d_geom; K.n = c->n;
+        M.bvh_nodes = c->d_sbvh_nodes; M.bvh_tris = c->d_sbvh_geom; M.bvh_index = c->d_sbvh_index;
+        M.always = c->d_sbvh_always; M.nalways = c->sbvh_nalways; M.sphere_mode = 1u;
+    }
+    for (uint64_t first = 0; first < n; first += spt::kQuerySlice) {
+        const uint32_t m = (uint32_t)(n - first < spt::kQuerySlice ? n - first : spt::kQuerySlice);
+        const float* const rays = d_rays + first * 6;
+        float* const hits = d_hits + first * 11;
+        if (path == spt::kQueryExhaustive) {
+            SPT_HIP(c, spt_query_exhaustive_launch(c->d_geom, c->n, rays, m, hits, nullptr, nullptr, 0, guard_all, st));
+            continue;
+        }
+        if (first != 0) SPT_HIP(c, hipMemsetAsync(c->d_qcount, 0, 4, st));
+        if (path == spt::kQueryGrid)
+            SPT_HIP(c, spt_query_grid_launch(c->d_geom, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, where, rays, m, hits,
+                                             c->d_qlist, c->d_qcount, grid_blocks, st));
+        else
+            SPT_HIP(c, spt_query_bvh_launch(&K, &M, rays, m, hits, c->d_qlist, c->d_qcount, st));
+        SPT_HIP(c, spt_query_exhaustive_launch(c->d_geom, c->n, rays, m, hits, c->d_qlist, c->d_qcount, list_blocks, guard_all, st));
+    }
+    SPT_HIP(c, hipEventRecord(c->ev_query, st));
+    c->query_pending = true;
+    c->query_path = (int)path;
+    return 0;
+}
+
+static int trace_spheres_check(spt_ctx* c, const char* who, const void* rays, uint64_t n, const void* hits)
+{
+    if (c->mesh_scene || !c->d_geom) return c->fail("%s: no sphere scene set (call spt_set_scene)", who);
+    if (n == 0) return 0;
+    if (!rays || !hits) return c->fail("%s: NULL argument", who);
+    if (n > 0x7FFFFFFFull * 256ull) return c->fail("%s: too many rays for one call", who);
+    return 0;
+}
+
+int spt_trace_spheres_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream)
+{
+    if (!c) return 1;
+    if (trace_spheres_check(c, "spt_trace_spheres_device", d_rays, n, d_hits)) return 1;
+    if (n == 0) return 0;
+    SPT_HIP(c, hipSetDevice(c->device));
+    return trace_spheres_enqueue(c, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits),
+                                 hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int spt_trace_spheres(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
+{
+    if (!c) return 1;
+    if (trace_spheres_check(c, "spt_trace_spheres", rays, n, hits)) return 1;
+    if (n == 0) return 0;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
+    hipError_t e = ensure_trace_staging(c, n);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_trace_rays, rays, n * sizeof(spt_ray), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return c->fail("spt_trace_spheres: %s", hipGetErrorString(e));
+    if (trace_spheres_enqueue(c, c->d_trace_rays, n, c->d_trace_hits, c->stream)) return 1;
+    e = hipMemcpyAsync(hits, c->d_trace_hits, n * sizeof(spt_hit), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return c->fail("spt_trace_spheres: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int spt_last_query_path(spt_ctx* c, uint64_t* fallback_rays)
+{
+    if (fallback_rays) *fallback_rays = 0;
+    if (!c || c->query_path < 0) return -1;
+    if (c->query_path != (int)spt::kQueryExhaustive && fallback_rays) {
+        unsigned long long total = 0;
+        if (hipSetDevice(c->device) != hipSuccess || hipEventSynchronize(c->ev_query) != hipSuccess ||
+            hipMemcpy(&total, c->d_qcount + 2, sizeof total, hipMemcpyDeviceToHost) != hipSuccess) {
+            c->fail("spt_last_query_path: reading the fallback count failed");
+            return -1;
+        }
+        *fallback_rays = total;
+    }
+    return c->query_path;
 }
 
 // smallpt.cpp:277-279 (D10: cx = (w*.5135/h, 0, 0))

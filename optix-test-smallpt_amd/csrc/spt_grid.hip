@@ -20,6 +20,8 @@
 #define SPT_GRID_DEVICE_ONLY
 #include "spt_grid.h"
 #include "spt_kernel.h"
+#define SPT_QUERY_DEVICE
+#include "spt_query.h"
 
 namespace spt {
 
@@ -34,12 +36,14 @@ __device__ __forceinline__ uint32_t lane_id_g() { return __builtin_amdgcn_mbcnt_
 
 // intersectAnalytic of one sphere record {c, r*r} on integer keys (scene.cpp:129-140, smallpt.cpp:59-65): key(t) = bits(t) - (bits(eps) + 1),
 // "t > eps && t < nearest" is one unsigned compare; det < 0 gives NaN roots whose keys lie above every valid one.
+// GUARD: the range-guarded square root (spt_query.h: rays or tables outside the unguarded form's proven range).
+template <bool GUARD = false>
 __device__ __forceinline__ uint32_t sphere_key_g(const float4 g, f3 o, f3 d)
 {
     const f3 op = mk(g.x - o.x, g.y - o.y, g.z - o.z);                                  // :132
     const float bb = dot(op, d);                                                        // :133
     const float det = bb * bb - dot(op, op) + g.w;                                      // :133 (g.w = r*r)
-    const float sd = sqrt_rsq(det);                                                     // :134
+    const float sd = GUARD ? sqrt_exact(det) : sqrt_rsq(det);                           // :134
     const uint32_t key1 = __float_as_uint(bb - sd) - kGEpsBias;                         // :135
     const uint32_t key2 = __float_as_uint(bb + sd) - kGEpsBias;
     return key1 < key2 ? key1 : key2;
@@ -438,6 +442,180 @@ __global__ __launch_bounds__(kGridBlock) void gridkernel(const KParams K, const 
     }
 }
 
+// ---- batched closest-hit queries against the sphere table (spt_trace_spheres, spt_query.h) -------------------------------------------------
+// Exhaustive loop: every sphere for every ray (smallpt.cpp:54-70, ascending index, strict '<').  The table streams through LDS in tiles of
+// kQTile records that every lane of the workgroup reads at the same address (broadcast); a wave holding a ray outside the unguarded square
+// root's range -- or a table that needs the guard -- runs the tile with sqrt_exact.  LIST = false: ray r is lane r of the launch, its Hit is
+// staged in LDS so that each wave writes its 64 x 44 contiguous bytes with 11 coalesced stores; LIST = true: the rays a walk handed over
+// (spt_query.h query_append), persistent workgroups over the list, one Hit per lane.
+constexpr uint32_t kQTile = 1024;                                // 16 KB of sphere records per tile (+ 11 KB of Hit staging: 5 workgroups per CU)
+
+template <bool GUARD>
+__device__ __forceinline__ void query_tile(const float4* s_geom, uint32_t cnt, uint32_t first, f3 o, f3 d, uint32_t& near_key, uint32_t& near_i)
+{
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t key = sphere_key_g<GUARD>(s_geom[k], o, d);
+        if (key < near_key) { near_key = key; near_i = first + k; }
+    }
+}
+
+template <bool LIST>
+__global__ __launch_bounds__(kQueryBlock) void query_exhaustive(const float4* __restrict__ geom, uint32_t n, const float* __restrict__ rays, uint32_t nrays,
+                                                                float* __restrict__ hits, const uint32_t* __restrict__ list, const uint32_t* __restrict__ qcount,
+                                                                int guard_all)
+{
+    __shared__ float4 s_geom[kQTile];
+    __shared__ float s_stage[LIST ? 1 : kQueryBlock * 11];
+    const uint32_t lane = lane_id_g(), wave = threadIdx.x >> 6;
+    const uint32_t count = LIST ? qcount[0] : nrays;
+    const bool one_tile = n <= kQTile;
+    if (one_tile) {
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) s_geom[i] = geom[i];
+        __syncthreads();
+    }
+    for (uint32_t base = blockIdx.x * kQueryBlock; base < count; base += gridDim.x * kQueryBlock) {     // workgroup-uniform
+        const uint32_t slot = base + threadIdx.x;
+        const bool active = slot < count;
+        const uint32_t r = active ? (LIST ? list[slot] : slot) : 0u;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        if (active) {
+            const float* q = rays + (size_t)r * 6;
+            o = mk(q[0], q[1], q[2]); d = mk(q[3], q[4], q[5]);
+        }
+        const bool guard = guard_all != 0 || __ballot(active && !query_ray_unguarded(o.x, o.y, o.z, d.x, d.y, d.z)) != 0ull;   // wave-uniform
+        uint32_t near_key = kGInfKey, near_i = 0u;
+        for (uint32_t tb = 0; tb < n; tb += kQTile) {
+            const uint32_t cnt = n - tb < kQTile ? n - tb : kQTile;
+            if (!one_tile) {
+                __syncthreads();                                 // the previous tile is no longer read
+                for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) s_geom[i] = geom[tb + i];
+                __syncthreads();
+            }
+            if (guard) query_tile<true>(s_geom, cnt, tb, o, d, near_key, near_i);
+            else query_tile<false>(s_geom, cnt, tb, o, d, near_key, near_i);
+        }
+        const bool hit = near_key != kGInfKey;
+        const QueryHit h = query_hit(hit, near_i, __uint_as_float(near_key + kGEpsBias), geom[hit ? near_i : 0u], o, d);
+        if (LIST) {
+            if (active) {
+                float* const out = hits + (size_t)r * 11;
+#pragma unroll
+                for (int k = 0; k < 11; ++k) out[k] = h.f[k];
+            }
+        } else {
+            float* const st = s_stage + wave * 64u * 11u;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) st[lane * 11u + k] = h.f[k];   // (stride 11: no two lanes of a store share a bank)
+            __syncthreads();
+            const uint32_t wbase = base + wave * 64u;
+            const uint32_t nv = wbase < count ? (count - wbase < 64u ? count - wbase : 64u) : 0u;
+            float* const out = hits + (size_t)wbase * 11;
+            for (uint32_t j = lane; j < nv * 11u; j += 64u) out[j] = st[j];
+            __syncthreads();
+        }
+    }
+}
+
+// The grid (spt_grid.h) over a caller's rays: persistent workgroups of kGridBlock threads share one LDS copy of the tables (WHERE as in
+// gridkernel), one lane per ray, a wave takes 64 consecutive rays at a time.  Each ray that query_ray_route admits tests the always-list,
+// then walks: an iteration TESTS the next sphere of the lane's cell or STEPS to the next cell, whichever more lanes want (as gridkernel's
+// walk phase).  Rays the route refuses, and walks that end beyond t_ok, go to the fallback list for query_exhaustive<true>.
+template <int WHERE>
+__global__ __launch_bounds__(kGridBlock) void query_grid(const float4* __restrict__ geom, const GridParams G, const uint32_t* __restrict__ g_cells,
+                                                         const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always,
+                                                         const float* __restrict__ rays, uint32_t nrays, float* __restrict__ hits,
+                                                         uint32_t* __restrict__ list, uint32_t* __restrict__ qcount)
+{
+    constexpr bool GLOBAL_TABLES = WHERE == 1, GLOBAL_GEOM = WHERE != 0;
+    extern __shared__ float4 s_lds_geom[];
+    uint32_t* const s_lds_cells = reinterpret_cast<uint32_t*>(s_lds_geom + (GLOBAL_GEOM ? 0u : (G.n ? G.n : 1u)));
+    uint16_t* const s_lds_refs = reinterpret_cast<uint16_t*>(s_lds_cells + G.ncells);
+    if (!GLOBAL_GEOM) for (uint32_t i = threadIdx.x; i < G.n; i += blockDim.x) s_lds_geom[i] = geom[i];
+    if (!GLOBAL_TABLES) {
+        for (uint32_t i = threadIdx.x; i < G.ncells; i += blockDim.x) s_lds_cells[i] = g_cells[i];
+        for (uint32_t i = threadIdx.x; i < G.nrefs; i += blockDim.x) s_lds_refs[i] = g_refs[i];
+        for (uint32_t i = threadIdx.x; i <= G.nalways; i += blockDim.x) s_lds_refs[G.nrefs + i] = i < G.nalways ? (uint16_t)g_always[i] : (uint16_t)0;
+    }
+    auto geom_at = [&](uint32_t i) -> float4 { return GLOBAL_GEOM ? geom[i] : s_lds_geom[i]; };
+    auto cell_at = [&](uint32_t ci) -> uint32_t { return GLOBAL_TABLES ? g_cells[ci] : s_lds_cells[ci]; };
+    auto ref_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? (uint32_t)g_refs[k] : (uint32_t)s_lds_refs[k]; };
+    auto always_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? g_always[k] : (uint32_t)s_lds_refs[G.nrefs + k]; };
+    __syncthreads();
+
+    const uint32_t lane = lane_id_g();
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t base = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 64u; base < nrays; base += waves * 64u) {   // wave-uniform
+        const uint32_t r = base + lane;
+        const bool active = r < nrays;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        if (active) {
+            const float* q = rays + (size_t)r * 6;
+            o = mk(q[0], q[1], q[2]); d = mk(q[3], q[4], q[5]);
+        }
+        float t_ok = 0.f;
+        const bool walk = active && query_ray_route(kQueryGrid, G, o.x, o.y, o.z, d.x, d.y, d.z, t_ok) == kQueryGrid;
+        uint32_t near_key = kGInfKey, near_i = 0u;               // index 0 with the inf key: never replaced by another inf key
+        for (uint32_t k = 0; k < G.nalways; ++k) {              // walls / lights: ascending indices, strict '<' (smallpt.cpp:61)
+            const uint32_t i = always_at(k);
+            const float4 g = geom_at(i);
+            if (walk) {
+                const uint32_t key = sphere_key_g(g, o, d);
+                if (key < near_key) { near_key = key; near_i = i; }
+            }
+        }
+        float wtx = 0.f, wty = 0.f, wtz = 0.f, wdx = 0.f, wdy = 0.f, wdz = 0.f;   // the walk (GridWalk) in separate registers
+        int32_t wsx = 0, wsy = 0, wsz = 0;
+        uint32_t wci = 0, cur = 0, end = 0;                      // end = 0 outside the walk
+        bool walking = walk;
+        if (walk) {
+            GridWalk w;
+            grid_walk_begin(G, o.x, o.y, o.z, d.x, d.y, d.z, w);
+            wtx = w.tx; wty = w.ty; wtz = w.tz; wdx = w.dtx; wdy = w.dty; wdz = w.dtz; wsx = w.sx; wsy = w.sy; wsz = w.sz; wci = w.ci;
+            const uint32_t h = cell_at(wci);                     // the start cell is clamped into the table: never a border cell
+            cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+        }
+        uint32_t nwalk = (uint32_t)__popcll(__ballot(walking));
+        while (nwalk != 0u) {
+            const bool wt = cur < end;
+            const uint32_t nt = (uint32_t)__popcll(__ballot(wt));
+            if (2u * nt >= nwalk) {                              // TEST the next sphere of the lane's cell
+                if (wt) {
+                    const uint32_t i = ref_at(cur);
+                    ++cur;
+                    const uint32_t key = sphere_key_g(geom_at(i), o, d);
+                    // a sphere may be listed in several cells and cells are not visited in index order: lowest index among equal keys
+                    const bool better = (key < near_key) | ((key == near_key) & (i < near_i));
+                    near_key = better ? key : near_key;
+                    near_i = better ? i : near_i;
+                }
+            } else {                                             // STEP: leave the cell (all its spheres are tested)
+                if (walking && !wt) {
+                    const float m = __builtin_fminf(wtx, __builtin_fminf(wty, wtz));   // grid_walk_exit
+                    bool stop = !(m < __uint_as_float(near_key + kGEpsBias));          // spt_grid.h (3)
+                    if (!stop) {
+                        grid_walk_step(wtx, wty, wtz, wdx, wdy, wdz, wsx, wsy, wsz, wci, m);
+                        const uint32_t h = cell_at(wci);
+                        stop = h == kGridBorder;                 // left the table
+                        cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+                    }
+                    if (stop) { walking = false; end = 0; }
+                }
+                nwalk = (uint32_t)__popcll(__ballot(walking));
+            }
+        }
+        const float t = __uint_as_float(near_key + kGEpsBias);
+        const bool fallback = active && (!walk || t > t_ok);    // spt_grid.h (1), (4): the exhaustive loop answers
+        query_append(fallback, r, list, qcount, reinterpret_cast<unsigned long long*>(qcount + 2));
+        if (walk && !fallback) {
+            const bool hit = near_key != kGInfKey;
+            const QueryHit h = query_hit(hit, near_i, t, geom_at(near_i), o, d);
+            float* const out = hits + (size_t)r * 11;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) out[k] = h.f[k];
+        }
+    }
+}
+
 }  // namespace spt
 
 extern "C" size_t spt_grid_lds_bytes(const spt::GridParams* G)
@@ -472,4 +650,40 @@ extern "C" hipError_t spt_grid_launch(const spt::KParams* K, const spt::GridPara
     if (where == 0) return stats ? launch_grid<true, 0>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream) : launch_grid<false, 0>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream);
     if (where == 1) return stats ? launch_grid<true, 1>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream) : launch_grid<false, 1>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream);
     return stats ? launch_grid<true, 2>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream) : launch_grid<false, 2>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream);
+}
+
+extern "C" hipError_t spt_query_exhaustive_launch(const float4* geom, uint32_t n, const float* rays, uint32_t nrays, float* hits,
+                                                  const uint32_t* list, const uint32_t* qcount, uint32_t list_blocks, int guard_all, hipStream_t stream)
+{
+    if (nrays == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)nrays + spt::kQueryBlock - 1) / spt::kQueryBlock);
+    if (list) hipLaunchKernelGGL(spt::query_exhaustive<true>, dim3(blocks < list_blocks ? blocks : list_blocks), dim3(spt::kQueryBlock), 0, stream,
+                                 geom, n, rays, nrays, hits, list, qcount, guard_all);
+    else hipLaunchKernelGGL(spt::query_exhaustive<false>, dim3(blocks), dim3(spt::kQueryBlock), 0, stream, geom, n, rays, nrays, hits, list, qcount, guard_all);
+    return hipGetLastError();
+}
+
+template <int WHERE>
+static hipError_t launch_query_grid(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs, const uint32_t* d_always,
+                                    const float* rays, uint32_t nrays, float* hits, uint32_t* list, uint32_t* qcount, uint32_t blocks, size_t lds, hipStream_t stream)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::query_grid<WHERE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((spt::query_grid<WHERE>), dim3(blocks), dim3(spt::kGridBlock), lds, stream, geom, *G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount);
+    return hipGetLastError();
+}
+
+// blocks: persistent workgroups of kGridBlock threads (the caller sizes them from the CU count); where as in spt_grid_launch
+extern "C" hipError_t spt_query_grid_launch(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
+                                            const uint32_t* d_always, int where, const float* rays, uint32_t nrays, float* hits,
+                                            uint32_t* list, uint32_t* qcount, uint32_t blocks, hipStream_t stream)
+{
+    if (where < 0 || where > 2) return hipErrorInvalidValue;
+    if (nrays == 0) return hipSuccess;
+    const uint32_t need = (uint32_t)(((uint64_t)nrays + spt::kGridBlock - 1) / spt::kGridBlock);
+    if (blocks > need) blocks = need;
+    const size_t lds = where == 1 ? 0 : (where == 2 ? spt_grid_lds_bytes_tables(G) : spt_grid_lds_bytes(G));
+    if (where == 0) return launch_query_grid<0>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
+    if (where == 1) return launch_query_grid<1>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
+    return launch_query_grid<2>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
 }

@@ -78,6 +78,17 @@ int  spt_selftest_sphere_bvh(const spt_sphere* spheres, uint32_t n, uint32_t* ou
  * out8 = {dim x, dim y, dim z, references, always-tested spheres, table bytes, usable, most references in one cell}; 0 = valid, 2 = not usable / invalid, 1 = builder error. */
 int  spt_selftest_sphere_grid(const spt_sphere* spheres, uint32_t n, uint32_t cells_per_sphere, uint32_t* out8, char* why, uint32_t why_len);
 
+/* spt_trace_spheres*: what the last query of this context ran through -- 0 = the exhaustive loop, 1 = the uniform grid, 2 = the sphere
+ * hierarchy, -1 = no query yet -- and, in *fallback_rays (may be NULL), how many of its rays the grid or the hierarchy handed to the exhaustive
+ * loop (csrc/spt_query.h: refused by the routing, or a grid walk that ended beyond its valid range).  Waits for that query.  Renders do not
+ * change it, and queries change no render state (spt_last_kernel). */
+int  spt_last_query_path(spt_ctx* ctx, uint64_t* fallback_rays);
+/* Host-only evaluation of the query routing (csrc/spt_query.h query_ray_route, the same function the query kernels run; no device call):
+ * route[i] of ray i = 0 exhaustive loop, 1 grid walk, 2 hierarchy walk, under structure 0 (exhaustive), 1 (the grid over this table at the
+ * default resolution) or 2 (the hierarchy); t_ok (may be NULL) = the parameter up to which a grid walk's answer stands.
+ * Returns 0, 2 = the grid does not take this table, 1 = builder error. */
+int  spt_selftest_query_route(const spt_sphere* spheres, uint32_t n, uint32_t structure, const spt_ray* rays, uint64_t nrays, uint32_t* route, float* t_ok);
+
 /* libsmallpt_mi355x_multi.so: kernel watchdog (spt_set_watchdog) of ONE rank's context, so that a test can make exactly one
  * device's render fail and check that spt_multi_render returns its error instead of hanging in the exchange. */
 struct spt_multi;

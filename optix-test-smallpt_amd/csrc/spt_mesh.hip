@@ -21,6 +21,9 @@
 //     exhaustive loop's Hit for every ray.  SPT_ACCEL_BVH_FAST: the spatial hierarchy alone.
 #include "spt_device.h"
 #include "spt_kernel.h"
+#define SPT_GRID_DEVICE_ONLY
+#define SPT_QUERY_DEVICE
+#include "spt_query.h"
 
 namespace spt {
 
@@ -352,6 +355,31 @@ __global__ __launch_bounds__(kMeshBlock) void trace_rays(const MParams M, const 
     h[3] = m.x.x; h[4] = m.x.y; h[5] = m.x.z; h[6] = m.n.x; h[7] = m.n.y; h[8] = m.n.z; h[9] = m.u; h[10] = m.v;
 }
 
+// Batched closest-hit query against a sphere table through its hierarchy (spt_trace_spheres, spt_query.h): one lane per ray, closest_sphere_bvh
+// with the tables spt_set_sphere_accel built.  Rays that query_ray_route keeps out of the tree go to the fallback list (the exhaustive loop,
+// spt_grid.hip query_exhaustive<true>); their Hit is written there.
+__global__ __launch_bounds__(kMeshBlock) void trace_spheres_bvh(const KParams K, const MParams M, const float* __restrict__ rays, uint32_t nrays,
+                                                                float* __restrict__ hits, uint32_t* __restrict__ list, uint32_t* __restrict__ qcount)
+{
+    extern __shared__ float4 s_tile[];
+    const uint32_t r = blockIdx.x * kMeshBlock + threadIdx.x;
+    const bool active = r < nrays;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    if (active) { const float* q = rays + (size_t)r * 6; ro = mk(q[0], q[1], q[2]); rd = mk(q[3], q[4], q[5]); }
+    float t_ok;
+    const GridParams G{};
+    const bool walk = active && query_ray_route(kQueryBvh, G, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, t_ok) == kQueryBvh;
+    float t;
+    const uint32_t i = closest_sphere_bvh(K, M, M.bvh_nodes, M.bvh_tris, M.bvh_index, reinterpret_cast<uint32_t*>(s_tile), walk, ro, rd, t);
+    query_append(active && !walk, r, list, qcount, reinterpret_cast<unsigned long long*>(qcount + 2));
+    if (!walk) return;
+    const bool hit = i != 0xFFFFFFFFu;
+    const QueryHit h = query_hit(hit, i, t, K.geom[hit ? i : 0u], ro, rd);
+    float* const out = hits + (size_t)r * 11;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) out[k] = h.f[k];
+}
+
 // ---- path tracer over the mesh scene ------------------------------------------------------------------------------
 struct MPath { f3 o, d, w; uint32_t depth, branch, rbase; };
 
@@ -647,5 +675,15 @@ extern "C" hipError_t spt_mesh_trace_rays(const spt::MParams* M, const float* d_
     const uint64_t blocks = (nrays + spt::kMeshBlock - 1) / spt::kMeshBlock;
     if (M->bvh_nodes) hipLaunchKernelGGL(spt::trace_rays<true>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *M, d_rays, nrays, d_hits);
     else hipLaunchKernelGGL(spt::trace_rays<false>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *M, d_rays, nrays, d_hits);
+    return hipGetLastError();
+}
+
+// K: geom = the sphere table; M: the sphere hierarchy (bvh_nodes / bvh_tris / bvh_index / always / nalways).  nrays <= kQuerySlice.
+extern "C" hipError_t spt_query_bvh_launch(const spt::KParams* K, const spt::MParams* M, const float* rays, uint32_t nrays, float* hits,
+                                           uint32_t* list, uint32_t* qcount, hipStream_t stream)
+{
+    if (nrays == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)nrays + spt::kMeshBlock - 1) / spt::kMeshBlock);
+    hipLaunchKernelGGL(spt::trace_spheres_bvh, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, rays, nrays, hits, list, qcount);
     return hipGetLastError();
 }

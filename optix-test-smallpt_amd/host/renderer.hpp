@@ -65,6 +65,7 @@ public:
     // The Intersector seam of the reference (smallpt.cpp:427-473 CPUIntersector / :475-603 OptixIntersector):
     //   addTriangleMesh(mesh) for every instance + build()  ->  setMeshes(meshes, materials)   (materials[i] <-> instance i, :170)
     //   Vector<Hit> traceRays(const PathContrib*, size_t)    ->  traceRays(rays, n)
+    //   cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits) ->  traceSpheres(rays, n)
     void setMeshes(const std::vector<TriMesh>& meshes, const std::vector<Material>& materials)
     {
         if (meshes.size() != materials.size()) throw std::runtime_error("setMeshes: one material per mesh instance");
@@ -97,6 +98,20 @@ public:
     void traceRaysDevice(const void* dRays, size_t n, void* dHits, void* hipStream = nullptr)
     {
         check(spt_trace_rays_device(ctx_, dRays, (uint64_t)n, dHits, hipStream));
+    }
+
+    // cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits) (smallpt.cpp:144-152) against the current sphere table: one Hit per ray
+    // (instId = sphere index, triId = 0, uv = 0; dist = 1e20 on a miss), what cpuRender's loop (:342-361) shades
+    std::vector<Hit> traceSpheres(const Ray* rays, size_t n)
+    {
+        std::vector<Hit> hits(n);
+        check(spt_trace_spheres(ctx_, reinterpret_cast<const spt_ray*>(rays), (uint64_t)n, reinterpret_cast<spt_hit*>(hits.data())));
+        return hits;
+    }
+    // the same query on device buffers of this context's device, enqueued on `hipStream` (nullptr: the context's stream) without waiting
+    void traceSpheresDevice(const void* dRays, size_t n, void* dHits, void* hipStream = nullptr)
+    {
+        check(spt_trace_spheres_device(ctx_, dRays, (uint64_t)n, dHits, hipStream));
     }
 
     const spt_stats& stats() const { return stats_; }

@@ -17,6 +17,20 @@ FLAG_ONE_SHOT = 2          # scheduling only: no dispatch order used or recorded
 ACCEL_EXHAUSTIVE, ACCEL_BVH, ACCEL_GRID, ACCEL_BVH_FAST, ACCEL_AUTO = 0, 1, 2, 3, 4
 
 
+def _ray_array(rays):
+    """RAY_DTYPE[n], or floats of shape (n, 6), as a contiguous RAY_DTYPE array; anything else is refused."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        if a.ndim != 1:
+            raise ValueError(f"rays: expected a 1-D array of RAY_DTYPE, got shape {a.shape}")
+        return np.ascontiguousarray(a)
+    if a.dtype.fields is not None or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"rays: expected RAY_DTYPE or real numbers, got dtype {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError(f"rays: expected shape (n, 6), got {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32).view(RAY_DTYPE).reshape(-1)
+
+
 class SptError(RuntimeError):
     pass
 
@@ -170,6 +184,49 @@ class Renderer:
         st = (stream if stream is not None else torch.cuda.current_stream(rays_t.device)).cuda_stream
         self._check(self._lib.spt_trace_rays_device(self._h, C.c_void_p(rays_t.data_ptr()), n, C.c_void_p(hits_t.data_ptr()), C.c_void_p(st)))
         return hits_t
+
+    def trace_spheres(self, rays):
+        """cpuIntersectGlobalSpheres (smallpt.cpp:144-152) against the current sphere table: rays = RAY_DTYPE[n] or floats of shape (n, 6);
+        returns HIT_DTYPE[n] (instId = sphere index, triId = 0, uv = 0; a miss is dist = 1e20 with every other field 0)."""
+        rays = _ray_array(rays)
+        n = len(rays)
+        hits = np.zeros(n, dtype=HIT_DTYPE)
+        self._check(self._lib.spt_trace_spheres(self._h, rays.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)))
+        return hits
+
+    def trace_spheres_device(self, rays_t, hits_t=None, stream=None):
+        """spt_trace_spheres_device: rays_t = contiguous float32 tensor (n, 6) on this renderer's device; returns the float32 tensor (n, 11)
+        of Hit records (dist, instId and triId as raw bits, x, n, uv), enqueued on `stream` (a torch stream; default: the current one)."""
+        import torch
+        if not (isinstance(rays_t, torch.Tensor) and rays_t.is_cuda and rays_t.dtype == torch.float32 and rays_t.is_contiguous()
+                and rays_t.dim() == 2 and rays_t.shape[1] == 6):
+            raise ValueError("trace_spheres_device: rays_t must be a contiguous float32 device tensor of shape (n, 6)")
+        n = rays_t.shape[0]
+        if hits_t is None:
+            hits_t = torch.empty((n, 11), dtype=torch.float32, device=rays_t.device)
+        elif not (isinstance(hits_t, torch.Tensor) and hits_t.device == rays_t.device and hits_t.dtype == torch.float32
+                  and hits_t.is_contiguous() and tuple(hits_t.shape) == (n, 11)):
+            raise ValueError("trace_spheres_device: hits_t must be a contiguous float32 tensor of shape (n, 11) on the rays' device")
+        stream = stream if stream is not None else torch.cuda.current_stream(rays_t.device)
+        if stream.cuda_stream == 0:
+            # torch's default stream is handle 0, which the C call reads as "the context's own stream" -- a non-blocking stream not ordered
+            # with it: run on a pool stream that waits for the default one, and make the default one wait for the query
+            side = torch.cuda.Stream(rays_t.device)
+            side.wait_stream(stream)
+            self._check(self._lib.spt_trace_spheres_device(self._h, C.c_void_p(rays_t.data_ptr()), n, C.c_void_p(hits_t.data_ptr()),
+                                                           C.c_void_p(side.cuda_stream)))
+            stream.wait_stream(side)
+            return hits_t
+        self._check(self._lib.spt_trace_spheres_device(self._h, C.c_void_p(rays_t.data_ptr()), n, C.c_void_p(hits_t.data_ptr()),
+                                                       C.c_void_p(stream.cuda_stream)))
+        return hits_t
+
+    def last_query_path(self):
+        """What the last trace_spheres* query ran through and how many of its rays the walk handed to the exhaustive loop:
+        ("exhaustive" | "grid" | "bvh" | None before the first query, fallback_rays).  Waits for that query."""
+        fb = C.c_uint64(0)
+        path = self._lib.spt_last_query_path(self._h, C.byref(fb))
+        return {-1: None, 0: "exhaustive", 1: "grid", 2: "bvh"}[path], int(fb.value)
 
     def set_tuning(self, blocks_per_cu=0, variant=0):
         self._check(self._lib.spt_set_tuning(self._h, blocks_per_cu, variant))
