@@ -16,6 +16,9 @@
  *   Intersector::traceRays + shadePaths per bounce              inside the kernels; the triangle seam itself
  *     (smallpt.cpp:553-587,154-267)                               (addTriangleMesh/build/traceRays, :427-473) is
  *                                                                 spt_set_meshes() / spt_trace_rays()
+ *   shadePaths' debug views as shipped: the first hit's normal  spt_render_aov()       (host image)
+ *     added and `continue` (smallpt.cpp:179-183; uv and          spt_render_aov_rows_device() (row band, async)
+ *     triangle id one comment away)
  *   cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits)      spt_trace_spheres() (host buffers),
  *     (smallpt.cpp:144-152; intersectGlobalSpheres :54-70 +     spt_trace_spheres_device() (device buffers, async)
  *     Sphere::makeHit scene.cpp:118-127)
@@ -235,6 +238,36 @@ int  spt_render_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uin
                             uint32_t row_begin, uint32_t row_count,
                             uint32_t samps_per_cell, uint64_t seed, uint32_t flags,
                             void* d_out_rgb, void* hip_stream);
+
+/* First-hit feature buffers: the image the reference program draws as shipped -- shadePaths adds the first hit's normal and
+ * `continue`s (smallpt.cpp:179-183, nl = n at :174) -- and the normal / albedo / uv / depth companions a denoiser takes.
+ *   Samples: the camera sample of (pixel, cell, sample) is exactly the one spt_render traces for the same camera, size, samples per
+ *     cell and seed (same D7 keys, same tent or box-in-cell sampler, same double-precision path), so each buffer lines up sample for
+ *     sample with the radiance render of that seed.  It is traced once against the current scene, through the structure that
+ *     spt_set_sphere_accel / spt_set_mesh_accel selects, and finds the Hit that spt_trace_spheres / spt_trace_rays returns for that ray.
+ *   Value of a sample: a miss adds nothing (:168).  A hit adds
+ *     SPT_AOV_NORMAL  hit.n unflipped (:181 as shipped): normalize(x - c) for spheres, the interpolated, un-normalised vertex normal
+ *                     for meshes;
+ *     SPT_AOV_ALBEDO  the material colour of hit.instId (:175);
+ *     SPT_AOV_UV      (hit.uv.x, hit.uv.y, 0) (:182): (0, 0, 0) for spheres;
+ *     SPT_AOV_DIST    (dist, dist, dist).
+ *   Accumulation: the D9 order of spt_render bit for bit (float32, samples ascending within a block, blocks of a cell in order, pixel =
+ *     ((c0 + c1) + c2) + c3); SPT_FLAG_NORMALISE multiplies by 1.f / spp.  Stats: samples = rows * w * spp, bounces = samples,
+ *     max_depth_kills = 0.
+ *   A call changes no render state (the chunk-order records, SPT_ACCEL_AUTO's bounce share of the last launch, spt_last_kernel, the
+ *   progressive buffers); like the render entries it first waits for a pending launch.  It fails on an unknown aov, without a
+ *   current scene, for w, h or samps of 0 and for a row band outside the image.
+ *   Not covered: the reference's triangle-id view int2color(triId) (:182) -- a fract(sin(x) * 43758) hash that turns one ulp of sin
+ *   into 1e-3 of colour, so it cannot be bit-exact --; several buffers per launch; the multi-GPU front; a progressive variant (callers
+ *   accumulate the rows output with spt_accumulate_device). */
+enum { SPT_AOV_NORMAL = 0, SPT_AOV_ALBEDO = 1, SPT_AOV_UV = 2, SPT_AOV_DIST = 3 };
+/* Full w x h buffer to out_rgb (host, w*h*3 floats, row 0 = bottom).  Blocking. */
+int  spt_render_aov(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps_per_cell, uint64_t seed,
+                    uint32_t aov, uint32_t flags, float* out_rgb, spt_stats* stats);
+/* Rows [row_begin, row_begin+row_count) into d_out_rgb (DEVICE, row_count*w*3 floats), enqueued on hip_stream (NULL = the context's
+ * stream); returns without waiting, as spt_render_rows_device (keys use the global pixel index; call spt_sync() before reading stats). */
+int  spt_render_aov_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                                uint32_t samps_per_cell, uint64_t seed, uint32_t aov, uint32_t flags, void* d_out_rgb, void* hip_stream);
 
 /* Progressive accumulation of the viewer's render thread (smallpt.cpp:924-937), device-resident:
  * d_accum[i] = clear ? d_frame[i] : d_accum[i] + d_frame[i] for n floats (both 16-byte aligned, on this device);

@@ -59,6 +59,10 @@ SYMBOLS = {
                              C.c_uint32, _P, C.POINTER(SptStats)]),
     "spt_render_rows_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),
+    "spt_render_aov": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                 C.c_uint32, _P, C.POINTER(SptStats)]),
+    "spt_render_aov_rows_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     "spt_interleaved_row_count": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "spt_render_interleaved_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),

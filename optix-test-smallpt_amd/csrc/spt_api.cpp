@@ -6,6 +6,7 @@
 #include "spt_grid.h"
 #include "spt_kernel.h"
 #include "spt_query.h"
+#include "spt_aov.h"
 
 #include <chrono>
 #include <cmath>
@@ -125,6 +126,7 @@ struct spt_ctx {
     unsigned long long watchdog_ticks = 0;   // pool kernel: s_memtime ticks (shader cycles) per launch; 0 = no watchdog
     // last launch
     bool pending = false;
+    bool last_aov = false;          // ... was a spt_render_aov* launch (spt_sync reports it without the render bookkeeping)
     spt_stats last{};
     unsigned long long diag[24] = {};   // DIAG build only: phase wave-times and lane counts (pool kernel: its statistics)
     std::string error;
@@ -1024,6 +1026,36 @@ int spt_render_interleaved_device(spt_ctx* c, const spt_camera* cam, uint32_t w,
     return render_rows_impl(c, cam, w, h, rank * block_rows, rows, lb, world * block_rows, block_rows - 1u, samps, seed, flags, d_out_rgb, hip_stream);
 }
 
+// The regular triangles in whose plane the camera's origin lies (spt_bvh.h camera_planes), for the depth-0 rays of a launch through the
+// exact hierarchy; cached per camera origin and push extent.  Fills M.cam_planes / ncam / cam_cull.
+static int camera_plane_list(spt_ctx* c, const spt_camera* cam, hipStream_t st, spt::MParams& M)
+{
+    // every ray of depth 0 lies on a line through cam->origin and starts at most |push| |d| from it (push = 0: a pinhole
+    // camera, every ray starts there), and a ray can only be reported by a regular triangle through a determinant that is
+    // zero to rounding if its origin lies in that triangle's plane (spt_tribvh.h (2), condition (B)): those triangles are
+    // listed once per camera (none, as a rule) and the camera rays skip the plane tree
+    auto norm3 = [](const float* v) { return std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); };
+    const float extra = (float)(std::fabs((double)cam->push) * (norm3(cam->dir) + 1.1 * (norm3(cam->cx) + norm3(cam->cy))) * 1.01);
+    const float key[4] = {cam->origin[0], cam->origin[1], cam->origin[2], extra};
+    if (!c->cam_valid || std::memcmp(c->cam_key, key, sizeof c->cam_key) != 0) {
+        std::vector<uint32_t> list;
+        spt::camera_planes(c->h_tris.data(), c->ntris, cam->origin, extra, list);
+        if (list.size() > c->cam_cap) {
+            if (c->d_cam_planes) (void)hipFree(c->d_cam_planes);
+            c->d_cam_planes = nullptr; c->cam_cap = 0;
+            SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cam_planes), list.size() * sizeof(uint32_t)));
+            c->cam_cap = (uint32_t)list.size();
+        }
+        if (!list.empty()) SPT_HIP(c, hipMemcpyAsync(c->d_cam_planes, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (!list.empty()) SPT_HIP(c, hipStreamSynchronize(st));           // (the list is a local)
+        c->ncam = (uint32_t)list.size();
+        std::memcpy(c->cam_key, key, sizeof c->cam_key);
+        c->cam_valid = true;
+    }
+    M.cam_planes = c->d_cam_planes; M.ncam = c->ncam; M.cam_cull = 1u;
+    return 0;
+}
+
 static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
                             uint32_t rb_log2, uint32_t rb_stride, uint32_t rb_mask, uint32_t samps, uint64_t seed,
                             uint32_t flags, void* d_out_rgb, void* hip_stream)
@@ -1040,6 +1072,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
     if (!c->d_geom && !c->mesh_scene) return c->fail("spt_render_rows_device: no scene set (call spt_set_scene)");
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
+    c->last_aov = false;
 
     const size_t ntasks = (size_t)npix * 4 * nb;
     if (ntasks > c->cells_cap) {
@@ -1178,31 +1211,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         } else {
             P.n = 0; P.n_pad = 1; P.geom = nullptr; P.mat = nullptr;
             M = mesh_params(c, mode);
-            if (M.plane_nodes) {
-                // every ray of depth 0 lies on a line through cam->origin and starts at most |push| |d| from it (push = 0: a pinhole
-                // camera, every ray starts there), and a ray can only be reported by a regular triangle through a determinant that is
-                // zero to rounding if its origin lies in that triangle's plane (spt_tribvh.h (2), condition (B)): those triangles are
-                // listed once per camera (none, as a rule) and the camera rays skip the plane tree
-                auto norm3 = [](const float* v) { return std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); };
-                const float extra = (float)(std::fabs((double)cam->push) * (norm3(cam->dir) + 1.1 * (norm3(cam->cx) + norm3(cam->cy))) * 1.01);
-                const float key[4] = {cam->origin[0], cam->origin[1], cam->origin[2], extra};
-                if (!c->cam_valid || std::memcmp(c->cam_key, key, sizeof c->cam_key) != 0) {
-                    std::vector<uint32_t> list;
-                    spt::camera_planes(c->h_tris.data(), c->ntris, cam->origin, extra, list);
-                    if (list.size() > c->cam_cap) {
-                        if (c->d_cam_planes) (void)hipFree(c->d_cam_planes);
-                        c->d_cam_planes = nullptr; c->cam_cap = 0;
-                        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cam_planes), list.size() * sizeof(uint32_t)));
-                        c->cam_cap = (uint32_t)list.size();
-                    }
-                    if (!list.empty()) SPT_HIP(c, hipMemcpyAsync(c->d_cam_planes, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                    if (!list.empty()) SPT_HIP(c, hipStreamSynchronize(st));           // (the list is a local)
-                    c->ncam = (uint32_t)list.size();
-                    std::memcpy(c->cam_key, key, sizeof c->cam_key);
-                    c->cam_valid = true;
-                }
-                M.cam_planes = c->d_cam_planes; M.ncam = c->ncam; M.cam_cull = 1u;
-            }
+            if (M.plane_nodes && camera_plane_list(c, cam, st, M)) return 1;
         }
         SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
         SPT_HIP(c, hipEventRecord(c->ev_start, st));
@@ -1376,6 +1385,13 @@ int spt_sync(spt_ctx* c, spt_stats* stats)
         SPT_HIP(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_mid));
         SPT_HIP(c, hipEventElapsedTime(&fms, c->ev_mid, c->ev_stop));
         c->last.finalize_ms = fms;
+        if (c->last_aov) {                                       // spt_render_aov*: one closest-hit query per sample, no render bookkeeping
+            c->last.kernel_ms = ms;
+            c->last.bounces = c->last.samples;
+            c->pending = false;
+            if (stats) *stats = c->last;
+            return 0;
+        }
         unsigned long long ctr[2] = {0, 0};
         SPT_HIP(c, hipMemcpy(ctr, c->d_counters, sizeof ctr, hipMemcpyDeviceToHost));
         c->last.kernel_ms = ms;
@@ -1412,6 +1428,125 @@ int spt_render(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32
         c->out_cap = nfl;
     }
     if (int rc = spt_render_rows_device(c, cam, w, h, 0, h, samps, seed, flags, c->d_out, nullptr)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (int rc = spt_sync(c, nullptr)) return rc;
+    c->last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = c->last;
+    return 0;
+}
+
+// ---- first-hit feature buffers (smallpt.cpp:179-183 as shipped: the first hit's normal, uv or triangle id instead of radiance) ----
+// One closest hit per camera sample of spt_render's sample layout, through the structure the scene's accel mode selects for queries
+// (spt_trace_spheres / spt_trace_rays), folded by spt_k_finalize.  Shares the render scratch (cells) and the launch events, so it waits for a
+// pending launch and the next launch waits for it; the render state (chunk order, SPT_ACCEL_AUTO's bounce share, spt_last_kernel, the
+// progressive buffers) is left alone.  A pending RENDER is completed first as spt_sync would complete it, so that its bookkeeping is kept.
+static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                           uint32_t samps, uint64_t seed, uint32_t aov, uint32_t flags, void* d_out_rgb, void* hip_stream)
+{
+    if (!cam || !d_out_rgb) return c->fail("%s: NULL argument", who);
+    if (aov > SPT_AOV_DIST) return c->fail("%s: unknown aov %u (SPT_AOV_NORMAL, _ALBEDO, _UV or _DIST)", who, aov);
+    if (!c->d_geom && !c->mesh_scene) return c->fail("%s: no scene set (call spt_set_scene or spt_set_meshes)", who);
+    if (w == 0 || h == 0 || samps == 0) return c->fail("%s: empty image or samps == 0", who);
+    if (row_count == 0 || (uint64_t)row_begin + row_count > h) return c->fail("%s: row band [%u,+%u) outside image height %u", who, row_begin, row_count, h);
+    if ((uint64_t)w * h > 0xFFFFFFFFull) return c->fail("%s: w*h exceeds 2^32-1 pixels", who);
+    if ((uint64_t)samps * 4 > 0xFFFFFFFFull) return c->fail("%s: spp overflows 32 bits", who);
+    if (cam->sampler > SPT_SAMPLER_PINHOLE) return c->fail("%s: unknown camera sampler %u", who, cam->sampler);
+    const uint32_t nb_log2 = samps >= 128u ? 3u : (samps >= 64u ? 2u : (samps >= 32u ? 1u : 0u));   // D9, as spt_render
+    const uint32_t nb = 1u << nb_log2;
+    const uint64_t npix = (uint64_t)row_count * w;
+    const uint64_t qend = (uint64_t)((w + 7u) >> 3) * ((row_count + 7u) >> 3) * 64u * 4u * nb;     // spt_deal.h deal_tiles_end
+    if (npix * 4 * nb > 0xF0000000ull || qend > 0xFFFFFFFFull) return c->fail("%s: band has too many sample blocks (%u per pixel); split it", who, 4u * nb);
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) {
+        if (!c->last_aov) { if (int rc = spt_sync(c, nullptr)) return rc; }
+        else SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+    }
+    const size_t ntasks = (size_t)npix * 4 * nb;
+    if (ntasks > c->cells_cap) {
+        if (c->d_cells) (void)hipFree(c->d_cells);
+        c->d_cells = nullptr; c->cells_cap = 0;
+        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cells), ntasks * sizeof(float4)));
+        c->cells_cap = ntasks;
+    }
+    spt::KParams P{};
+    std::memcpy(P.cam_o, cam->origin, 12); std::memcpy(P.cam_d, cam->dir, 12);
+    std::memcpy(P.cam_cx, cam->cx, 12); std::memcpy(P.cam_cy, cam->cy, 12);
+    P.cam_push = cam->push;
+    P.sampler = cam->sampler;
+    P.inv_wf = 1.f / (float)w; P.inv_hf = 1.f / (float)h;
+    P.w = w; P.h = h; P.row_begin = row_begin; P.row_count = row_count;
+    P.rb_log2 = 0u; P.rb_stride = 1u; P.rb_mask = 0u;
+    P.inv_w = 1.0 / (double)w; P.inv_h = 1.0 / (double)h;
+    P.samps = samps; P.ntasks = (uint32_t)ntasks;
+    P.nb_log2 = nb_log2; P.sb = (samps + nb - 1u) / nb;
+    P.s0 = mix32((uint32_t)seed + 0x243F6A88u);
+    P.s1 = mix32((uint32_t)(seed >> 32) ^ P.s0 ^ 0x85A308D3u);
+    P.n = c->mesh_scene ? 0u : c->n; P.n_pad = P.n ? P.n : 1u;
+    P.geom = c->mesh_scene ? nullptr : c->d_geom; P.mat = c->mesh_scene ? nullptr : c->d_mat;
+    P.cells = c->d_cells;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    uint32_t blocks = 0, threads = 256;
+    spt::MParams M{};
+    int path = 0;                                    // 0 sphere table exhaustive, 1 grid, 2 sphere hierarchy, 3 meshes
+    if (c->mesh_scene) {
+        path = 3;
+        M = mesh_params(c, mesh_mode(c, false));     // (every ray is a camera ray: the bounce share of renders does not apply)
+        if (M.plane_nodes && camera_plane_list(c, cam, st, M)) return 1;
+    } else if (c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready) {
+        path = 1;
+        const size_t lds = c->grid_global == 1 ? 0 : (c->grid_global == 2 ? spt_grid_lds_bytes_tables(&c->grid) : spt_grid_lds_bytes(&c->grid));
+        const uint32_t per_cu = lds == 0 ? 2u : (lds * 2 <= (size_t)160 * 1024 ? 2u : 1u);   // 1024-thread workgroups, 160 KB of LDS per CU
+        blocks = (uint32_t)(c->cu_count > 0 ? c->cu_count : 1) * per_cu;
+        threads = (uint32_t)spt_grid_block_threads();
+    } else if (c->sphere_accel != SPT_ACCEL_EXHAUSTIVE && c->sbvh_ready && !c->needs_guard) {
+        path = 2;
+        M.bvh_nodes = c->d_sbvh_nodes; M.bvh_tris = c->d_sbvh_geom; M.bvh_index = c->d_sbvh_index;
+        M.always = c->d_sbvh_always; M.nalways = c->sbvh_nalways; M.sphere_mode = 1u;
+    } else if (c->n > SPT_MAX_SPHERES) {
+        return c->fail("%s: %u spheres > SPT_MAX_SPHERES (%u) and no structure over them", who, c->n, SPT_MAX_SPHERES);
+    }
+    if (path != 1) blocks = (uint32_t)((qend + 255u) / 256u);
+    SPT_HIP(c, hipEventRecord(c->ev_start, st));
+    if (path == 0) SPT_HIP(c, spt_aov_exhaustive_launch(&P, aov, c->needs_guard ? 1 : 0, st));
+    else if (path == 1) SPT_HIP(c, spt_aov_grid_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, c->grid_global, aov, blocks, st));
+    else if (path == 2) SPT_HIP(c, spt_aov_sphere_bvh_launch(&P, &M, aov, st));
+    else SPT_HIP(c, spt_aov_mesh_launch(&P, &M, aov, st));
+    SPT_HIP(c, hipEventRecord(c->ev_mid, st));
+    SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, 1.0f / (float)(4u * samps), (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
+    SPT_HIP(c, hipEventRecord(c->ev_stop, st));
+    c->pending = true;
+    c->last_aov = true;
+    c->last = spt_stats{};
+    c->last.samples = npix * 4ull * samps;
+    c->last.grid_blocks = blocks;
+    c->last.block_threads = threads;
+    return 0;
+}
+
+int spt_render_aov_rows_device(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                               uint32_t samps, uint64_t seed, uint32_t aov, uint32_t flags, void* d_out_rgb, void* hip_stream)
+{
+    if (!c) return 1;
+    return render_aov_impl(c, "spt_render_aov_rows_device", cam, w, h, row_begin, row_count, samps, seed, aov, flags, d_out_rgb, hip_stream);
+}
+
+int spt_render_aov(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps, uint64_t seed, uint32_t aov, uint32_t flags,
+                   float* out_rgb, spt_stats* stats)
+{
+    if (!c) return 1;
+    if (!out_rgb) return c->fail("spt_render_aov: out_rgb is NULL");
+    const auto t0 = std::chrono::steady_clock::now();
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t nfl = (size_t)w * h * 3;
+    if (nfl > c->out_cap) {
+        if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+        if (c->d_out) (void)hipFree(c->d_out);
+        c->d_out = nullptr; c->out_cap = 0;
+        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), nfl * sizeof(float)));
+        c->out_cap = nfl;
+    }
+    if (int rc = render_aov_impl(c, "spt_render_aov", cam, w, h, 0, h, samps, seed, aov, flags, c->d_out, nullptr)) return rc;
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     if (int rc = spt_sync(c, nullptr)) return rc;

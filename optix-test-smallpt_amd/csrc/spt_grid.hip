@@ -22,6 +22,7 @@
 #include "spt_kernel.h"
 #define SPT_QUERY_DEVICE
 #include "spt_query.h"
+#include "spt_aov.h"
 
 namespace spt {
 
@@ -616,6 +617,171 @@ __global__ __launch_bounds__(kGridBlock) void query_grid(const float4* __restric
     }
 }
 
+// ---- first-hit feature buffers (spt_render_aov, spt_aov.h) over the sphere table ----------------------------------------------------------
+// One lane per D9 task (a block of one jitter cell's samples), the lanes of a wave dealt an 8 x 8 tile of pixels (spt_deal.h deal_task_tiles);
+// per sample: the camera ray, its closest hit, acc += the selected value; then cells[task].  No bounces: no pools, stacks or watchdog.
+// Exhaustive loop: the whole table in LDS (<= SPT_MAX_SPHERES x 16 B), ascending index and strict '<' (smallpt.cpp:54-70); a wave holding a
+// ray outside the unguarded square root's range (spt_query.h) -- or a table that needs the guard -- runs the sample with sqrt_exact.
+__device__ __forceinline__ uint32_t aov_task_at(const KParams& K, uint32_t q, uint32_t qend)
+{
+    const uint32_t S = 4u << K.nb_log2;
+    const uint32_t task = q < qend ? deal_task_tiles(q, K.w, K.row_count, S) : 0xFFFFFFFFu;
+    return task < K.ntasks ? task : 0xFFFFFFFFu;
+}
+
+// value of a sphere hit (Sphere::makeHit, scene.cpp:118-127: n = normalize(x - centre), uv = 0) added to acc
+__device__ __forceinline__ f3 aov_sphere_add(const KParams& K, uint32_t kind, f3 acc, uint32_t i, float t, const float4 g, f3 o, f3 d)
+{
+    const QueryHit h = query_hit(true, i, t, g, o, d);
+    const float4 colour = kind == kAovAlbedo ? K.mat[3 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+    return aov_add(acc, kind, mk(h.f[6], h.f[7], h.f[8]), colour, 0.0f, 0.0f, t);
+}
+
+template <bool GUARD>
+__device__ __forceinline__ void aov_sphere_loop(const float4* s_geom, uint32_t n, f3 o, f3 d, uint32_t& near_key, uint32_t& near_i)
+{
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t key = sphere_key_g<GUARD>(s_geom[k], o, d);
+        if (key < near_key) { near_key = key; near_i = k; }
+    }
+}
+
+__global__ __launch_bounds__(kAovBlock) void aov_exhaustive(const KParams K, uint32_t kind, int guard_all)
+{
+    extern __shared__ float4 s_aov_geom[];
+    for (uint32_t i = threadIdx.x; i < K.n; i += blockDim.x) s_aov_geom[i] = K.geom[i];
+    __syncthreads();
+    const uint32_t qend = deal_tiles_end(K.w, K.row_count, 4u << K.nb_log2);
+    const uint32_t task = aov_task_at(K, blockIdx.x * kAovBlock + threadIdx.x, qend);
+    const bool valid = task != 0xFFFFFFFFu;
+    AovTask a{};
+    if (valid) a = aov_task(K, task);
+    f3 acc = mk(0, 0, 0);
+    for (uint32_t s = a.s_begin; __ballot(valid && s < a.s_end) != 0ull; ++s) {     // wave-uniform
+        const bool active = valid && s < a.s_end;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        if (active) aov_camera_ray(K, a, s, o, d);
+        const bool guard = guard_all != 0 || __ballot(active && !query_ray_unguarded(o.x, o.y, o.z, d.x, d.y, d.z)) != 0ull;
+        uint32_t near_key = kGInfKey, near_i = 0u;
+        if (active) {
+            if (guard) aov_sphere_loop<true>(s_aov_geom, K.n, o, d, near_key, near_i);
+            else aov_sphere_loop<false>(s_aov_geom, K.n, o, d, near_key, near_i);
+        }
+        if (active && near_key != kGInfKey)                                         // a miss adds nothing (smallpt.cpp:168)
+            acc = aov_sphere_add(K, kind, acc, near_i, __uint_as_float(near_key + kGEpsBias), s_aov_geom[near_i], o, d);
+    }
+    if (valid) K.cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+}
+
+// Through the grid: persistent workgroups of kGridBlock threads share one LDS copy of the tables (WHERE as in gridkernel), a wave takes 64
+// queue positions at a time.  Per sample, as query_grid does for a caller's ray: query_ray_route, the always-list, then the walk -- an
+// iteration TESTS the next sphere of the lane's cell or STEPS to the next cell, whichever more lanes want.  A ray the route refuses (a far
+// or pushed camera origin) or whose walk ends beyond t_ok runs the exhaustive loop in its lane over the global table (guarded square root).
+template <int WHERE>
+__global__ __launch_bounds__(kGridBlock) void aov_grid(const KParams K, const GridParams G, const uint32_t* __restrict__ g_cells,
+                                                       const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always, uint32_t kind)
+{
+    constexpr bool GLOBAL_TABLES = WHERE == 1, GLOBAL_GEOM = WHERE != 0;
+    extern __shared__ float4 s_lds_geom[];
+    uint32_t* const s_lds_cells = reinterpret_cast<uint32_t*>(s_lds_geom + (GLOBAL_GEOM ? 0u : (G.n ? G.n : 1u)));
+    uint16_t* const s_lds_refs = reinterpret_cast<uint16_t*>(s_lds_cells + G.ncells);
+    const float4* const geom = K.geom;
+    if (!GLOBAL_GEOM) for (uint32_t i = threadIdx.x; i < G.n; i += blockDim.x) s_lds_geom[i] = geom[i];
+    if (!GLOBAL_TABLES) {
+        for (uint32_t i = threadIdx.x; i < G.ncells; i += blockDim.x) s_lds_cells[i] = g_cells[i];
+        for (uint32_t i = threadIdx.x; i < G.nrefs; i += blockDim.x) s_lds_refs[i] = g_refs[i];
+        for (uint32_t i = threadIdx.x; i <= G.nalways; i += blockDim.x) s_lds_refs[G.nrefs + i] = i < G.nalways ? (uint16_t)g_always[i] : (uint16_t)0;
+    }
+    auto geom_at = [&](uint32_t i) -> float4 { return GLOBAL_GEOM ? geom[i] : s_lds_geom[i]; };
+    auto cell_at = [&](uint32_t ci) -> uint32_t { return GLOBAL_TABLES ? g_cells[ci] : s_lds_cells[ci]; };
+    auto ref_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? (uint32_t)g_refs[k] : (uint32_t)s_lds_refs[k]; };
+    auto always_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? g_always[k] : (uint32_t)s_lds_refs[G.nrefs + k]; };
+    __syncthreads();
+
+    const uint32_t lane = lane_id_g();
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    const uint32_t qend = deal_tiles_end(K.w, K.row_count, 4u << K.nb_log2);
+    // the camera constants are read from the kernel-argument segment where a ray is generated (the empty asm keeps the scalar loads from
+    // being hoisted out of the loops, where they would spill beside the walk's scalars; K is the first kernel argument)
+    typedef const __attribute__((address_space(4))) KParams KArg;
+    for (uint32_t base = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 64u; base < qend; base += waves * 64u) {   // wave-uniform
+        const uint32_t task = aov_task_at(K, base + lane, qend);
+        const bool valid = task != 0xFFFFFFFFu;
+        AovTask a{};
+        if (valid) a = aov_task(K, task);
+        f3 acc = mk(0, 0, 0);
+        for (uint32_t s = a.s_begin; __ballot(valid && s < a.s_end) != 0ull; ++s) {
+            const bool active = valid && s < a.s_end;
+            f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+            if (active) {
+                KArg* kc = (KArg*)__builtin_amdgcn_kernarg_segment_ptr();
+                asm volatile("" : "+s"(kc));
+                aov_camera_ray(*kc, a, s, o, d);
+            }
+            float t_ok = 0.f;
+            const bool walk = active && query_ray_route(kQueryGrid, G, o.x, o.y, o.z, d.x, d.y, d.z, t_ok) == kQueryGrid;
+            uint32_t near_key = kGInfKey, near_i = 0u;           // index 0 with the inf key: never replaced by another inf key
+            for (uint32_t k = 0; k < G.nalways; ++k) {          // walls / lights: ascending indices, strict '<' (smallpt.cpp:61)
+                const uint32_t i = always_at(k);
+                const float4 g = geom_at(i);
+                if (walk) {
+                    const uint32_t key = sphere_key_g(g, o, d);
+                    if (key < near_key) { near_key = key; near_i = i; }
+                }
+            }
+            float wtx = 0.f, wty = 0.f, wtz = 0.f, wdx = 0.f, wdy = 0.f, wdz = 0.f;
+            int32_t wsx = 0, wsy = 0, wsz = 0;
+            uint32_t wci = 0, cur = 0, end = 0;
+            bool walking = walk;
+            if (walk) {
+                GridWalk w;
+                grid_walk_begin(G, o.x, o.y, o.z, d.x, d.y, d.z, w);
+                wtx = w.tx; wty = w.ty; wtz = w.tz; wdx = w.dtx; wdy = w.dty; wdz = w.dtz; wsx = w.sx; wsy = w.sy; wsz = w.sz; wci = w.ci;
+                const uint32_t h = cell_at(wci);
+                cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+            }
+            uint32_t nwalk = (uint32_t)__popcll(__ballot(walking));
+            while (nwalk != 0u) {
+                const bool wt = cur < end;
+                const uint32_t nt = (uint32_t)__popcll(__ballot(wt));
+                if (2u * nt >= nwalk) {
+                    if (wt) {
+                        const uint32_t i = ref_at(cur);
+                        ++cur;
+                        const uint32_t key = sphere_key_g(geom_at(i), o, d);
+                        const bool better = (key < near_key) | ((key == near_key) & (i < near_i));   // cells are not visited in index order
+                        near_key = better ? key : near_key;
+                        near_i = better ? i : near_i;
+                    }
+                } else {
+                    if (walking && !wt) {
+                        const float m = __builtin_fminf(wtx, __builtin_fminf(wty, wtz));   // grid_walk_exit
+                        bool stop = !(m < __uint_as_float(near_key + kGEpsBias));          // spt_grid.h (3)
+                        if (!stop) {
+                            grid_walk_step(wtx, wty, wtz, wdx, wdy, wdz, wsx, wsy, wsz, wci, m);
+                            const uint32_t h = cell_at(wci);
+                            stop = h == kGridBorder;
+                            cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+                        }
+                        if (stop) { walking = false; end = 0; }
+                    }
+                    nwalk = (uint32_t)__popcll(__ballot(walking));
+                }
+            }
+            if (active && (!walk || __uint_as_float(near_key + kGEpsBias) > t_ok)) {   // spt_grid.h (1), (4): the exhaustive loop answers
+                near_key = kGInfKey; near_i = 0u;
+                for (uint32_t i = 0; i < G.n; ++i) {
+                    const uint32_t key = sphere_key_g<true>(geom[i], o, d);
+                    if (key < near_key) { near_key = key; near_i = i; }
+                }
+            }
+            if (active && near_key != kGInfKey)
+                acc = aov_sphere_add(K, kind, acc, near_i, __uint_as_float(near_key + kGEpsBias), geom_at(near_i), o, d);
+        }
+        if (valid) K.cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    }
+}
+
 }  // namespace spt
 
 extern "C" size_t spt_grid_lds_bytes(const spt::GridParams* G)
@@ -686,4 +852,40 @@ extern "C" hipError_t spt_query_grid_launch(const float4* geom, const spt::GridP
     if (where == 0) return launch_query_grid<0>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
     if (where == 1) return launch_query_grid<1>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
     return launch_query_grid<2>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
+}
+
+extern "C" hipError_t spt_aov_exhaustive_launch(const spt::KParams* K, uint32_t kind, int guard_all, hipStream_t stream)
+{
+    const size_t lds = (size_t)(K->n ? K->n : 1u) * sizeof(float4);
+    const uint32_t qend = spt::deal_tiles_end(K->w, K->row_count, 4u << K->nb_log2);
+    const uint32_t blocks = (uint32_t)(((uint64_t)qend + spt::kAovBlock - 1) / spt::kAovBlock);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_exhaustive), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(spt::aov_exhaustive, dim3(blocks), dim3(spt::kAovBlock), lds, stream, *K, kind, guard_all);
+    return hipGetLastError();
+}
+
+template <int WHERE>
+static hipError_t launch_aov_grid(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs, const uint32_t* d_always,
+                                  uint32_t kind, uint32_t blocks, size_t lds, hipStream_t stream)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_grid<WHERE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((spt::aov_grid<WHERE>), dim3(blocks), dim3(spt::kGridBlock), lds, stream, *K, *G, d_cells, d_refs, d_always, kind);
+    return hipGetLastError();
+}
+
+// blocks: persistent workgroups of kGridBlock threads (the caller sizes them from the CU count); where as in spt_grid_launch
+extern "C" hipError_t spt_aov_grid_launch(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
+                                          const uint32_t* d_always, int where, uint32_t kind, uint32_t blocks, hipStream_t stream)
+{
+    if (where < 0 || where > 2) return hipErrorInvalidValue;
+    const uint32_t qend = spt::deal_tiles_end(K->w, K->row_count, 4u << K->nb_log2);
+    const uint32_t need = (uint32_t)(((uint64_t)qend + spt::kGridBlock - 1) / spt::kGridBlock);
+    if (blocks > need) blocks = need;
+    if (blocks < 1) blocks = 1;
+    const size_t lds = where == 1 ? 0 : (where == 2 ? spt_grid_lds_bytes_tables(G) : spt_grid_lds_bytes(G));
+    if (where == 0) return launch_aov_grid<0>(K, G, d_cells, d_refs, d_always, kind, blocks, lds, stream);
+    if (where == 1) return launch_aov_grid<1>(K, G, d_cells, d_refs, d_always, kind, blocks, lds, stream);
+    return launch_aov_grid<2>(K, G, d_cells, d_refs, d_always, kind, blocks, lds, stream);
 }

@@ -24,6 +24,7 @@
 #define SPT_GRID_DEVICE_ONLY
 #define SPT_QUERY_DEVICE
 #include "spt_query.h"
+#include "spt_aov.h"
 
 namespace spt {
 
@@ -656,6 +657,62 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
     }
 }
 
+// ---- first-hit feature buffers (spt_render_aov, spt_aov.h) ----------------------------------------------------------------------------------
+// One lane per D9 task, the lanes of a wave dealt an 8 x 8 tile of pixels (spt_deal.h deal_task_tiles: there are no long chains here, so the
+// reasons of MParams::strips do not apply); per sample: the camera ray, its closest hit, acc += the selected value; then cells[task].
+// GEOM 0: triangles, exhaustive (the workgroup stages the tiles together: the sample loop runs to the workgroup's longest block);
+// 1: triangles through the hierarchy, every ray a depth-0 ray (the launch's camera-plane list replaces the plane tree); 2: a sphere table
+// through its hierarchy, rays that query_ray_route keeps out of the tree run the exhaustive loop in their lane over the global table.
+template <int GEOM>
+__global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MParams M, uint32_t kind)
+{
+    extern __shared__ float4 s_tile[];
+    const uint32_t S = 4u << K.nb_log2, qend = deal_tiles_end(K.w, K.row_count, S);
+    const uint32_t q = blockIdx.x * kMeshBlock + threadIdx.x;
+    uint32_t task = q < qend ? deal_task_tiles(q, K.w, K.row_count, S) : 0xFFFFFFFFu;
+    const bool valid = task < K.ntasks;
+    AovTask a{};
+    if (valid) a = aov_task(K, task);
+    f3 acc = mk(0, 0, 0);
+    for (uint32_t s = a.s_begin;; ++s) {
+        const bool active = valid && s < a.s_end;
+        if (GEOM == 0) { if (__syncthreads_count(active ? 1 : 0) == 0) break; }   // workgroup-uniform: closest_triangle stages tiles
+        else if (__ballot(active) == 0ull) break;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        if (active) aov_camera_ray(K, a, s, o, d);
+        float t = 0.f;
+        if (GEOM == 2) {
+            float t_ok;
+            const GridParams G{};
+            const bool walk = active && query_ray_route(kQueryBvh, G, o.x, o.y, o.z, d.x, d.y, d.z, t_ok) == kQueryBvh;
+            uint32_t i = closest_sphere_bvh(K, M, M.bvh_nodes, M.bvh_tris, M.bvh_index, reinterpret_cast<uint32_t*>(s_tile), walk, o, d, t);
+            if (active && !walk) {                                                 // smallpt.cpp:54-70: ascending index, strict '<'
+                uint32_t near_key = kSphInfKey;
+                i = 0xFFFFFFFFu;
+                for (uint32_t k = 0; k < K.n; ++k) {
+                    const uint32_t key = sphere_key(K.geom[k], o, d);
+                    if (key < near_key) { near_key = key; i = k; }
+                }
+                t = __uint_as_float(near_key + kSphEpsBias);
+            }
+            if (active && i != 0xFFFFFFFFu) {                                       // a miss adds nothing (smallpt.cpp:168)
+                const QueryHit h = query_hit(true, i, t, K.geom[i], o, d);
+                const float4 colour = kind == kAovAlbedo ? K.mat[3 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = aov_add(acc, kind, mk(h.f[6], h.f[7], h.f[8]), colour, 0.0f, 0.0f, t);
+            }
+        } else {
+            const uint32_t tri = GEOM == 1 ? closest_triangle_bvh<kMeshArgOffset>(M, reinterpret_cast<uint32_t*>(s_tile), active, M.cam_cull != 0u, o, d, t)
+                                           : closest_triangle(M.tris, M.ntris, s_tile, active, o, d, t);
+            if (active && tri != 0xFFFFFFFFu) {
+                const MeshHit h = make_hit(M, tri, t, o, d);
+                const float4 colour = kind == kAovAlbedo ? M.mats[3 * (size_t)h.inst + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = aov_add(acc, kind, h.n, colour, h.u, h.v, h.dist);
+            }
+        }
+    }
+    if (valid) K.cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+}
+
 }  // namespace spt
 
 // exhaustive: one tile of triangle records; hierarchy: 32 stack entries per thread
@@ -685,5 +742,25 @@ extern "C" hipError_t spt_query_bvh_launch(const spt::KParams* K, const spt::MPa
     if (nrays == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((uint64_t)nrays + spt::kMeshBlock - 1) / spt::kMeshBlock);
     hipLaunchKernelGGL(spt::trace_spheres_bvh, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, rays, nrays, hits, list, qcount);
+    return hipGetLastError();
+}
+
+// K: camera, band, D9 layout, cells (and, GEOM 2, the sphere table); M: the mesh tables or the sphere hierarchy, as for spt_mesh_launch
+static uint32_t aov_mesh_blocks(const spt::KParams* K)
+{
+    const uint32_t qend = spt::deal_tiles_end(K->w, K->row_count, 4u << K->nb_log2);
+    return (uint32_t)(((uint64_t)qend + spt::kMeshBlock - 1) / spt::kMeshBlock);
+}
+
+extern "C" hipError_t spt_aov_sphere_bvh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t kind, hipStream_t stream)
+{
+    hipLaunchKernelGGL(spt::aov_mesh<2>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t spt_aov_mesh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t kind, hipStream_t stream)
+{
+    if (M->bvh_nodes) hipLaunchKernelGGL(spt::aov_mesh<1>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind);
+    else hipLaunchKernelGGL(spt::aov_mesh<0>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, kind);
     return hipGetLastError();
 }

@@ -46,6 +46,17 @@ public:
         return out;
     }
 
+    // First-hit feature buffer (spt_render_aov; SPT_AOV_NORMAL / _ALBEDO / _UV / _DIST): the closest hit of every camera sample of render()
+    // with the same arguments, folded in its order -- with SPT_AOV_NORMAL the image shadePaths draws as shipped (smallpt.cpp:179-183).
+    std::vector<float3> renderAov(const spt_camera& camera, size_t imageWidth, size_t imageHeight, size_t sampleCountPerJitterCell,
+                                  size_t seed, uint32_t aov, bool normalise = false)
+    {
+        std::vector<float3> out(imageWidth * imageHeight);
+        check(spt_render_aov(ctx_, &camera, (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)sampleCountPerJitterCell, (uint64_t)seed,
+                             aov, normalise ? SPT_FLAG_NORMALISE : 0u, reinterpret_cast<float*>(out.data()), &stats_));
+        return out;
+    }
+
     // accumBuffer of the viewer loop in HBM (spt_progressive_*, smallpt.cpp:881-883,922-937,955-959)
     void progressiveBegin(size_t w, size_t h) { check(spt_progressive_begin(ctx_, (uint32_t)w, (uint32_t)h)); }
     void progressiveFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool clear)

@@ -6,6 +6,8 @@
 //   smallpt_mi355x [spp] [--scene file.json | shipped-meshes] [--size WxH] [--seed N] [--out image.ppm] [--device D]
 //                  [--dump-scene out.json] [--parse-only]
 //                  [--accel grid|bvh|bvh-fast|exhaustive]             closest hit of sphere tables above 24 (default grid) / mesh scenes (default bvh)
+//                  [--aov normal|albedo|uv|dist]                  first-hit feature buffer instead of radiance (spt_render_aov); with
+//                                                              --single-triangle --aov normal: the reference program's own image (smallpt.cpp:179-183)
 //                  [--devices 0,1,...] [--self-exchange]      row bands over several GPUs + RCCL exchange (MultiRenderer)
 //   smallpt_mi355x [spp] --viewer [--frames N] [--request JSON] [--frames-after M] [--threaded] [--org x,y,z]
 //                  [--pipeline L] [--bench-frames N]           L frames in flight (one context each); frames/s of N frames as JSON
@@ -37,6 +39,7 @@ int main(int argc, char* argv[])
     double watchdog = 0.0;                           // test hook: kernel watchdog in seconds (csrc/spt_internal.h)
     std::string scene_path, out_path = "image.ppm", dump_path;
     bool single_triangle = false;
+    int aov = -1;                                  // --aov: SPT_AOV_* (-1: radiance)
     bool parse_only = false, viewer = false, threaded = false, self_exchange = false;
     int frames = 1, frames_after = 0;
     std::vector<int> devices;
@@ -66,6 +69,7 @@ int main(int argc, char* argv[])
         else if (a == "--pipeline") { pipeline = std::atoi(next()); if (pipeline < 1 || pipeline > 8) { std::fprintf(stderr, "--pipeline 1..8\n"); return 2; } }
         else if (a == "--bench-frames") bench_frames = std::atoi(next());
         else if (a == "--watchdog") watchdog = std::atof(next());
+        else if (a == "--aov") { const std::string m = next(); if (m == "normal") aov = SPT_AOV_NORMAL; else if (m == "albedo") aov = SPT_AOV_ALBEDO; else if (m == "uv") aov = SPT_AOV_UV; else if (m == "dist") aov = SPT_AOV_DIST; else { std::fprintf(stderr, "--aov normal|albedo|uv|dist\n"); return 2; } }
         else if (a == "--single-triangle") single_triangle = true;   // SingleTriangleScene of main(), smallpt.cpp:818-832
         else if (a == "--viewer") viewer = true;
         else if (a == "--threaded") threaded = true;
@@ -100,6 +104,7 @@ int main(int argc, char* argv[])
             return 0;
         }
         const int samps = spp / 4 > 0 ? spp / 4 : 1;                               // :276
+        if (aov >= 0 && viewer) throw std::runtime_error("--aov renders one offline image (no --viewer)");
         if (viewer) {
             // main() of the reference (smallpt.cpp:840-1005) without GLFW/GL: render thread + request queue + accumulation
             Renderer renderer(device);
@@ -167,6 +172,7 @@ int main(int argc, char* argv[])
         const spt_camera cam = make_camera(scene.camera, (uint32_t)w, (uint32_t)h);  // :277-279
         std::fprintf(stderr, "Starting rendering\n");                               // :272
         const auto start = std::chrono::high_resolution_clock::now();
+        if (aov >= 0 && !devices.empty()) throw std::runtime_error("--aov renders on one device (no --devices)");
         if (!devices.empty()) {
             MultiRenderer multi(devices, self_exchange);
             multi.setScene(scene.spheres);
@@ -185,7 +191,8 @@ int main(int argc, char* argv[])
         Renderer renderer(device);
         upload(renderer);
         renderer.setOneShot(true);                               // cpuRender renders its view once
-        std::vector<float3> c = renderer.render(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, /*normalise=*/true);
+        std::vector<float3> c = aov >= 0 ? renderer.renderAov(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, (uint32_t)aov, /*normalise=*/true)
+                                         : renderer.render(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, /*normalise=*/true);
         const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
         const spt_stats& st = renderer.stats();
         std::fprintf(stderr, "Rendering (%d spp) 100.00%%\nElapsed time: %lld ms\n", samps * 4, (long long)ms);   // :368,373

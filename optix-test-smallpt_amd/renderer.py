@@ -31,6 +31,16 @@ def _ray_array(rays):
     return np.ascontiguousarray(a, dtype=np.float32).view(RAY_DTYPE).reshape(-1)
 
 
+# spt_render_aov kinds (include/smallpt_mi355x.h SPT_AOV_*)
+AOV_KINDS = {"normal": 0, "albedo": 1, "uv": 2, "dist": 3}
+
+
+def _aov_kind(aov):
+    if not isinstance(aov, str) or aov not in AOV_KINDS:
+        raise ValueError(f"unknown aov {aov!r}: one of {', '.join(AOV_KINDS)}")
+    return AOV_KINDS[aov]
+
+
 class SptError(RuntimeError):
     pass
 
@@ -267,6 +277,32 @@ class Renderer:
         cam = camera if camera is not None else smallpt_camera(w, h)
         self._check(self._lib.spt_render_rows_device(
             self._h, C.byref(cam), w, h, row_begin, row_count, samps_per_cell, seed,
+            FLAG_NORMALISE if normalise else 0, C.c_void_p(out_tensor.data_ptr()),
+            C.c_void_p(stream) if stream else None))
+
+    def render_aov(self, w, h, samps_per_cell, aov="normal", seed=0, normalise=False, camera=None):
+        """First-hit feature buffer (spt_render_aov): 'normal', 'albedo', 'uv' or 'dist' of the closest hit of every camera sample of
+        ``render`` with the same arguments, folded in its order.  Returns ((h, w, 3) float32, stats)."""
+        kind = _aov_kind(aov)
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        out = np.empty((h, w, 3), dtype=np.float32)
+        st = SptStats()
+        self._check(self._lib.spt_render_aov(self._h, C.byref(cam), w, h, samps_per_cell, seed, kind,
+                                             FLAG_NORMALISE if normalise else 0, out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return out, _stats_dict(st)
+
+    def render_aov_rows_device(self, out_tensor, w, h, row_begin, row_count, samps_per_cell, aov="normal", seed=0,
+                               normalise=False, camera=None, stream=None):
+        """Enqueues rows [row_begin, row_begin+row_count) of ``render_aov`` into ``out_tensor`` (as ``render_rows_device``).  Asynchronous:
+        call ``sync()`` for completion + statistics."""
+        kind = _aov_kind(aov)
+        if out_tensor.numel() != row_count * w * 3 or not out_tensor.is_contiguous():
+            raise ValueError("out_tensor must be contiguous with row_count*w*3 float32 elements")
+        if str(out_tensor.dtype) != "torch.float32" or out_tensor.device.type != "cuda":
+            raise ValueError("out_tensor must be a float32 tensor on the GPU")
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        self._check(self._lib.spt_render_aov_rows_device(
+            self._h, C.byref(cam), w, h, row_begin, row_count, samps_per_cell, seed, kind,
             FLAG_NORMALISE if normalise else 0, C.c_void_p(out_tensor.data_ptr()),
             C.c_void_p(stream) if stream else None))
 
