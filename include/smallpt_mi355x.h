@@ -22,6 +22,9 @@
  *   cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits)      spt_trace_spheres() (host buffers),
  *     (smallpt.cpp:144-152; intersectGlobalSpheres :54-70 +     spt_trace_spheres_device() (device buffers, async)
  *     Sphere::makeHit scene.cpp:118-127)
+ *   OptiX Prime RTP_QUERY_TYPE_ANY over OptixRay::tmax          spt_occluded_spheres(), spt_occluded_rays() (host),
+ *     (smallpt.cpp:395-403,567,579): shadow / visibility       spt_occluded_spheres_device(),
+ *     rays with a bounded segment                                spt_occluded_rays_device() (device buffers, async)
  *   accumBuffer += outImage under accumBufferMutex and the      spt_progressive_begin / _frame / _snapshot / _end
  *     GL thread's copy of it (smallpt.cpp:881-883,924-940,       (accumulation buffer resident in HBM)
  *     955-959)
@@ -202,6 +205,28 @@ int  spt_trace_spheres(spt_ctx* ctx, const spt_ray* rays, uint64_t n, spt_hit* h
 /* The same query on DEVICE buffers of this context's device (n spt_ray in, n spt_hit out), enqueued on `hip_stream` (NULL = the context's
  * stream), returns without waiting.  Queries of one context run one after another, whatever their streams (they share a work list). */
 int  spt_trace_spheres_device(spt_ctx* ctx, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream);
+/* Any-hit (shadow / visibility) queries with a bounded segment: what OptiX Prime's RTP_QUERY_TYPE_ANY answers for the reference's OptixRay
+ * {origin, tmin, direction, tmax} (smallpt.cpp:395-403; the reference fills tmax = inf at :567 and asks RTP_QUERY_TYPE_CLOSEST at :579).
+ * occluded[i] = 1 exactly when the Hit h that the matching closest-hit query returns in SPT_ACCEL_EXHAUSTIVE mode has
+ *     h.dist < 1e20 && h.dist < tmax[i]          (strict, float32)
+ * else 0: some primitive's report lies strictly below min(tmax[i], 1e20) -- for a sphere the root intersectAnalytic chooses (> eps = 1e-4),
+ * for a triangle triIntersect's dist (> 0).  tmax = NULL means +inf for every ray (does the ray hit anything?); a NaN bound, a bound <= 0 --
+ * or <= 1e-4 for spheres -- never occludes; tmax[i] == h.dist is not occluded, the next float above it is.  There is no tmin (the reference
+ * uses 0).  One byte per ray (0 / 1).  The same for every accel mode: a report below the bound proves occlusion whatever structure finds it,
+ * and a walk stops there.
+ * Call conventions, messages and structures are those of the closest-hit entry of the same scene kind:
+ *   spt_occluded_spheres* (current SPHERE table, as spt_trace_spheres*): the structure spt_set_sphere_accel selects and the same routing of
+ *     rays outside a structure's proven range to the exhaustive loop; these queries and spt_trace_spheres* of one context run one after
+ *     another and spt_last_query_path reports them.
+ *   spt_occluded_rays* (current MESH scene, as spt_trace_rays*): SPT_ACCEL_EXHAUSTIVE = every triangle, SPT_ACCEL_BVH = the exact hierarchy,
+ *     SPT_ACCEL_AUTO = the hierarchy unless the scene has fewer than 256 triangles; SPT_ACCEL_BVH_FAST answers through the EXACT hierarchy
+ *     (built in every mode), so the fast mode's misses of rays in a triangle's plane never turn into a wrong answer.
+ * Host forms: blocking, wait for a pending render first.  Device forms: n spt_ray, n floats (or NULL) and n bytes on this context's device,
+ * enqueued on `hip_stream` (NULL = the context's stream), return without waiting.  A query changes no render state. */
+int  spt_occluded_spheres(spt_ctx* ctx, const spt_ray* rays, const float* tmax, uint64_t n, uint8_t* occluded);
+int  spt_occluded_spheres_device(spt_ctx* ctx, const void* d_rays, const void* d_tmax, uint64_t n, void* d_occluded, void* hip_stream);
+int  spt_occluded_rays(spt_ctx* ctx, const spt_ray* rays, const float* tmax, uint64_t n, uint8_t* occluded);
+int  spt_occluded_rays_device(spt_ctx* ctx, const void* d_rays, const void* d_tmax, uint64_t n, void* d_occluded, void* hip_stream);
 /* Host-only helper: makeSphereTriMesh(origin, radius, subdivLongitude) (scene.cpp:3-48): fills (L+1)(2L+1) positions and
  * normals and 4L^2 triangles (L = subdiv_longitude, default 32 at scene.h:17); returns the triangle count. */
 uint32_t spt_make_sphere_trimesh(const float origin[3], float radius, uint32_t subdiv_longitude,

@@ -800,8 +800,8 @@ int spt_trace_rays_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hi
     return 0;
 }
 
-// ray / hit staging buffers of the host-buffer queries (spt_trace_rays, spt_trace_spheres), kept between calls (traceRays is called once per
-// bounce by the reference's render loop)
+// ray / hit staging buffers of the host-buffer queries (spt_trace_rays, spt_trace_spheres; spt_occluded_* keep their bounds and bytes in the
+// hits buffer), kept between calls (traceRays is called once per bounce by the reference's render loop)
 static hipError_t ensure_trace_staging(spt_ctx* c, uint64_t n)
 {
     hipError_t e = hipSuccess;
@@ -846,8 +846,9 @@ int spt_trace_rays(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
 // Structure: the one spt_set_sphere_accel selects for renders -- SPT_ACCEL_GRID: the grid if the scene has one, else the hierarchy if built,
 // else the exhaustive loop; SPT_ACCEL_BVH: the hierarchy if built, else the exhaustive loop; SPT_ACCEL_EXHAUSTIVE: the exhaustive loop.
 // (Tables that need the guarded square root never walk: the grid refuses them at build time, the query keeps them off the hierarchy.)
-// Enqueued on `st`; touches no render state.
-static int trace_spheres_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, float* d_hits, hipStream_t st)
+// Enqueued on `st`; touches no render state.  d_occ != NULL: the occlusion form (spt_occluded_spheres*) -- bounds d_tmax (NULL: +inf), one byte
+// per ray in d_occ, d_hits unused -- through the same structure, fallback list and completion event.
+static int sphere_query_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, float* d_hits, const float* d_tmax, uint8_t* d_occ, hipStream_t st)
 {
     uint32_t path = spt::kQueryExhaustive;
     if (c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready) path = spt::kQueryGrid;
@@ -882,6 +883,22 @@ static int trace_spheres_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, fl
     for (uint64_t first = 0; first < n; first += spt::kQuerySlice) {
         const uint32_t m = (uint32_t)(n - first < spt::kQuerySlice ? n - first : spt::kQuerySlice);
         const float* const rays = d_rays + first * 6;
+        if (d_occ) {
+            const float* const tmax = d_tmax ? d_tmax + first : nullptr;
+            uint8_t* const occ = d_occ + first;
+            if (path == spt::kQueryExhaustive) {
+                SPT_HIP(c, spt_occ_exhaustive_launch(c->d_geom, c->n, rays, tmax, m, occ, nullptr, nullptr, 0, guard_all, st));
+                continue;
+            }
+            if (first != 0) SPT_HIP(c, hipMemsetAsync(c->d_qcount, 0, 4, st));
+            if (path == spt::kQueryGrid)
+                SPT_HIP(c, spt_occ_grid_launch(c->d_geom, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, where, rays, tmax, m, occ,
+                                               c->d_qlist, c->d_qcount, grid_blocks, st));
+            else
+                SPT_HIP(c, spt_occ_bvh_launch(&K, &M, rays, tmax, m, occ, c->d_qlist, c->d_qcount, st));
+            SPT_HIP(c, spt_occ_exhaustive_launch(c->d_geom, c->n, rays, tmax, m, occ, c->d_qlist, c->d_qcount, list_blocks, guard_all, st));
+            continue;
+        }
         float* const hits = d_hits + first * 11;
         if (path == spt::kQueryExhaustive) {
             SPT_HIP(c, spt_query_exhaustive_launch(c->d_geom, c->n, rays, m, hits, nullptr, nullptr, 0, guard_all, st));
@@ -916,8 +933,8 @@ int spt_trace_spheres_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d
     if (trace_spheres_check(c, "spt_trace_spheres_device", d_rays, n, d_hits)) return 1;
     if (n == 0) return 0;
     SPT_HIP(c, hipSetDevice(c->device));
-    return trace_spheres_enqueue(c, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits),
-                                 hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+    return sphere_query_enqueue(c, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits), nullptr, nullptr,
+                                hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
 }
 
 int spt_trace_spheres(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
@@ -930,10 +947,89 @@ int spt_trace_spheres(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits
     hipError_t e = ensure_trace_staging(c, n);
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_trace_rays, rays, n * sizeof(spt_ray), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return c->fail("spt_trace_spheres: %s", hipGetErrorString(e));
-    if (trace_spheres_enqueue(c, c->d_trace_rays, n, c->d_trace_hits, c->stream)) return 1;
+    if (sphere_query_enqueue(c, c->d_trace_rays, n, c->d_trace_hits, nullptr, nullptr, c->stream)) return 1;
     e = hipMemcpyAsync(hits, c->d_trace_hits, n * sizeof(spt_hit), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return c->fail("spt_trace_spheres: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// ---- any-hit queries under a per-ray bound: OptiX Prime's RTP_QUERY_TYPE_ANY over OptixRay {origin, tmin, direction, tmax} (smallpt.cpp:395-403,
+// 567, 579) -- occluded[i] = the exhaustive closest hit h of ray i has h.dist < 1e20 and h.dist < tmax[i] (spt_query.h occ_bound).  The call
+// conventions, messages and structures are those of the matching closest-hit entry.  The host forms stage the bounds and the bytes in the
+// hits buffer of the staging pair (4 + 1 <= 44 bytes per ray).
+int spt_occluded_spheres_device(spt_ctx* c, const void* d_rays, const void* d_tmax, uint64_t n, void* d_occluded, void* hip_stream)
+{
+    if (!c) return 1;
+    if (trace_spheres_check(c, "spt_occluded_spheres_device", d_rays, n, d_occluded)) return 1;
+    if (n == 0) return 0;
+    SPT_HIP(c, hipSetDevice(c->device));
+    return sphere_query_enqueue(c, static_cast<const float*>(d_rays), n, nullptr, static_cast<const float*>(d_tmax), static_cast<uint8_t*>(d_occluded),
+                                hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int spt_occluded_spheres(spt_ctx* c, const spt_ray* rays, const float* tmax, uint64_t n, uint8_t* occluded)
+{
+    if (!c) return 1;
+    if (trace_spheres_check(c, "spt_occluded_spheres", rays, n, occluded)) return 1;
+    if (n == 0) return 0;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
+    hipError_t e = ensure_trace_staging(c, n);
+    float* const d_tmax = tmax ? c->d_trace_hits : nullptr;
+    uint8_t* const d_occ = reinterpret_cast<uint8_t*>(c->d_trace_hits + n);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_trace_rays, rays, n * sizeof(spt_ray), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && tmax) e = hipMemcpyAsync(d_tmax, tmax, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return c->fail("spt_occluded_spheres: %s", hipGetErrorString(e));
+    if (sphere_query_enqueue(c, c->d_trace_rays, n, nullptr, d_tmax, d_occ, c->stream)) return 1;
+    e = hipMemcpyAsync(occluded, d_occ, n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return c->fail("spt_occluded_spheres: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// Mesh scenes: the mode of spt_trace_rays (mesh_mode(c, false)); one that resolves to SPT_ACCEL_BVH_FAST takes the exact hierarchy, whose
+// cones, plane tree and line tables build_accel makes in every mode -- the fast form's holes must not turn into a wrong yes / no.
+static int occluded_rays_enqueue(spt_ctx* c, const float* d_rays, const float* d_tmax, uint64_t n, uint8_t* d_occ, hipStream_t st)
+{
+    const int mode = mesh_mode(c, false);
+    c->last_mesh_mode = mode == SPT_ACCEL_BVH_FAST ? SPT_ACCEL_BVH : mode;
+    const spt::MParams M = mesh_params(c, c->last_mesh_mode);
+    SPT_HIP(c, spt_mesh_occluded(&M, d_rays, d_tmax, n, d_occ, st));
+    return 0;
+}
+
+int spt_occluded_rays_device(spt_ctx* c, const void* d_rays, const void* d_tmax, uint64_t n, void* d_occluded, void* hip_stream)
+{
+    if (!c) return 1;
+    if (!c->mesh_scene) return c->fail("spt_occluded_rays_device: no mesh scene set (call spt_set_meshes)");
+    if (n == 0) return 0;
+    if (!d_rays || !d_occluded) return c->fail("spt_occluded_rays_device: NULL argument");
+    if (n > 0x7FFFFFFFull * 256ull) return c->fail("spt_occluded_rays_device: too many rays for one call");
+    SPT_HIP(c, hipSetDevice(c->device));
+    return occluded_rays_enqueue(c, static_cast<const float*>(d_rays), static_cast<const float*>(d_tmax), n, static_cast<uint8_t*>(d_occluded),
+                                 hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int spt_occluded_rays(spt_ctx* c, const spt_ray* rays, const float* tmax, uint64_t n, uint8_t* occluded)
+{
+    if (!c) return 1;
+    if (!c->mesh_scene) return c->fail("spt_occluded_rays: no mesh scene set (call spt_set_meshes)");
+    if (n == 0) return 0;
+    if (!rays || !occluded) return c->fail("spt_occluded_rays: NULL argument");
+    if (n > 0x7FFFFFFFull * 256ull) return c->fail("spt_occluded_rays: too many rays for one call");
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
+    hipError_t e = ensure_trace_staging(c, n);
+    float* const d_tmax = tmax ? c->d_trace_hits : nullptr;
+    uint8_t* const d_occ = reinterpret_cast<uint8_t*>(c->d_trace_hits + n);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_trace_rays, rays, n * sizeof(spt_ray), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && tmax) e = hipMemcpyAsync(d_tmax, tmax, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return c->fail("spt_occluded_rays: %s", hipGetErrorString(e));
+    if (occluded_rays_enqueue(c, c->d_trace_rays, d_tmax, n, d_occ, c->stream)) return 1;
+    e = hipMemcpyAsync(occluded, d_occ, n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return c->fail("spt_occluded_rays: %s", hipGetErrorString(e));
     return 0;
 }
 

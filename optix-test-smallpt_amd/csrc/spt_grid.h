@@ -38,6 +38,12 @@
 //       every ray, like the hierarchy's always-list) -- goes through the exhaustive loop / is tested unconditionally.
 // Extra tests can never change the answer (every test is the reference's arithmetic on a sphere of the table), so the only
 // obligation is the one (1)-(3) discharge: every sphere whose key beats or ties the final answer has been tested.
+//   (5) occlusion under a bound b = min(tmax, 1e20) (spt_occluded_spheres, spt_grid.hip occ_grid).  The question is whether some report
+//       lies below b; a report found anywhere answers "yes" by itself, so only "no" needs coverage.  The walk takes b in place of the
+//       current nearest t of (3): it stops when the computed exit time of the current cell reaches b, and by (3) every cell that can hold a
+//       report t_j < b has been visited by then.  That holds for reports up to t_ok (1), so "no" stands only if b <= t_ok; a ray with b > t_ok,
+//       and every ray the route refuses (1) / (4), takes the exhaustive loop unless the walk already found a report below b.  The always-list
+//       is tested first, as in (4).
 #ifndef SPT_GRID_H
 #define SPT_GRID_H
 #include <hip/hip_runtime.h>

@@ -617,6 +617,151 @@ __global__ __launch_bounds__(kGridBlock) void query_grid(const float4* __restric
     }
 }
 
+// ---- batched occlusion queries against the sphere table (spt_occluded_spheres, spt_query.h occ_sphere_key) --------------------------------
+// A ray is settled by the first report below its bound (key < bkey): every report is the reference's arithmetic on a sphere of the table, so
+// one of them proves occlusion whatever structure found it.  Exhaustive loop: query_exhaustive's LDS tiles and per-wave square root; a lane
+// stops at its first report below the bound, a wave skips a tile once all its lanes are settled, and the workgroup stops loading tiles once
+// all of its lanes are (the barrier that guards the tile is the vote).  One byte per ray: a wave's 64 lanes store 64 contiguous bytes.
+template <bool GUARD>
+__device__ __forceinline__ bool occ_tile(const float4* s_geom, uint32_t cnt, f3 o, f3 d, uint32_t bkey)
+{
+    for (uint32_t k = 0; k < cnt; ++k)
+        if (sphere_key_g<GUARD>(s_geom[k], o, d) < bkey) return true;
+    return false;
+}
+
+template <bool LIST>
+__global__ __launch_bounds__(kQueryBlock) void occ_exhaustive(const float4* __restrict__ geom, uint32_t n, const float* __restrict__ rays,
+                                                              const float* __restrict__ tmax, uint32_t nrays, uint8_t* __restrict__ occ_out,
+                                                              const uint32_t* __restrict__ list, const uint32_t* __restrict__ qcount, int guard_all)
+{
+    __shared__ float4 s_geom[kQTile];
+    const uint32_t count = LIST ? qcount[0] : nrays;
+    const bool one_tile = n <= kQTile;
+    if (one_tile) {
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) s_geom[i] = geom[i];
+        __syncthreads();
+    }
+    for (uint32_t base = blockIdx.x * kQueryBlock; base < count; base += gridDim.x * kQueryBlock) {     // workgroup-uniform
+        const uint32_t slot = base + threadIdx.x;
+        const bool active = slot < count;
+        const uint32_t r = active ? (LIST ? list[slot] : slot) : 0u;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        uint32_t bkey = 0u;
+        if (active) {
+            const float* q = rays + (size_t)r * 6;
+            o = mk(q[0], q[1], q[2]); d = mk(q[3], q[4], q[5]);
+            bkey = occ_sphere_key(tmax ? tmax[r] : __builtin_inff());
+        }
+        const bool guard = guard_all != 0 || __ballot(active && !query_ray_unguarded(o.x, o.y, o.z, d.x, d.y, d.z)) != 0ull;   // wave-uniform
+        bool occ = false, done = bkey == 0u;                     // (inactive lanes have bkey = 0)
+        for (uint32_t tb = 0; tb < n; tb += kQTile) {
+            const uint32_t cnt = n - tb < kQTile ? n - tb : kQTile;
+            if (!one_tile) {
+                if (__syncthreads_or(done ? 0 : 1) == 0) break;  // the previous tile is no longer read; every lane settled: no more tiles
+                for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) s_geom[i] = geom[tb + i];
+                __syncthreads();
+            }
+            if (__ballot(!done) == 0ull) continue;              // wave-uniform: the wave joins the next tile's barriers only
+            if (!done) {
+                occ = guard ? occ_tile<true>(s_geom, cnt, o, d, bkey) : occ_tile<false>(s_geom, cnt, o, d, bkey);
+                done = occ;
+            }
+        }
+        if (active) occ_out[r] = occ ? 1u : 0u;
+    }
+}
+
+// The grid under a bound: query_grid's walk with the bound in place of the running nearest t.  The always-list first, stopping at the first
+// report below the bound; then the walk, which a lane leaves at its first report below the bound or when the cell exit reaches the bound
+// (spt_grid.h (3), (5)).  A ray that is not occluded is covered only if the route admitted it and its bound is <= t_ok (spt_grid.h (5)); the
+// others go to the fallback list for occ_exhaustive<true>, as do all rays the route refuses.
+template <int WHERE>
+__global__ __launch_bounds__(kGridBlock) void occ_grid(const float4* __restrict__ geom, const GridParams G, const uint32_t* __restrict__ g_cells,
+                                                       const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always,
+                                                       const float* __restrict__ rays, const float* __restrict__ tmax, uint32_t nrays,
+                                                       uint8_t* __restrict__ occ_out, uint32_t* __restrict__ list, uint32_t* __restrict__ qcount)
+{
+    constexpr bool GLOBAL_TABLES = WHERE == 1, GLOBAL_GEOM = WHERE != 0;
+    extern __shared__ float4 s_lds_geom[];
+    uint32_t* const s_lds_cells = reinterpret_cast<uint32_t*>(s_lds_geom + (GLOBAL_GEOM ? 0u : (G.n ? G.n : 1u)));
+    uint16_t* const s_lds_refs = reinterpret_cast<uint16_t*>(s_lds_cells + G.ncells);
+    if (!GLOBAL_GEOM) for (uint32_t i = threadIdx.x; i < G.n; i += blockDim.x) s_lds_geom[i] = geom[i];
+    if (!GLOBAL_TABLES) {
+        for (uint32_t i = threadIdx.x; i < G.ncells; i += blockDim.x) s_lds_cells[i] = g_cells[i];
+        for (uint32_t i = threadIdx.x; i < G.nrefs; i += blockDim.x) s_lds_refs[i] = g_refs[i];
+        for (uint32_t i = threadIdx.x; i <= G.nalways; i += blockDim.x) s_lds_refs[G.nrefs + i] = i < G.nalways ? (uint16_t)g_always[i] : (uint16_t)0;
+    }
+    auto geom_at = [&](uint32_t i) -> float4 { return GLOBAL_GEOM ? geom[i] : s_lds_geom[i]; };
+    auto cell_at = [&](uint32_t ci) -> uint32_t { return GLOBAL_TABLES ? g_cells[ci] : s_lds_cells[ci]; };
+    auto ref_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? (uint32_t)g_refs[k] : (uint32_t)s_lds_refs[k]; };
+    auto always_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? g_always[k] : (uint32_t)s_lds_refs[G.nrefs + k]; };
+    __syncthreads();
+
+    const uint32_t lane = lane_id_g();
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t base = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 64u; base < nrays; base += waves * 64u) {   // wave-uniform
+        const uint32_t r = base + lane;
+        const bool active = r < nrays;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        uint32_t bkey = 0u;
+        if (active) {
+            const float* q = rays + (size_t)r * 6;
+            o = mk(q[0], q[1], q[2]); d = mk(q[3], q[4], q[5]);
+            bkey = occ_sphere_key(tmax ? tmax[r] : __builtin_inff());
+        }
+        const float bound = __uint_as_float(bkey + kGEpsBias);  // min(tmax, 1e20) for every lane with bkey != 0
+        float t_ok = 0.f;
+        const bool walk = bkey != 0u && query_ray_route(kQueryGrid, G, o.x, o.y, o.z, d.x, d.y, d.z, t_ok) == kQueryGrid;
+        bool occ = false;
+        for (uint32_t k = 0; k < G.nalways; ++k) {              // walls / lights
+            if (__ballot(walk && !occ) == 0ull) break;          // wave-uniform
+            const uint32_t i = always_at(k);
+            const float4 g = geom_at(i);
+            if (walk && !occ) occ = sphere_key_g(g, o, d) < bkey;
+        }
+        float wtx = 0.f, wty = 0.f, wtz = 0.f, wdx = 0.f, wdy = 0.f, wdz = 0.f;   // the walk (GridWalk) in separate registers
+        int32_t wsx = 0, wsy = 0, wsz = 0;
+        uint32_t wci = 0, cur = 0, end = 0;                      // end = 0 outside the walk
+        bool walking = walk && !occ;
+        if (walking) {
+            GridWalk w;
+            grid_walk_begin(G, o.x, o.y, o.z, d.x, d.y, d.z, w);
+            wtx = w.tx; wty = w.ty; wtz = w.tz; wdx = w.dtx; wdy = w.dty; wdz = w.dtz; wsx = w.sx; wsy = w.sy; wsz = w.sz; wci = w.ci;
+            const uint32_t h = cell_at(wci);                     // the start cell is clamped into the table: never a border cell
+            cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+        }
+        uint32_t nwalk = (uint32_t)__popcll(__ballot(walking));
+        while (nwalk != 0u) {
+            const bool wt = cur < end;
+            const uint32_t nt = (uint32_t)__popcll(__ballot(wt));
+            if (2u * nt >= nwalk) {                              // TEST the next sphere of the lane's cell
+                if (wt) {
+                    const uint32_t i = ref_at(cur);
+                    ++cur;
+                    if (sphere_key_g(geom_at(i), o, d) < bkey) { occ = true; walking = false; end = cur; }   // settled: leaves the walk
+                }
+            } else {                                             // STEP: leave the cell (all its spheres are tested)
+                if (walking && !wt) {
+                    const float m = __builtin_fminf(wtx, __builtin_fminf(wty, wtz));   // grid_walk_exit
+                    bool stop = !(m < bound);                    // spt_grid.h (5): every report below the bound is covered
+                    if (!stop) {
+                        grid_walk_step(wtx, wty, wtz, wdx, wdy, wdz, wsx, wsy, wsz, wci, m);
+                        const uint32_t h = cell_at(wci);
+                        stop = h == kGridBorder;                 // left the table
+                        cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+                    }
+                    if (stop) { walking = false; end = 0; }
+                }
+                nwalk = (uint32_t)__popcll(__ballot(walking));
+            }
+        }
+        const bool fallback = bkey != 0u && !occ && (!walk || bound > t_ok);    // spt_grid.h (1), (4), (5): the exhaustive loop answers
+        query_append(fallback, r, list, qcount, reinterpret_cast<unsigned long long*>(qcount + 2));
+        if (active) occ_out[r] = occ ? 1u : 0u;
+    }
+}
+
 // ---- first-hit feature buffers (spt_render_aov, spt_aov.h) over the sphere table ----------------------------------------------------------
 // One lane per D9 task (a block of one jitter cell's samples), the lanes of a wave dealt an 8 x 8 tile of pixels (spt_deal.h deal_task_tiles);
 // per sample: the camera ray, its closest hit, acc += the selected value; then cells[task].  No bounces: no pools, stacks or watchdog.
@@ -888,4 +1033,41 @@ extern "C" hipError_t spt_aov_grid_launch(const spt::KParams* K, const spt::Grid
     if (where == 0) return launch_aov_grid<0>(K, G, d_cells, d_refs, d_always, kind, blocks, lds, stream);
     if (where == 1) return launch_aov_grid<1>(K, G, d_cells, d_refs, d_always, kind, blocks, lds, stream);
     return launch_aov_grid<2>(K, G, d_cells, d_refs, d_always, kind, blocks, lds, stream);
+}
+
+extern "C" hipError_t spt_occ_exhaustive_launch(const float4* geom, uint32_t n, const float* rays, const float* tmax, uint32_t nrays, uint8_t* occ,
+                                                const uint32_t* list, const uint32_t* qcount, uint32_t list_blocks, int guard_all, hipStream_t stream)
+{
+    if (nrays == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)nrays + spt::kQueryBlock - 1) / spt::kQueryBlock);
+    if (list) hipLaunchKernelGGL(spt::occ_exhaustive<true>, dim3(blocks < list_blocks ? blocks : list_blocks), dim3(spt::kQueryBlock), 0, stream,
+                                 geom, n, rays, tmax, nrays, occ, list, qcount, guard_all);
+    else hipLaunchKernelGGL(spt::occ_exhaustive<false>, dim3(blocks), dim3(spt::kQueryBlock), 0, stream, geom, n, rays, tmax, nrays, occ, list, qcount, guard_all);
+    return hipGetLastError();
+}
+
+template <int WHERE>
+static hipError_t launch_occ_grid(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs, const uint32_t* d_always,
+                                  const float* rays, const float* tmax, uint32_t nrays, uint8_t* occ, uint32_t* list, uint32_t* qcount, uint32_t blocks,
+                                  size_t lds, hipStream_t stream)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::occ_grid<WHERE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((spt::occ_grid<WHERE>), dim3(blocks), dim3(spt::kGridBlock), lds, stream, geom, *G, d_cells, d_refs, d_always, rays, tmax, nrays, occ, list, qcount);
+    return hipGetLastError();
+}
+
+// blocks: persistent workgroups of kGridBlock threads (the caller sizes them from the CU count); where as in spt_grid_launch
+extern "C" hipError_t spt_occ_grid_launch(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
+                                          const uint32_t* d_always, int where, const float* rays, const float* tmax, uint32_t nrays, uint8_t* occ,
+                                          uint32_t* list, uint32_t* qcount, uint32_t blocks, hipStream_t stream)
+{
+    if (where < 0 || where > 2) return hipErrorInvalidValue;
+    if (nrays == 0) return hipSuccess;
+    const uint32_t need = (uint32_t)(((uint64_t)nrays + spt::kGridBlock - 1) / spt::kGridBlock);
+    if (blocks > need) blocks = need;
+    const size_t lds = where == 1 ? 0 : (where == 2 ? spt_grid_lds_bytes_tables(G) : spt_grid_lds_bytes(G));
+    if (where == 0) return launch_occ_grid<0>(geom, G, d_cells, d_refs, d_always, rays, tmax, nrays, occ, list, qcount, blocks, lds, stream);
+    if (where == 1) return launch_occ_grid<1>(geom, G, d_cells, d_refs, d_always, rays, tmax, nrays, occ, list, qcount, blocks, lds, stream);
+    return launch_occ_grid<2>(geom, G, d_cells, d_refs, d_always, rays, tmax, nrays, occ, list, qcount, blocks, lds, stream);
 }

@@ -212,6 +212,74 @@ __device__ __forceinline__ uint32_t closest_triangle_bvh(const MParams& M, uint3
     return near_tri;
 }
 
+// ---- occlusion queries of a mesh scene (spt_occluded_rays, spt_query.h occ_triangle_key) ---------------------------------------
+// A triangle's report t (tri_test, the closest-hit arithmetic) occludes when key(t) = bits(t) - 1 < bkey: 0 < t < min(tmax, 1e20).  One such
+// report settles the ray, whichever structure found it.
+__device__ __forceinline__ bool tri_occludes(const float4 r0, const float4 r1, const float4 r2, f3 ro, f3 rd, uint32_t bkey)
+{
+    float u, v;
+    return __float_as_uint(tri_test(r0, r1, r2, ro, rd, u, v)) - 1u < bkey;
+}
+
+// closest_triangle's LDS tiles with early exits: a lane stops at its first report below the bound, a wave skips the rest of a tile once all
+// its lanes are settled, and the workgroup stops staging tiles once all of its lanes are (the barrier before a tile is the vote).  All threads
+// of the workgroup call this together; bkey = 0 (inactive lanes, bounds nothing can beat) is settled from the start.
+__device__ __forceinline__ bool any_triangle(const float4* __restrict__ tris, uint32_t ntris, float4* s_tile, f3 ro, f3 rd, uint32_t bkey)
+{
+    bool occ = false, done = bkey == 0u;
+    for (uint32_t base = 0; base < ntris; base += kTile) {
+        const uint32_t cnt = ntris - base < (uint32_t)kTile ? ntris - base : (uint32_t)kTile;
+        if (__syncthreads_or(done ? 0 : 1) == 0) break;        // the previous tile is no longer read; every lane settled
+        for (uint32_t i = threadIdx.x; i < 3u * cnt; i += blockDim.x) s_tile[i] = tris[3u * (size_t)base + i];
+        __syncthreads();
+        if (__ballot(!done) == 0ull) continue;                 // wave-uniform
+        if (!done) {
+            uint32_t k = 0;
+            for (; k + 4 <= cnt; k += 4) {                     // four records (12 broadcast reads) in flight per LDS round trip
+                const float4* r = s_tile + 3 * k;
+                const float4 a0 = r[0], a1 = r[1], a2 = r[2], b0 = r[3], b1 = r[4], b2 = r[5];
+                const float4 c0 = r[6], c1 = r[7], c2 = r[8], d0 = r[9], d1 = r[10], d2 = r[11];
+                if (tri_occludes(a0, a1, a2, ro, rd, bkey) | tri_occludes(b0, b1, b2, ro, rd, bkey) |
+                    tri_occludes(c0, c1, c2, ro, rd, bkey) | tri_occludes(d0, d1, d2, ro, rd, bkey)) { occ = true; break; }
+            }
+            for (; !occ && k < cnt; ++k) occ = tri_occludes(s_tile[3 * k], s_tile[3 * k + 1], s_tile[3 * k + 2], ro, rd, bkey);
+            done = occ;
+        }
+    }
+    return occ;
+}
+
+// The exact hierarchy under a bound (spt_tribvh.h): the spatial walk with tcut = min(tmax, 1e20) * 1.0001 -- a box it skips holds no report
+// below the bound, by (1) --, then the plane tree (2) and the line table / tree (3), each only while the ray is unoccluded.  The first report
+// below the bound sets tcut to NaN: tri_box_child's `tn <= tcut` is then false for every box, those containing the origin included (a
+// negative tcut would not reject a box whose entry parameter is negative), so the walk only unwinds its stack; the leaf and triangle
+// callbacks test nothing more.  No camera-plane list: a query's rays come from anywhere.
+__device__ __forceinline__ bool any_triangle_bvh(const MParams& M, uint32_t* s_stack, bool active, f3 ro, f3 rd, uint32_t bkey)
+{
+    bool occ = false;
+    if (active) {
+        float tcut = __uint_as_float(bkey + 1u) * 1.0001f;
+        LdsStack st{s_stack};
+        auto consider = [&](const float4* r) {
+            if (!occ && tri_occludes(r[0], r[1], r[2], ro, rd, bkey)) { occ = true; tcut = __builtin_nanf(""); }
+        };
+        TriQuery q;
+        tri_query(ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, q);
+        const float ivx = __builtin_amdgcn_rcpf(rd.x), ivy = __builtin_amdgcn_rcpf(rd.y), ivz = __builtin_amdgcn_rcpf(rd.z);   // 1 ulp; inside the widening
+        auto leaf = [&](uint32_t first, uint32_t cnt) {
+            for (uint32_t k = 0; k < cnt && !occ; ++k) consider(M.bvh_tris + 3 * (size_t)(first + k));
+        };
+        auto by_index = [&](uint32_t g) { consider(M.tris + 3 * (size_t)g); };
+        tri_walk_boxes<true>(M.bvh_nodes, M.bvh_cones, ro.x, ro.y, ro.z, ivx, ivy, ivz, q.h[0], q.h[1], q.h[2], tcut, st, leaf);
+        if (!occ && M.plane_nodes) tri_walk_planes(M.plane_nodes, q, st, by_index);
+        if (!occ) {
+            if (M.flat_lines) tri_scan_lines(M.flat_lines, M.flat_line_index, M.nline_slots, q, st, by_index);
+            else if (M.line_nodes) tri_walk_lines(M.line_nodes, q, st, by_index);
+        }
+    }
+    return occ;
+}
+
 // ---- sphere tables through a hierarchy (spt_set_sphere_accel; spt_bvh.h build_sphere_bvh) -----------------------------------
 // intersectAnalytic of one sphere record {c, r*r} on the integer keys of the sphere kernels (scene.cpp:129-140, smallpt.cpp:59-65):
 // key(t) = bits(t) - (bits(eps) + 1); returns the smaller of the two root keys (NaN roots give keys above every valid one).
@@ -238,19 +306,29 @@ __device__ __forceinline__ uint32_t sphere_key(const float4 g, f3 o, f3 d)
 // of this slab test (~3u D) and of the measured eta (8u).  Hence a sphere whose reported key beats the final answer is never
 // skipped: its box is entered at a parameter <= its t <= the current nearest.  NaN from 0 * inf drops out of v_min/v_max (no
 // constraint).  (One pad for the whole traversal from the root's extent was measured: fatter boxes, 4-12 % slower.)
+//
+// ANY (occlusion queries, spt_occluded_spheres): bound_key = occ_sphere_key(tmax) (> 0) takes the place of the nearest key and tcut starts at
+// the bound, widened like the nearest distance; the walk ends at the first report below the bound (its index is returned, else 0xFFFFFFFF).
+// A box skipped against that tcut holds no report below the bound, by the argument above.
+template <bool ANY = false>
 __device__ __forceinline__ uint32_t closest_sphere_bvh(const KParams& K, const MParams& M, const float4* nodes, const float4* leaf_geom, const uint32_t* leaf_index,
-                                                    uint32_t* s_stack, bool active, f3 ro, f3 rd, float& t_out)
+                                                    uint32_t* s_stack, bool active, f3 ro, f3 rd, float& t_out, uint32_t bound_key = kSphInfKey)
 {
-    uint32_t near_key = kSphInfKey, near_i = 0xFFFFFFFFu;
+    uint32_t near_key = ANY ? bound_key : kSphInfKey, near_i = 0xFFFFFFFFu;
     if (active) {
-        float tcut = 1e20f;
+        float tcut = ANY ? __uint_as_float(bound_key + kSphEpsBias) * 1.0001f : 1e20f;
         auto consider = [&](const float4 g, uint32_t index) {
             const uint32_t key = sphere_key(g, ro, rd);
-            if (key < near_key || (key == near_key && index < near_i)) {       // ascending index + strict '<' of smallpt.cpp:61
+            if (ANY) {
+                if (key < near_key) { near_key = key; near_i = index; }
+            } else if (key < near_key || (key == near_key && index < near_i)) {       // ascending index + strict '<' of smallpt.cpp:61
                 if (key < kSphInfKey) { near_key = key; near_i = index; tcut = __uint_as_float(key + kSphEpsBias) * 1.0001f; }
             }
         };
-        for (uint32_t k = 0; k < M.nalways; ++k) { const uint32_t i = M.always[k]; consider(K.geom[i], i); }
+        for (uint32_t k = 0; k < M.nalways; ++k) {
+            if (ANY && near_i != 0xFFFFFFFFu) break;
+            const uint32_t i = M.always[k]; consider(K.geom[i], i);
+        }
         const f3 iv = mk(__builtin_amdgcn_rcpf(rd.x), __builtin_amdgcn_rcpf(rd.y), __builtin_amdgcn_rcpf(rd.z));
         // inflation per unit of D for THIS ray: 2^-7 for the rounding budget, plus 2.1 sqrt(|eta|) for a direction whose squared
         // length is 1 + eta (intersectAnalytic assumes 1; mirror reflections are not renormalised and drift over a long chain):
@@ -258,7 +336,7 @@ __device__ __forceinline__ uint32_t closest_sphere_bvh(const KParams& K, const M
         const float kpad = (1.0f / 128.0f + 2.1f * __builtin_amdgcn_sqrtf(__builtin_fabsf(dot(rd, rd) - 1.0f) + 0x1p-21f)) * 1.001f;
         uint32_t sp = 0;
         int cur = 0;
-        for (;;) {
+        if (!ANY || near_i == 0xFFFFFFFFu) for (;;) {      // (ANY: a ray the always-list settled does not walk)
             if (cur >= 0) {
                 const float4* nd = nodes + 4 * (size_t)cur;
                 const float4 a = nd[0], b = nd[1], c = nd[2], d = nd[3];
@@ -293,6 +371,7 @@ __device__ __forceinline__ uint32_t closest_sphere_bvh(const KParams& K, const M
             } else {
                 const uint32_t code = (uint32_t)~cur, first = code >> 4, cnt = code & 15u;
                 for (uint32_t k = 0; k < cnt; ++k) consider(leaf_geom[first + k], leaf_index[first + k]);
+                if (ANY && near_i != 0xFFFFFFFFu) break;
             }
             if (sp == 0u) break;
             --sp;
@@ -379,6 +458,50 @@ __global__ __launch_bounds__(kMeshBlock) void trace_spheres_bvh(const KParams K,
     float* const out = hits + (size_t)r * 11;
 #pragma unroll
     for (int k = 0; k < 11; ++k) out[k] = h.f[k];
+}
+
+// Occlusion queries (spt_occluded_spheres) through the sphere hierarchy: trace_spheres_bvh with closest_sphere_bvh<true>.  Every lane writes
+// its byte (0 for the rays the route hands to the exhaustive loop, whose list form overwrites it); rays whose bound nothing can beat stay 0.
+__global__ __launch_bounds__(kMeshBlock) void occ_spheres_bvh(const KParams K, const MParams M, const float* __restrict__ rays, const float* __restrict__ tmax,
+                                                              uint32_t nrays, uint8_t* __restrict__ occ_out, uint32_t* __restrict__ list, uint32_t* __restrict__ qcount)
+{
+    extern __shared__ float4 s_tile[];
+    const uint32_t r = blockIdx.x * kMeshBlock + threadIdx.x;
+    const bool active = r < nrays;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    uint32_t bkey = 0u;
+    if (active) {
+        const float* q = rays + (size_t)r * 6;
+        ro = mk(q[0], q[1], q[2]); rd = mk(q[3], q[4], q[5]);
+        bkey = occ_sphere_key(tmax ? tmax[r] : __builtin_inff());
+    }
+    float t_ok;
+    const GridParams G{};
+    const bool walk = bkey != 0u && query_ray_route(kQueryBvh, G, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, t_ok) == kQueryBvh;
+    float t;
+    const uint32_t i = closest_sphere_bvh<true>(K, M, M.bvh_nodes, M.bvh_tris, M.bvh_index, reinterpret_cast<uint32_t*>(s_tile), walk, ro, rd, t, bkey);
+    query_append(bkey != 0u && !walk, r, list, qcount, reinterpret_cast<unsigned long long*>(qcount + 2));
+    if (active) occ_out[r] = i != 0xFFFFFFFFu ? 1u : 0u;
+}
+
+// Occlusion queries of a mesh scene (spt_occluded_rays): one lane per ray, one byte per ray (a wave stores 64 contiguous bytes).
+// BVH = the exact hierarchy (any_triangle_bvh), else the exhaustive loop (any_triangle).
+template <bool BVH>
+__global__ __launch_bounds__(kMeshBlock) void occluded_rays(const MParams M, const float* __restrict__ rays, const float* __restrict__ tmax, uint64_t nrays,
+                                                            uint8_t* __restrict__ occ_out)
+{
+    extern __shared__ float4 s_tile[];
+    const uint64_t i = (uint64_t)blockIdx.x * kMeshBlock + threadIdx.x;
+    const bool active = i < nrays;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    uint32_t bkey = 0u;
+    if (active) {
+        ro = mk(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]); rd = mk(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+        bkey = occ_triangle_key(tmax ? tmax[i] : __builtin_inff());
+    }
+    const bool occ = BVH ? any_triangle_bvh(M, reinterpret_cast<uint32_t*>(s_tile), bkey != 0u, ro, rd, bkey)
+                         : any_triangle(M.tris, M.ntris, s_tile, ro, rd, bkey);
+    if (active) occ_out[i] = occ ? 1u : 0u;
 }
 
 // ---- path tracer over the mesh scene ------------------------------------------------------------------------------
@@ -762,5 +885,23 @@ extern "C" hipError_t spt_aov_mesh_launch(const spt::KParams* K, const spt::MPar
 {
     if (M->bvh_nodes) hipLaunchKernelGGL(spt::aov_mesh<1>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind);
     else hipLaunchKernelGGL(spt::aov_mesh<0>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, kind);
+    return hipGetLastError();
+}
+
+// K: geom = the sphere table; M: the sphere hierarchy, as for spt_query_bvh_launch.  nrays <= kQuerySlice.
+extern "C" hipError_t spt_occ_bvh_launch(const spt::KParams* K, const spt::MParams* M, const float* rays, const float* tmax, uint32_t nrays, uint8_t* occ,
+                                         uint32_t* list, uint32_t* qcount, hipStream_t stream)
+{
+    if (nrays == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)nrays + spt::kMeshBlock - 1) / spt::kMeshBlock);
+    hipLaunchKernelGGL(spt::occ_spheres_bvh, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, rays, tmax, nrays, occ, list, qcount);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t spt_mesh_occluded(const spt::MParams* M, const float* d_rays, const float* d_tmax, uint64_t nrays, uint8_t* d_occ, hipStream_t stream)
+{
+    const uint64_t blocks = (nrays + spt::kMeshBlock - 1) / spt::kMeshBlock;
+    if (M->bvh_nodes) hipLaunchKernelGGL(spt::occluded_rays<true>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *M, d_rays, d_tmax, nrays, d_occ);
+    else hipLaunchKernelGGL(spt::occluded_rays<false>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *M, d_rays, d_tmax, nrays, d_occ);
     return hipGetLastError();
 }

@@ -42,6 +42,21 @@ SPT_HD uint32_t query_ray_route(uint32_t structure, const GridParams& G, float o
     return grid_ray_ok(G, ox, oy, oz, dx, dy, dz, t_ok) ? kQueryGrid : kQueryExhaustive;
 }
 
+// Occlusion queries (spt_occluded_*): ray i is occluded when the exhaustive closest hit h has h.dist < 1e20 and h.dist < tmax[i], i.e. when some
+// primitive's report lies strictly below b = min(tmax, 1e20) (a NaN tmax stays NaN: never occluded).  As a key of the closest-hit kernels a
+// report beats the bound when key(t) < occ_*_key(tmax); 0 = nothing can (b <= eps for spheres, b <= 0 for triangles, NaN).
+SPT_HD float occ_bound(float tmax) { return tmax >= 1e20f ? 1e20f : tmax; }
+SPT_HD uint32_t occ_sphere_key(float tmax)            // key(t) = bits(t) - (bits(1e-4f) + 1): reports are roots > eps
+{
+    const float b = occ_bound(tmax);
+    return b > 1e-4f ? __builtin_bit_cast(uint32_t, b) - (0x38D1B717u + 1u) : 0u;
+}
+SPT_HD uint32_t occ_triangle_key(float tmax)          // key(t) = bits(t) - 1: reports are t > 0
+{
+    const float b = occ_bound(tmax);
+    return b > 0.0f ? __builtin_bit_cast(uint32_t, b) - 1u : 0u;
+}
+
 #if defined(SPT_QUERY_DEVICE)      // the kernel translation units (spt_grid.hip, spt_mesh.hip: after spt_device.h)
 // Hit record of scene.h:31-43 for the sphere `g` = {centre, r*r} hit at t (Sphere::makeHit, scene.cpp:118-127): x = o + d t (scene.cpp:137),
 // n = normalize(x - centre) (:124; the guarded form: x may sit on the centre of a tiny sphere), triId = 0, uv = 0.  Miss: dist = 1e20, rest 0.
@@ -87,4 +102,15 @@ extern "C" hipError_t spt_query_grid_launch(const float4* geom, const spt::GridP
                                             uint32_t* list, uint32_t* qcount, uint32_t blocks, hipStream_t stream);
 extern "C" hipError_t spt_query_bvh_launch(const spt::KParams* K, const spt::MParams* M, const float* rays, uint32_t nrays, float* hits,
                                            uint32_t* list, uint32_t* qcount, hipStream_t stream);
+// Occlusion forms (spt_occluded_spheres*): tmax = nrays bounds (NULL: +inf), occ = nrays bytes (0 / 1) in place of the hits.  The walks write
+// every ray's byte (0 for the rays they hand over); the list form of the exhaustive loop overwrites the listed ones.
+extern "C" hipError_t spt_occ_exhaustive_launch(const float4* geom, uint32_t n, const float* rays, const float* tmax, uint32_t nrays, uint8_t* occ,
+                                                const uint32_t* list, const uint32_t* qcount, uint32_t list_blocks, int guard_all, hipStream_t stream);
+extern "C" hipError_t spt_occ_grid_launch(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
+                                          const uint32_t* d_always, int where, const float* rays, const float* tmax, uint32_t nrays, uint8_t* occ,
+                                          uint32_t* list, uint32_t* qcount, uint32_t blocks, hipStream_t stream);
+extern "C" hipError_t spt_occ_bvh_launch(const spt::KParams* K, const spt::MParams* M, const float* rays, const float* tmax, uint32_t nrays, uint8_t* occ,
+                                         uint32_t* list, uint32_t* qcount, hipStream_t stream);
+// Mesh scenes (spt_occluded_rays*): M as for spt_mesh_trace_rays; bvh_nodes set = the exact hierarchy (the caller passes its cones and trees).
+extern "C" hipError_t spt_mesh_occluded(const spt::MParams* M, const float* d_rays, const float* d_tmax, uint64_t nrays, uint8_t* d_occ, hipStream_t stream);
 #endif

@@ -77,6 +77,7 @@ public:
     //   addTriangleMesh(mesh) for every instance + build()  ->  setMeshes(meshes, materials)   (materials[i] <-> instance i, :170)
     //   Vector<Hit> traceRays(const PathContrib*, size_t)    ->  traceRays(rays, n)
     //   cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits) ->  traceSpheres(rays, n)
+    //   RTP_QUERY_TYPE_ANY with OptixRay::tmax (:395-403,579)  ->  occludedSpheres / occludedRays(rays, tmax, n)
     void setMeshes(const std::vector<TriMesh>& meshes, const std::vector<Material>& materials)
     {
         if (meshes.size() != materials.size()) throw std::runtime_error("setMeshes: one material per mesh instance");
@@ -123,6 +124,30 @@ public:
     void traceSpheresDevice(const void* dRays, size_t n, void* dHits, void* hipStream = nullptr)
     {
         check(spt_trace_spheres_device(ctx_, dRays, (uint64_t)n, dHits, hipStream));
+    }
+
+    // Any-hit (shadow / visibility) queries, OptiX Prime's RTP_QUERY_TYPE_ANY over OptixRay::tmax (smallpt.cpp:395-403,567,579): one byte per
+    // ray, 1 where the exhaustive closest hit has dist < 1e20 and dist < tmax[i]; tmax = nullptr means +inf (contract in include/smallpt_mi355x.h)
+    std::vector<uint8_t> occludedSpheres(const Ray* rays, const float* tmax, size_t n)
+    {
+        std::vector<uint8_t> occ(n);
+        check(spt_occluded_spheres(ctx_, reinterpret_cast<const spt_ray*>(rays), tmax, (uint64_t)n, occ.data()));
+        return occ;
+    }
+    void occludedSpheresDevice(const void* dRays, const void* dTmax, size_t n, void* dOccluded, void* hipStream = nullptr)
+    {
+        check(spt_occluded_spheres_device(ctx_, dRays, dTmax, (uint64_t)n, dOccluded, hipStream));
+    }
+    // the same against the current mesh scene
+    std::vector<uint8_t> occludedRays(const Ray* rays, const float* tmax, size_t n)
+    {
+        std::vector<uint8_t> occ(n);
+        check(spt_occluded_rays(ctx_, reinterpret_cast<const spt_ray*>(rays), tmax, (uint64_t)n, occ.data()));
+        return occ;
+    }
+    void occludedRaysDevice(const void* dRays, const void* dTmax, size_t n, void* dOccluded, void* hipStream = nullptr)
+    {
+        check(spt_occluded_rays_device(ctx_, dRays, dTmax, (uint64_t)n, dOccluded, hipStream));
     }
 
     const spt_stats& stats() const { return stats_; }

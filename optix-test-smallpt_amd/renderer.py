@@ -31,6 +31,51 @@ def _ray_array(rays):
     return np.ascontiguousarray(a, dtype=np.float32).view(RAY_DTYPE).reshape(-1)
 
 
+def _occluded_host(r, who, name, rays, tmax):
+    """Renderer.occluded_spheres / occluded_rays: every argument is checked before the library is called."""
+    rays = _ray_array(rays)
+    n = len(rays)
+    tm = None
+    if tmax is not None:
+        tm = np.asarray(tmax)
+        if not (np.issubdtype(tm.dtype, np.floating) or np.issubdtype(tm.dtype, np.integer)) or tm.shape != (n,):
+            raise ValueError(f"{who}: tmax must be real numbers of shape ({n},), got dtype {tm.dtype} and shape {tm.shape}")
+        tm = np.ascontiguousarray(tm, dtype=np.float32)
+    out = np.zeros(n, dtype=np.bool_)
+    r._check(getattr(r._lib, name)(r._h, rays.ctypes.data_as(C.c_void_p), tm.ctypes.data_as(C.c_void_p) if tm is not None else None, n,
+                                   out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def _occluded_device(r, who, name, rays_t, tmax_t, out_t, stream):
+    """Renderer.occluded_spheres_device / occluded_rays_device: the same, for device tensors."""
+    import torch
+    if not (isinstance(rays_t, torch.Tensor) and rays_t.is_cuda and rays_t.dtype == torch.float32 and rays_t.is_contiguous()
+            and rays_t.dim() == 2 and rays_t.shape[1] == 6):
+        raise ValueError(f"{who}: rays_t must be a contiguous float32 device tensor of shape (n, 6)")
+    n = rays_t.shape[0]
+    if tmax_t is not None and not (isinstance(tmax_t, torch.Tensor) and tmax_t.device == rays_t.device and tmax_t.dtype == torch.float32
+                                   and tmax_t.is_contiguous() and tuple(tmax_t.shape) == (n,)):
+        raise ValueError(f"{who}: tmax_t must be a contiguous float32 tensor of shape (n,) on the rays' device")
+    if out_t is None:
+        out_t = torch.empty(n, dtype=torch.bool, device=rays_t.device)
+    elif not (isinstance(out_t, torch.Tensor) and out_t.device == rays_t.device and out_t.dtype == torch.bool
+              and out_t.is_contiguous() and tuple(out_t.shape) == (n,)):
+        raise ValueError(f"{who}: out_t must be a contiguous torch.bool tensor of shape (n,) on the rays' device")
+    fn = getattr(r._lib, name)
+    tp = C.c_void_p(tmax_t.data_ptr()) if tmax_t is not None else None
+    stream = stream if stream is not None else torch.cuda.current_stream(rays_t.device)
+    if stream.cuda_stream == 0:
+        # handle 0 would be the context's own stream, not ordered with torch's default one: as trace_spheres_device
+        side = torch.cuda.Stream(rays_t.device)
+        side.wait_stream(stream)
+        r._check(fn(r._h, C.c_void_p(rays_t.data_ptr()), tp, n, C.c_void_p(out_t.data_ptr()), C.c_void_p(side.cuda_stream)))
+        stream.wait_stream(side)
+        return out_t
+    r._check(fn(r._h, C.c_void_p(rays_t.data_ptr()), tp, n, C.c_void_p(out_t.data_ptr()), C.c_void_p(stream.cuda_stream)))
+    return out_t
+
+
 # spt_render_aov kinds (include/smallpt_mi355x.h SPT_AOV_*)
 AOV_KINDS = {"normal": 0, "albedo": 1, "uv": 2, "dist": 3}
 
@@ -231,8 +276,27 @@ class Renderer:
                                                        C.c_void_p(stream.cuda_stream)))
         return hits_t
 
+    def occluded_spheres(self, rays, tmax=None):
+        """Any-hit queries against the current sphere table (spt_occluded_spheres; OptiX Prime's RTP_QUERY_TYPE_ANY with OptixRay::tmax,
+        smallpt.cpp:395-403): rays = RAY_DTYPE[n] or floats (n, 6), tmax = floats (n,) or None (+inf); returns np.bool_[n], True where the
+        closest hit of trace_spheres in exhaustive mode has dist < 1e20 and dist < tmax."""
+        return _occluded_host(self, "occluded_spheres", "spt_occluded_spheres", rays, tmax)
+
+    def occluded_rays(self, rays, tmax=None):
+        """The same against the current mesh scene (spt_occluded_rays: the closest hit of trace_rays in exhaustive mode decides)."""
+        return _occluded_host(self, "occluded_rays", "spt_occluded_rays", rays, tmax)
+
+    def occluded_spheres_device(self, rays_t, tmax_t=None, out_t=None, stream=None):
+        """spt_occluded_spheres_device: rays_t = contiguous float32 device tensor (n, 6), tmax_t = contiguous float32 tensor (n,) on the same
+        device or None (+inf); returns the torch.bool tensor (n,) (out_t if given), enqueued on `stream` (a torch stream; default: the current one)."""
+        return _occluded_device(self, "occluded_spheres_device", "spt_occluded_spheres_device", rays_t, tmax_t, out_t, stream)
+
+    def occluded_rays_device(self, rays_t, tmax_t=None, out_t=None, stream=None):
+        """spt_occluded_rays_device: as occluded_spheres_device, against the current mesh scene."""
+        return _occluded_device(self, "occluded_rays_device", "spt_occluded_rays_device", rays_t, tmax_t, out_t, stream)
+
     def last_query_path(self):
-        """What the last trace_spheres* query ran through and how many of its rays the walk handed to the exhaustive loop:
+        """What the last trace_spheres* / occluded_spheres* query ran through and how many of its rays the walk handed to the exhaustive loop:
         ("exhaustive" | "grid" | "bvh" | None before the first query, fallback_rays).  Waits for that query."""
         fb = C.c_uint64(0)
         path = self._lib.spt_last_query_path(self._h, C.byref(fb))
