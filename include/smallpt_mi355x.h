@@ -25,6 +25,9 @@
  *   OptiX Prime RTP_QUERY_TYPE_ANY over OptixRay::tmax          spt_occluded_spheres(), spt_occluded_rays() (host),
  *     (smallpt.cpp:395-403,567,579): shadow / visibility       spt_occluded_spheres_device(),
  *     rays with a bounded segment                                spt_occluded_rays_device() (device buffers, async)
+ *   OptiX Prime RTP_QUERY_TYPE_CLOSEST over OptixRay             spt_trace_spheres_range(), spt_trace_rays_range() (host),
+ *     {origin, tmin, direction, tmax} (smallpt.cpp:395-403,     spt_trace_spheres_range_device(),
+ *     559-569,579): closest hit inside a per-ray interval        spt_trace_rays_range_device() (device buffers, async)
  *   accumBuffer += outImage under accumBufferMutex and the      spt_progressive_begin / _frame / _snapshot / _end
  *     GL thread's copy of it (smallpt.cpp:881-883,924-940,       (accumulation buffer resident in HBM)
  *     955-959)
@@ -130,6 +133,13 @@ typedef struct spt_mesh {
 typedef struct spt_material { float emission[3]; float color[3]; int32_t refl; uint32_t pad; } spt_material;
 typedef struct spt_ray { float o[3]; float d[3]; } spt_ray;
 typedef struct spt_hit { float dist; uint32_t instId; uint32_t triId; float x[3]; float n[3]; float uv[2]; } spt_hit;
+/* OptixRay (smallpt.cpp:395-403), RTP_BUFFER_FORMAT_RAY_ORIGIN_TMIN_DIRECTION_TMAX: 32 bytes */
+typedef struct spt_ray_range { float o[3]; float tmin; float d[3]; float tmax; } spt_ray_range;
+#if defined(__cplusplus)
+static_assert(sizeof(spt_ray_range) == 32, "spt_ray_range is OptixRay: 32 bytes");
+#else
+_Static_assert(sizeof(spt_ray_range) == 32, "spt_ray_range is OptixRay: 32 bytes");
+#endif
 
 /* Intersector::addTriangleMesh for every mesh + build() (smallpt.cpp:437-447 / :489-530): uploads the instances
  * (materials[i] belongs to mesh i, :170) and makes the mesh scene current: spt_render* then trace it with the reference's
@@ -227,6 +237,27 @@ int  spt_occluded_spheres(spt_ctx* ctx, const spt_ray* rays, const float* tmax, 
 int  spt_occluded_spheres_device(spt_ctx* ctx, const void* d_rays, const void* d_tmax, uint64_t n, void* d_occluded, void* hip_stream);
 int  spt_occluded_rays(spt_ctx* ctx, const spt_ray* rays, const float* tmax, uint64_t n, uint8_t* occluded);
 int  spt_occluded_rays_device(spt_ctx* ctx, const void* d_rays, const void* d_tmax, uint64_t n, void* d_occluded, void* hip_stream);
+/* Closest-hit queries over a per-ray interval: what OptiX Prime's RTP_QUERY_TYPE_CLOSEST answers for the reference's OptixRay records
+ * {origin, tmin, direction, tmax} (smallpt.cpp:395-403, filled at :559-569, queried at :579), passed through unchanged (spt_ray_range).
+ * Let hi = min(tmax, 1e20f).  A NaN tmin or tmax always gives a miss.
+ *   Spheres: lo = max(tmin, 1e-4f).  Both roots with intersectAnalytic's arithmetic (scene.cpp:129-140): t1 = b - det, t2 = b + det.  A
+ *     sphere's report is the smaller root that is > lo, if it is also < hi.  The answer is the smallest report, the lowest index winning
+ *     ties; the Hit is Sphere::makeHit at that t: x = o + d t, n = normalize(x - c), instId = the sphere's index, triId = 0, uv = 0.
+ *   Triangles: lo = max(tmin, 0).  A triangle reports triIntersect's t (scene.cpp:52-70) when lo < t < hi.  Selection and Hit are those of
+ *     spt_trace_rays: smallest t, then lowest (instance, triangle), then makeHit.
+ *   Miss (tmin >= tmax included): dist = 1e20, every other field 0.
+ *   Anchor: with tmin <= 1e-4 for spheres (<= 0 for triangles, -inf included) and tmax >= 1e20 (+inf included) the result is bit-identical to
+ *     spt_trace_spheres / spt_trace_rays under SPT_ACCEL_EXHAUSTIVE.  Peeling -- tmin = the previous hit's dist until a miss -- visits the
+ *     reports along one ray in order without moving its origin.
+ *   The answer is the same in every accel mode.  spt_trace_spheres_range* share the sphere structures, routing, work list and
+ *     spt_last_query_path with spt_trace_spheres* and spt_occluded_spheres*; spt_trace_rays_range* take the mesh mode of spt_trace_rays,
+ *     except that SPT_ACCEL_BVH_FAST answers through the exact hierarchy (as spt_occluded_rays does).
+ * Host forms: blocking, wait for a pending render first.  Device forms: n spt_ray_range (16-byte aligned) in and n spt_hit out on this
+ * context's device, enqueued on `hip_stream` (NULL = the context's stream), return without waiting.  A query changes no render state. */
+int  spt_trace_spheres_range(spt_ctx* ctx, const spt_ray_range* rays, uint64_t n, spt_hit* hits);
+int  spt_trace_spheres_range_device(spt_ctx* ctx, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream);
+int  spt_trace_rays_range(spt_ctx* ctx, const spt_ray_range* rays, uint64_t n, spt_hit* hits);
+int  spt_trace_rays_range_device(spt_ctx* ctx, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream);
 /* Host-only helper: makeSphereTriMesh(origin, radius, subdivLongitude) (scene.cpp:3-48): fills (L+1)(2L+1) positions and
  * normals and 4L^2 triangles (L = subdiv_longitude, default 32 at scene.h:17); returns the triangle count. */
 uint32_t spt_make_sphere_trimesh(const float origin[3], float radius, uint32_t subdiv_longitude,

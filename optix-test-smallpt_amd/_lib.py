@@ -52,6 +52,10 @@ SYMBOLS = {
     "spt_trace_rays_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "spt_trace_spheres": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "spt_trace_spheres_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    "spt_trace_spheres_range": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "spt_trace_spheres_range_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    "spt_trace_rays_range": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "spt_trace_rays_range_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "spt_occluded_spheres": (C.c_int, [_P, _P, _P, C.c_uint64, _P]),
     "spt_occluded_spheres_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "spt_occluded_rays": (C.c_int, [_P, _P, _P, C.c_uint64, _P]),

@@ -61,6 +61,7 @@ struct spt_ctx {
     bool mesh_specular = false;            // a mesh material is SPEC or REFR: long mirror / glass chains are possible (task dealing of the hierarchy kernel)
     float4* d_tris = nullptr; uint4* d_tri_index = nullptr; float4* d_verts = nullptr; uint32_t* d_inst_first = nullptr; float4* d_mesh_mats = nullptr;
     float* d_trace_rays = nullptr; float* d_trace_hits = nullptr; uint64_t trace_cap = 0;   // spt_trace_rays staging (rays)
+    float* d_range_rays = nullptr; uint64_t range_cap = 0;   // spt_trace_*_range staging (32-byte rays; the hits go to d_trace_hits)
     // spt_trace_spheres*: the rays a walk hands to the exhaustive loop (one launch's worth), {count of the launch, pad, total of the query}, the
     // query's completion (a query waits for its predecessor: they share these), what the last query ran through (-1: none yet)
     uint32_t* d_qlist = nullptr; uint64_t qlist_cap = 0; uint32_t* d_qcount = nullptr;
@@ -220,6 +221,7 @@ void spt_destroy(spt_ctx* c)
     if (c->d_tri_index) (void)hipFree(c->d_tri_index);
     if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
     if (c->d_trace_hits) (void)hipFree(c->d_trace_hits);
+    if (c->d_range_rays) (void)hipFree(c->d_range_rays);
     if (c->d_qlist) (void)hipFree(c->d_qlist);
     if (c->d_qcount) (void)hipFree(c->d_qcount);
     if (c->ev_query) (void)hipEventDestroy(c->ev_query);
@@ -847,8 +849,10 @@ int spt_trace_rays(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
 // else the exhaustive loop; SPT_ACCEL_BVH: the hierarchy if built, else the exhaustive loop; SPT_ACCEL_EXHAUSTIVE: the exhaustive loop.
 // (Tables that need the guarded square root never walk: the grid refuses them at build time, the query keeps them off the hierarchy.)
 // Enqueued on `st`; touches no render state.  d_occ != NULL: the occlusion form (spt_occluded_spheres*) -- bounds d_tmax (NULL: +inf), one byte
-// per ray in d_occ, d_hits unused -- through the same structure, fallback list and completion event.
-static int sphere_query_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, float* d_hits, const float* d_tmax, uint8_t* d_occ, hipStream_t st)
+// per ray in d_occ, d_hits unused -- through the same structure, fallback list and completion event.  range: the interval form
+// (spt_trace_spheres_range*) -- d_rays holds 8 floats per ray {o, tmin, d, tmax} --, likewise.
+static int sphere_query_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, float* d_hits, const float* d_tmax, uint8_t* d_occ, hipStream_t st,
+                                bool range = false)
 {
     uint32_t path = spt::kQueryExhaustive;
     if (c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready) path = spt::kQueryGrid;
@@ -882,7 +886,22 @@ static int sphere_query_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, flo
     }
     for (uint64_t first = 0; first < n; first += spt::kQuerySlice) {
         const uint32_t m = (uint32_t)(n - first < spt::kQuerySlice ? n - first : spt::kQuerySlice);
-        const float* const rays = d_rays + first * 6;
+        const float* const rays = d_rays + first * (range ? 8 : 6);
+        if (range) {
+            float* const hits = d_hits + first * 11;
+            if (path == spt::kQueryExhaustive) {
+                SPT_HIP(c, spt_range_exhaustive_launch(c->d_geom, c->n, rays, m, hits, nullptr, nullptr, 0, guard_all, st));
+                continue;
+            }
+            if (first != 0) SPT_HIP(c, hipMemsetAsync(c->d_qcount, 0, 4, st));
+            if (path == spt::kQueryGrid)
+                SPT_HIP(c, spt_range_grid_launch(c->d_geom, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, where, rays, m, hits,
+                                                 c->d_qlist, c->d_qcount, grid_blocks, st));
+            else
+                SPT_HIP(c, spt_range_bvh_launch(&K, &M, rays, m, hits, c->d_qlist, c->d_qcount, st));
+            SPT_HIP(c, spt_range_exhaustive_launch(c->d_geom, c->n, rays, m, hits, c->d_qlist, c->d_qcount, list_blocks, guard_all, st));
+            continue;
+        }
         if (d_occ) {
             const float* const tmax = d_tmax ? d_tmax + first : nullptr;
             uint8_t* const occ = d_occ + first;
@@ -1030,6 +1049,93 @@ int spt_occluded_rays(spt_ctx* c, const spt_ray* rays, const float* tmax, uint64
     e = hipMemcpyAsync(occluded, d_occ, n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return c->fail("spt_occluded_rays: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// ---- closest-hit queries over a per-ray interval: OptixRay {origin, tmin, direction, tmax} records (smallpt.cpp:395-403) with
+// RTP_QUERY_TYPE_CLOSEST (:579); spt_query.h range_keys.  Call conventions, messages and structures are those of spt_trace_spheres* /
+// spt_trace_rays*; the host forms stage the 32-byte rays in their own buffer and the hits in the trace staging pair.
+static hipError_t ensure_range_staging(spt_ctx* c, uint64_t n)
+{
+    static_assert(sizeof(spt_ray_range) == 32, "OptixRay layout (RTP_BUFFER_FORMAT_RAY_ORIGIN_TMIN_DIRECTION_TMAX)");
+    hipError_t e = ensure_trace_staging(c, n);
+    if (e == hipSuccess && n > c->range_cap) {
+        if (c->d_range_rays) (void)hipFree(c->d_range_rays);
+        c->d_range_rays = nullptr; c->range_cap = 0;
+        e = hipMalloc(reinterpret_cast<void**>(&c->d_range_rays), n * sizeof(spt_ray_range));
+        if (e == hipSuccess) c->range_cap = n;
+    }
+    return e;
+}
+
+int spt_trace_spheres_range_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream)
+{
+    if (!c) return 1;
+    if (trace_spheres_check(c, "spt_trace_spheres_range_device", d_rays, n, d_hits)) return 1;
+    if (n == 0) return 0;
+    if (reinterpret_cast<uintptr_t>(d_rays) & 15u) return c->fail("spt_trace_spheres_range_device: d_rays must be 16-byte aligned");
+    SPT_HIP(c, hipSetDevice(c->device));
+    return sphere_query_enqueue(c, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits), nullptr, nullptr,
+                                hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream, true);
+}
+
+int spt_trace_spheres_range(spt_ctx* c, const spt_ray_range* rays, uint64_t n, spt_hit* hits)
+{
+    if (!c) return 1;
+    if (trace_spheres_check(c, "spt_trace_spheres_range", rays, n, hits)) return 1;
+    if (n == 0) return 0;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
+    hipError_t e = ensure_range_staging(c, n);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_range_rays, rays, n * sizeof(spt_ray_range), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return c->fail("spt_trace_spheres_range: %s", hipGetErrorString(e));
+    if (sphere_query_enqueue(c, c->d_range_rays, n, c->d_trace_hits, nullptr, nullptr, c->stream, true)) return 1;
+    e = hipMemcpyAsync(hits, c->d_trace_hits, n * sizeof(spt_hit), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return c->fail("spt_trace_spheres_range: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// Mesh scenes: the mode of spt_trace_rays (mesh_mode(c, false)); one that resolves to SPT_ACCEL_BVH_FAST takes the exact hierarchy, as
+// spt_occluded_rays does.
+static int trace_rays_range_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, float* d_hits, hipStream_t st)
+{
+    const int mode = mesh_mode(c, false);
+    c->last_mesh_mode = mode == SPT_ACCEL_BVH_FAST ? SPT_ACCEL_BVH : mode;
+    const spt::MParams M = mesh_params(c, c->last_mesh_mode);
+    SPT_HIP(c, spt_mesh_trace_rays_range(&M, d_rays, n, d_hits, st));
+    return 0;
+}
+
+int spt_trace_rays_range_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream)
+{
+    if (!c) return 1;
+    if (!c->mesh_scene) return c->fail("spt_trace_rays_range_device: no mesh scene set (call spt_set_meshes)");
+    if (n == 0) return 0;
+    if (!d_rays || !d_hits) return c->fail("spt_trace_rays_range_device: NULL argument");
+    if (n > 0x7FFFFFFFull * 256ull) return c->fail("spt_trace_rays_range_device: too many rays for one call");
+    if (reinterpret_cast<uintptr_t>(d_rays) & 15u) return c->fail("spt_trace_rays_range_device: d_rays must be 16-byte aligned");
+    SPT_HIP(c, hipSetDevice(c->device));
+    return trace_rays_range_enqueue(c, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits),
+                                    hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int spt_trace_rays_range(spt_ctx* c, const spt_ray_range* rays, uint64_t n, spt_hit* hits)
+{
+    if (!c) return 1;
+    if (!c->mesh_scene) return c->fail("spt_trace_rays_range: no mesh scene set (call spt_set_meshes)");
+    if (n == 0) return 0;
+    if (!rays || !hits) return c->fail("spt_trace_rays_range: NULL argument");
+    if (n > 0x7FFFFFFFull * 256ull) return c->fail("spt_trace_rays_range: too many rays for one call");
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
+    hipError_t e = ensure_range_staging(c, n);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_range_rays, rays, n * sizeof(spt_ray_range), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return c->fail("spt_trace_rays_range: %s", hipGetErrorString(e));
+    if (trace_rays_range_enqueue(c, c->d_range_rays, n, c->d_trace_hits, c->stream)) return 1;
+    e = hipMemcpyAsync(hits, c->d_trace_hits, n * sizeof(spt_hit), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return c->fail("spt_trace_rays_range: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -44,6 +44,15 @@
 //       report t_j < b has been visited by then.  That holds for reports up to t_ok (1), so "no" stands only if b <= t_ok; a ray with b > t_ok,
 //       and every ray the route refuses (1) / (4), takes the exhaustive loop unless the walk already found a report below b.  The always-list
 //       is tested first, as in (4).
+//   (6) closest hit over an interval (lo, hi) (spt_trace_spheres_range, spt_grid.hip range_grid; spt_query.h range_keys).  A sphere's report
+//       is now the smaller root above lo, which may be the far root t2 = b + det.  (1) bounds the error of ANY root the arithmetic reports,
+//       t1 and t2 alike (the derivation uses only that p = o + t d solves the computed quadratic), so (2) registers j in every cell within
+//       dgrid of p_j for either root, and (3) covers t2 as it covers t1.  The walk starts at the origin as before, with the current nearest
+//       t starting at hi: it stops when the computed exit time of the current cell reaches that t, and by (3) every cell that can hold a
+//       report below it has been visited -- reports at or below lo are visited too and lose on their keys.  The answer stands only if the
+//       final nearest t (hi for a miss) is <= t_ok; otherwise the ray is handed over, as before.  A ray with lo >= t_ok can only have
+//       reports beyond t_ok, so it goes to the exhaustive loop without walking.  Nothing is pruned by lo: no cell or box that ends before
+//       lo is skipped and the walk never starts at o + lo d, so no further argument is needed.
 #ifndef SPT_GRID_H
 #define SPT_GRID_H
 #include <hip/hip_runtime.h>

@@ -762,6 +762,201 @@ __global__ __launch_bounds__(kGridBlock) void occ_grid(const float4* __restrict_
     }
 }
 
+// ---- batched closest-hit queries over a per-ray interval (spt_trace_spheres_range, spt_query.h range_keys) ----------------------------------
+// sphere_key_g with the ray's own bias: key(t) = bits(t) - bits(lo) - 1, and min(key1, key2) is the smaller root above lo (spt_query.h).
+template <bool GUARD = false>
+__device__ __forceinline__ uint32_t sphere_key_range(const float4 g, f3 o, f3 d, uint32_t bias)
+{
+    const f3 op = mk(g.x - o.x, g.y - o.y, g.z - o.z);                                  // :132
+    const float bb = dot(op, d);                                                        // :133
+    const float det = bb * bb - dot(op, op) + g.w;                                      // :133 (g.w = r*r)
+    const float sd = GUARD ? sqrt_exact(det) : sqrt_rsq(det);                           // :134
+    const uint32_t key1 = __float_as_uint(bb - sd) - bias;                              // :135
+    const uint32_t key2 = __float_as_uint(bb + sd) - bias;
+    return key1 < key2 ? key1 : key2;
+}
+
+// One ray of the interval forms: {o, tmin, d, tmax} (32 bytes: two 16-byte loads).
+__device__ __forceinline__ void range_ray(const float* __restrict__ rays, uint32_t r, f3& o, f3& d, float& tmin, float& tmax)
+{
+    const float4* q = reinterpret_cast<const float4*>(rays) + 2 * (size_t)r;
+    const float4 a = q[0], b = q[1];
+    o = mk(a.x, a.y, a.z); tmin = a.w; d = mk(b.x, b.y, b.z); tmax = b.w;
+}
+
+template <bool GUARD>
+__device__ __forceinline__ void range_tile(const float4* s_geom, uint32_t cnt, uint32_t first, f3 o, f3 d, uint32_t bias, uint32_t& near_key, uint32_t& near_i)
+{
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t key = sphere_key_range<GUARD>(s_geom[k], o, d, bias);
+        if (key < near_key) { near_key = key; near_i = first + k; }
+    }
+}
+
+// query_exhaustive over an interval: the running nearest key starts at the ray's bound (hi), the bias is the ray's (lo); ascending index and
+// strict '<' as before.  A ray whose bound is 0 (hi <= lo, NaN) keeps it: a miss.
+template <bool LIST>
+__global__ __launch_bounds__(kQueryBlock) void range_exhaustive(const float4* __restrict__ geom, uint32_t n, const float* __restrict__ rays, uint32_t nrays,
+                                                                float* __restrict__ hits, const uint32_t* __restrict__ list, const uint32_t* __restrict__ qcount,
+                                                                int guard_all)
+{
+    __shared__ float4 s_geom[kQTile];
+    __shared__ float s_stage[LIST ? 1 : kQueryBlock * 11];
+    const uint32_t lane = lane_id_g(), wave = threadIdx.x >> 6;
+    const uint32_t count = LIST ? qcount[0] : nrays;
+    const bool one_tile = n <= kQTile;
+    if (one_tile) {
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) s_geom[i] = geom[i];
+        __syncthreads();
+    }
+    for (uint32_t base = blockIdx.x * kQueryBlock; base < count; base += gridDim.x * kQueryBlock) {     // workgroup-uniform
+        const uint32_t slot = base + threadIdx.x;
+        const bool active = slot < count;
+        const uint32_t r = active ? (LIST ? list[slot] : slot) : 0u;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        RangeKeys rk{kGEpsBias, 0u};
+        if (active) {
+            float tmin, tmax;
+            range_ray(rays, r, o, d, tmin, tmax);
+            rk = range_sphere_keys(tmin, tmax);
+        }
+        const bool guard = guard_all != 0 || __ballot(active && !query_ray_unguarded(o.x, o.y, o.z, d.x, d.y, d.z)) != 0ull;   // wave-uniform
+        uint32_t near_key = rk.bound, near_i = 0u;
+        for (uint32_t tb = 0; tb < n; tb += kQTile) {
+            const uint32_t cnt = n - tb < kQTile ? n - tb : kQTile;
+            if (!one_tile) {
+                __syncthreads();                                 // the previous tile is no longer read
+                for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) s_geom[i] = geom[tb + i];
+                __syncthreads();
+            }
+            if (guard) range_tile<true>(s_geom, cnt, tb, o, d, rk.bias, near_key, near_i);
+            else range_tile<false>(s_geom, cnt, tb, o, d, rk.bias, near_key, near_i);
+        }
+        const bool hit = near_key != rk.bound;
+        const QueryHit h = query_hit(hit, near_i, range_key_t(near_key, rk.bias), geom[hit ? near_i : 0u], o, d);
+        if (LIST) {
+            if (active) {
+                float* const out = hits + (size_t)r * 11;
+#pragma unroll
+                for (int k = 0; k < 11; ++k) out[k] = h.f[k];
+            }
+        } else {
+            float* const st = s_stage + wave * 64u * 11u;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) st[lane * 11u + k] = h.f[k];   // (stride 11: no two lanes of a store share a bank)
+            __syncthreads();
+            const uint32_t wbase = base + wave * 64u;
+            const uint32_t nv = wbase < count ? (count - wbase < 64u ? count - wbase : 64u) : 0u;
+            float* const out = hits + (size_t)wbase * 11;
+            for (uint32_t j = lane; j < nv * 11u; j += 64u) out[j] = st[j];
+            __syncthreads();
+        }
+    }
+}
+
+// The grid over an interval (spt_grid.h (6)): query_grid's walk from the origin with the running nearest starting at hi and reports filtered
+// by lo through the key.  The walk stops when the cell exit reaches the running nearest t (hi until something is found), so it covers every
+// report below that t up to t_ok, whatever lo is.  Rays the route refuses, rays with lo >= t_ok (every report they could have lies beyond
+// t_ok) and walks whose answer (hi for a miss) exceeds t_ok go to the fallback list for range_exhaustive<true>; rays with an empty interval
+// write a miss here.
+template <int WHERE>
+__global__ __launch_bounds__(kGridBlock) void range_grid(const float4* __restrict__ geom, const GridParams G, const uint32_t* __restrict__ g_cells,
+                                                         const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always,
+                                                         const float* __restrict__ rays, uint32_t nrays, float* __restrict__ hits,
+                                                         uint32_t* __restrict__ list, uint32_t* __restrict__ qcount)
+{
+    constexpr bool GLOBAL_TABLES = WHERE == 1, GLOBAL_GEOM = WHERE != 0;
+    extern __shared__ float4 s_lds_geom[];
+    uint32_t* const s_lds_cells = reinterpret_cast<uint32_t*>(s_lds_geom + (GLOBAL_GEOM ? 0u : (G.n ? G.n : 1u)));
+    uint16_t* const s_lds_refs = reinterpret_cast<uint16_t*>(s_lds_cells + G.ncells);
+    if (!GLOBAL_GEOM) for (uint32_t i = threadIdx.x; i < G.n; i += blockDim.x) s_lds_geom[i] = geom[i];
+    if (!GLOBAL_TABLES) {
+        for (uint32_t i = threadIdx.x; i < G.ncells; i += blockDim.x) s_lds_cells[i] = g_cells[i];
+        for (uint32_t i = threadIdx.x; i < G.nrefs; i += blockDim.x) s_lds_refs[i] = g_refs[i];
+        for (uint32_t i = threadIdx.x; i <= G.nalways; i += blockDim.x) s_lds_refs[G.nrefs + i] = i < G.nalways ? (uint16_t)g_always[i] : (uint16_t)0;
+    }
+    auto geom_at = [&](uint32_t i) -> float4 { return GLOBAL_GEOM ? geom[i] : s_lds_geom[i]; };
+    auto cell_at = [&](uint32_t ci) -> uint32_t { return GLOBAL_TABLES ? g_cells[ci] : s_lds_cells[ci]; };
+    auto ref_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? (uint32_t)g_refs[k] : (uint32_t)s_lds_refs[k]; };
+    auto always_at = [&](uint32_t k) -> uint32_t { return GLOBAL_TABLES ? g_always[k] : (uint32_t)s_lds_refs[G.nrefs + k]; };
+    __syncthreads();
+
+    const uint32_t lane = lane_id_g();
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t base = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 64u; base < nrays; base += waves * 64u) {   // wave-uniform
+        const uint32_t r = base + lane;
+        const bool active = r < nrays;
+        f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+        RangeKeys rk{kGEpsBias, 0u};
+        if (active) {
+            float tmin, tmax;
+            range_ray(rays, r, o, d, tmin, tmax);
+            rk = range_sphere_keys(tmin, tmax);
+        }
+        float t_ok = 0.f;
+        const bool routed = rk.bound != 0u && query_ray_route(kQueryGrid, G, o.x, o.y, o.z, d.x, d.y, d.z, t_ok) == kQueryGrid;
+        const bool walk = routed && range_key_t(0u, rk.bias) <= t_ok;    // the smallest report t (the first float above lo) is within t_ok
+        uint32_t near_key = rk.bound, near_i = 0u;               // index 0 with the bound key: never replaced by another bound key
+        for (uint32_t k = 0; k < G.nalways; ++k) {              // walls / lights: ascending indices, strict '<' (smallpt.cpp:61)
+            const uint32_t i = always_at(k);
+            const float4 g = geom_at(i);
+            if (walk) {
+                const uint32_t key = sphere_key_range(g, o, d, rk.bias);
+                if (key < near_key) { near_key = key; near_i = i; }
+            }
+        }
+        float wtx = 0.f, wty = 0.f, wtz = 0.f, wdx = 0.f, wdy = 0.f, wdz = 0.f;   // the walk (GridWalk) in separate registers
+        int32_t wsx = 0, wsy = 0, wsz = 0;
+        uint32_t wci = 0, cur = 0, end = 0;                      // end = 0 outside the walk
+        bool walking = walk;
+        if (walk) {
+            GridWalk w;
+            grid_walk_begin(G, o.x, o.y, o.z, d.x, d.y, d.z, w);
+            wtx = w.tx; wty = w.ty; wtz = w.tz; wdx = w.dtx; wdy = w.dty; wdz = w.dtz; wsx = w.sx; wsy = w.sy; wsz = w.sz; wci = w.ci;
+            const uint32_t h = cell_at(wci);                     // the start cell is clamped into the table: never a border cell
+            cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+        }
+        uint32_t nwalk = (uint32_t)__popcll(__ballot(walking));
+        while (nwalk != 0u) {
+            const bool wt = cur < end;
+            const uint32_t nt = (uint32_t)__popcll(__ballot(wt));
+            if (2u * nt >= nwalk) {                              // TEST the next sphere of the lane's cell
+                if (wt) {
+                    const uint32_t i = ref_at(cur);
+                    ++cur;
+                    const uint32_t key = sphere_key_range(geom_at(i), o, d, rk.bias);
+                    const bool better = (key < near_key) | ((key == near_key) & (i < near_i));
+                    near_key = better ? key : near_key;
+                    near_i = better ? i : near_i;
+                }
+            } else {                                             // STEP: leave the cell (all its spheres are tested)
+                if (walking && !wt) {
+                    const float m = __builtin_fminf(wtx, __builtin_fminf(wty, wtz));   // grid_walk_exit
+                    bool stop = !(m < range_key_t(near_key, rk.bias));                 // spt_grid.h (3), (6)
+                    if (!stop) {
+                        grid_walk_step(wtx, wty, wtz, wdx, wdy, wdz, wsx, wsy, wsz, wci, m);
+                        const uint32_t h = cell_at(wci);
+                        stop = h == kGridBorder;                 // left the table
+                        cur = h >> kGridCountBits; end = cur + (h & ((1u << kGridCountBits) - 1u));
+                    }
+                    if (stop) { walking = false; end = 0; }
+                }
+                nwalk = (uint32_t)__popcll(__ballot(walking));
+            }
+        }
+        const float t = range_key_t(near_key, rk.bias);         // hi while nothing is found
+        const bool fallback = rk.bound != 0u && (!walk || t > t_ok);    // spt_grid.h (1), (4), (6): the exhaustive loop answers
+        query_append(fallback, r, list, qcount, reinterpret_cast<unsigned long long*>(qcount + 2));
+        if (active && !fallback) {
+            const bool hit = walk && near_key != rk.bound;
+            const QueryHit h = query_hit(hit, near_i, t, geom_at(hit ? near_i : 0u), o, d);
+            float* const out = hits + (size_t)r * 11;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) out[k] = h.f[k];
+        }
+    }
+}
+
 // ---- first-hit feature buffers (spt_render_aov, spt_aov.h) over the sphere table ----------------------------------------------------------
 // One lane per D9 task (a block of one jitter cell's samples), the lanes of a wave dealt an 8 x 8 tile of pixels (spt_deal.h deal_task_tiles);
 // per sample: the camera ray, its closest hit, acc += the selected value; then cells[task].  No bounces: no pools, stacks or watchdog.
@@ -1070,4 +1265,41 @@ extern "C" hipError_t spt_occ_grid_launch(const float4* geom, const spt::GridPar
     if (where == 0) return launch_occ_grid<0>(geom, G, d_cells, d_refs, d_always, rays, tmax, nrays, occ, list, qcount, blocks, lds, stream);
     if (where == 1) return launch_occ_grid<1>(geom, G, d_cells, d_refs, d_always, rays, tmax, nrays, occ, list, qcount, blocks, lds, stream);
     return launch_occ_grid<2>(geom, G, d_cells, d_refs, d_always, rays, tmax, nrays, occ, list, qcount, blocks, lds, stream);
+}
+
+extern "C" hipError_t spt_range_exhaustive_launch(const float4* geom, uint32_t n, const float* rays, uint32_t nrays, float* hits,
+                                                  const uint32_t* list, const uint32_t* qcount, uint32_t list_blocks, int guard_all, hipStream_t stream)
+{
+    if (nrays == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)nrays + spt::kQueryBlock - 1) / spt::kQueryBlock);
+    if (list) hipLaunchKernelGGL(spt::range_exhaustive<true>, dim3(blocks < list_blocks ? blocks : list_blocks), dim3(spt::kQueryBlock), 0, stream,
+                                 geom, n, rays, nrays, hits, list, qcount, guard_all);
+    else hipLaunchKernelGGL(spt::range_exhaustive<false>, dim3(blocks), dim3(spt::kQueryBlock), 0, stream, geom, n, rays, nrays, hits, list, qcount, guard_all);
+    return hipGetLastError();
+}
+
+template <int WHERE>
+static hipError_t launch_range_grid(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs, const uint32_t* d_always,
+                                    const float* rays, uint32_t nrays, float* hits, uint32_t* list, uint32_t* qcount, uint32_t blocks, size_t lds,
+                                    hipStream_t stream)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::range_grid<WHERE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((spt::range_grid<WHERE>), dim3(blocks), dim3(spt::kGridBlock), lds, stream, geom, *G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount);
+    return hipGetLastError();
+}
+
+// blocks: persistent workgroups of kGridBlock threads (the caller sizes them from the CU count); where as in spt_grid_launch
+extern "C" hipError_t spt_range_grid_launch(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
+                                            const uint32_t* d_always, int where, const float* rays, uint32_t nrays, float* hits,
+                                            uint32_t* list, uint32_t* qcount, uint32_t blocks, hipStream_t stream)
+{
+    if (where < 0 || where > 2) return hipErrorInvalidValue;
+    if (nrays == 0) return hipSuccess;
+    const uint32_t need = (uint32_t)(((uint64_t)nrays + spt::kGridBlock - 1) / spt::kGridBlock);
+    if (blocks > need) blocks = need;
+    const size_t lds = where == 1 ? 0 : (where == 2 ? spt_grid_lds_bytes_tables(G) : spt_grid_lds_bytes(G));
+    if (where == 0) return launch_range_grid<0>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
+    if (where == 1) return launch_range_grid<1>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
+    return launch_range_grid<2>(geom, G, d_cells, d_refs, d_always, rays, nrays, hits, list, qcount, blocks, lds, stream);
 }

@@ -280,6 +280,76 @@ __device__ __forceinline__ bool any_triangle_bvh(const MParams& M, uint32_t* s_s
     return occ;
 }
 
+// ---- closest-hit queries of a mesh scene over a per-ray interval (spt_trace_rays_range, spt_query.h range_keys) ------------------------
+// A triangle reports triIntersect's t (tri_test) when key(t) = bits(t) - bias < bound: lo < t < hi.  Selection as closest_triangle /
+// closest_triangle_bvh -- smallest key, then lowest global index --, starting from the bound instead of the key of 1e20.
+__device__ __forceinline__ uint32_t closest_triangle_range(const float4* __restrict__ tris, uint32_t ntris, float4* s_tile, bool active, f3 ro, f3 rd,
+                                                           RangeKeys rk, float& t_out)
+{
+    uint32_t near_key = rk.bound, near_tri = 0xFFFFFFFFu;
+    auto consider = [&](const float4 r0, const float4 r1, const float4 r2, uint32_t index) {
+        float u, v;
+        const uint32_t key = __float_as_uint(tri_test(r0, r1, r2, ro, rd, u, v)) - rk.bias;
+        const bool better = key < near_key;
+        near_key = better ? key : near_key;
+        near_tri = better ? index : near_tri;
+    };
+    for (uint32_t base = 0; base < ntris; base += kTile) {
+        const uint32_t cnt = ntris - base < (uint32_t)kTile ? ntris - base : (uint32_t)kTile;
+        __syncthreads();                                       // the previous tile is no longer read
+        for (uint32_t i = threadIdx.x; i < 3u * cnt; i += blockDim.x) s_tile[i] = tris[3u * (size_t)base + i];
+        __syncthreads();
+        if (active) {
+            uint32_t k = 0;
+            for (; k + 4 <= cnt; k += 4) {                     // four records (12 broadcast reads) in flight per LDS round trip
+                const float4* r = s_tile + 3 * k;
+                const float4 a0 = r[0], a1 = r[1], a2 = r[2], b0 = r[3], b1 = r[4], b2 = r[5];
+                const float4 c0 = r[6], c1 = r[7], c2 = r[8], d0 = r[9], d1 = r[10], d2 = r[11];
+                consider(a0, a1, a2, base + k);
+                consider(b0, b1, b2, base + k + 1);
+                consider(c0, c1, c2, base + k + 2);
+                consider(d0, d1, d2, base + k + 3);
+            }
+            for (; k < cnt; ++k) consider(s_tile[3 * k], s_tile[3 * k + 1], s_tile[3 * k + 2], base + k);
+        }
+    }
+    t_out = range_key_t(near_key, rk.bias);
+    return near_tri;
+}
+
+// The exact hierarchy over an interval (spt_tribvh.h): the spatial walk from the origin with tcut = hi * 1.0001, narrowed to t * 1.0001 by
+// each better report -- a box it skips holds no report below the current nearest, by (1) --, then the plane tree (2) and the line table /
+// tree (3), which list the triangles whose report they cover whatever its t; every structure filters by lo through the key.
+__device__ __forceinline__ uint32_t closest_triangle_bvh_range(const MParams& M, uint32_t* s_stack, bool active, f3 ro, f3 rd, RangeKeys rk, float& t_out)
+{
+    uint32_t near_key = rk.bound, near_tri = 0xFFFFFFFFu;
+    if (active) {
+        float tcut = range_key_t(rk.bound, rk.bias) * 1.0001f;
+        LdsStack st{s_stack};
+        auto consider = [&](const float4* r, uint32_t g) {
+            float u, v;
+            const float t = tri_test(r[0], r[1], r[2], ro, rd, u, v);
+            const uint32_t key = __float_as_uint(t) - rk.bias;
+            if (key < near_key || (key == near_key && g < near_tri)) {          // key == bound never replaces: near_tri would have to be larger
+                if (key < rk.bound) { near_key = key; near_tri = g; tcut = t * 1.0001f; }
+            }
+        };
+        TriQuery q;
+        tri_query(ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, q);
+        const float ivx = __builtin_amdgcn_rcpf(rd.x), ivy = __builtin_amdgcn_rcpf(rd.y), ivz = __builtin_amdgcn_rcpf(rd.z);   // 1 ulp; inside the widening
+        auto leaf = [&](uint32_t first, uint32_t cnt) {
+            for (uint32_t k = 0; k < cnt; ++k) consider(M.bvh_tris + 3 * (size_t)(first + k), M.bvh_index[first + k]);
+        };
+        auto by_index = [&](uint32_t g) { consider(M.tris + 3 * (size_t)g, g); };
+        tri_walk_boxes<true>(M.bvh_nodes, M.bvh_cones, ro.x, ro.y, ro.z, ivx, ivy, ivz, q.h[0], q.h[1], q.h[2], tcut, st, leaf);
+        if (M.plane_nodes) tri_walk_planes(M.plane_nodes, q, st, by_index);
+        if (M.flat_lines) tri_scan_lines(M.flat_lines, M.flat_line_index, M.nline_slots, q, st, by_index);
+        else if (M.line_nodes) tri_walk_lines(M.line_nodes, q, st, by_index);
+    }
+    t_out = range_key_t(near_key, rk.bias);
+    return near_tri;
+}
+
 // ---- sphere tables through a hierarchy (spt_set_sphere_accel; spt_bvh.h build_sphere_bvh) -----------------------------------
 // intersectAnalytic of one sphere record {c, r*r} on the integer keys of the sphere kernels (scene.cpp:129-140, smallpt.cpp:59-65):
 // key(t) = bits(t) - (bits(eps) + 1); returns the smaller of the two root keys (NaN roots give keys above every valid one).
@@ -293,6 +363,17 @@ __device__ __forceinline__ uint32_t sphere_key(const float4 g, f3 o, f3 d)
     const float sd = sqrt_exact(det);                                                   // :134 (NaN for det < 0: both keys lose)
     const uint32_t key1 = __float_as_uint(bb - sd) - kSphEpsBias;                       // :135
     const uint32_t key2 = __float_as_uint(bb + sd) - kSphEpsBias;
+    return key1 < key2 ? key1 : key2;
+}
+// The same with the ray's own bias (interval queries: key(t) = bits(t) - bits(lo) - 1, spt_query.h range_keys).
+__device__ __forceinline__ uint32_t sphere_key_biased(const float4 g, f3 o, f3 d, uint32_t bias)
+{
+    const f3 op = mk(g.x - o.x, g.y - o.y, g.z - o.z);
+    const float bb = dot(op, d);
+    const float det = bb * bb - dot(op, op) + g.w;
+    const float sd = sqrt_exact(det);
+    const uint32_t key1 = __float_as_uint(bb - sd) - bias;
+    const uint32_t key2 = __float_as_uint(bb + sd) - bias;
     return key1 < key2 ? key1 : key2;
 }
 
@@ -310,19 +391,29 @@ __device__ __forceinline__ uint32_t sphere_key(const float4 g, f3 o, f3 d)
 // ANY (occlusion queries, spt_occluded_spheres): bound_key = occ_sphere_key(tmax) (> 0) takes the place of the nearest key and tcut starts at
 // the bound, widened like the nearest distance; the walk ends at the first report below the bound (its index is returned, else 0xFFFFFFFF).
 // A box skipped against that tcut holds no report below the bound, by the argument above.
-template <bool ANY = false>
+// RANGE (interval queries, spt_trace_spheres_range; spt_query.h range_keys): keys carry the ray's bias (lo), the nearest key starts at the
+// ray's bound (hi) and tcut at hi, widened; the walk starts at the origin as before.  A box skipped against tcut holds no report below the
+// current nearest t, by the argument above, and reports at or below lo lose on their keys wherever they are found.
+template <bool ANY = false, bool RANGE = false>
 __device__ __forceinline__ uint32_t closest_sphere_bvh(const KParams& K, const MParams& M, const float4* nodes, const float4* leaf_geom, const uint32_t* leaf_index,
-                                                    uint32_t* s_stack, bool active, f3 ro, f3 rd, float& t_out, uint32_t bound_key = kSphInfKey)
+                                                    uint32_t* s_stack, bool active, f3 ro, f3 rd, float& t_out, uint32_t bound_key = kSphInfKey,
+                                                    uint32_t bias = kSphEpsBias)
 {
-    uint32_t near_key = ANY ? bound_key : kSphInfKey, near_i = 0xFFFFFFFFu;
+    uint32_t near_key = ANY || RANGE ? bound_key : kSphInfKey, near_i = 0xFFFFFFFFu;
     if (active) {
-        float tcut = ANY ? __uint_as_float(bound_key + kSphEpsBias) * 1.0001f : 1e20f;
+        float tcut = ANY || RANGE ? __uint_as_float(bound_key + (RANGE ? bias : kSphEpsBias)) * 1.0001f : 1e20f;
         auto consider = [&](const float4 g, uint32_t index) {
-            const uint32_t key = sphere_key(g, ro, rd);
+            uint32_t key;
+            if constexpr (RANGE) key = sphere_key_biased(g, ro, rd, bias);
+            else key = sphere_key(g, ro, rd);
             if (ANY) {
                 if (key < near_key) { near_key = key; near_i = index; }
             } else if (key < near_key || (key == near_key && index < near_i)) {       // ascending index + strict '<' of smallpt.cpp:61
-                if (key < kSphInfKey) { near_key = key; near_i = index; tcut = __uint_as_float(key + kSphEpsBias) * 1.0001f; }
+                if constexpr (RANGE) {
+                    if (key < bound_key) { near_key = key; near_i = index; tcut = __uint_as_float(key + bias) * 1.0001f; }
+                } else {
+                    if (key < kSphInfKey) { near_key = key; near_i = index; tcut = __uint_as_float(key + kSphEpsBias) * 1.0001f; }
+                }
             }
         };
         for (uint32_t k = 0; k < M.nalways; ++k) {
@@ -378,7 +469,7 @@ __device__ __forceinline__ uint32_t closest_sphere_bvh(const KParams& K, const M
             cur = (int)s_stack[sp * kMeshBlock + threadIdx.x];
         }
     }
-    t_out = __uint_as_float(near_key + kSphEpsBias);
+    t_out = __uint_as_float(near_key + (RANGE ? bias : kSphEpsBias));
     return near_i;
 }
 
@@ -502,6 +593,68 @@ __global__ __launch_bounds__(kMeshBlock) void occluded_rays(const MParams M, con
     const bool occ = BVH ? any_triangle_bvh(M, reinterpret_cast<uint32_t*>(s_tile), bkey != 0u, ro, rd, bkey)
                          : any_triangle(M.tris, M.ntris, s_tile, ro, rd, bkey);
     if (active) occ_out[i] = occ ? 1u : 0u;
+}
+
+// Interval queries (spt_trace_spheres_range) through the sphere hierarchy: trace_spheres_bvh with closest_sphere_bvh<false, true>.  Rays the
+// route keeps out of the tree go to the fallback list (range_exhaustive<true> writes their Hit); rays with an empty interval write a miss.
+__global__ __launch_bounds__(kMeshBlock) void range_spheres_bvh(const KParams K, const MParams M, const float* __restrict__ rays, uint32_t nrays,
+                                                                float* __restrict__ hits, uint32_t* __restrict__ list, uint32_t* __restrict__ qcount)
+{
+    extern __shared__ float4 s_tile[];
+    const uint32_t r = blockIdx.x * kMeshBlock + threadIdx.x;
+    const bool active = r < nrays;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    RangeKeys rk{kSphEpsBias, 0u};
+    if (active) {
+        const float4* q = reinterpret_cast<const float4*>(rays) + 2 * (size_t)r;
+        const float4 a = q[0], b = q[1];
+        ro = mk(a.x, a.y, a.z); rd = mk(b.x, b.y, b.z);
+        rk = range_sphere_keys(a.w, b.w);
+    }
+    float t_ok;
+    const GridParams G{};
+    const bool walk = rk.bound != 0u && query_ray_route(kQueryBvh, G, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, t_ok) == kQueryBvh;
+    float t;
+    const uint32_t i = closest_sphere_bvh<false, true>(K, M, M.bvh_nodes, M.bvh_tris, M.bvh_index, reinterpret_cast<uint32_t*>(s_tile), walk, ro, rd, t,
+                                                       rk.bound, rk.bias);
+    query_append(rk.bound != 0u && !walk, r, list, qcount, reinterpret_cast<unsigned long long*>(qcount + 2));
+    if (!active || (rk.bound != 0u && !walk)) return;
+    const bool hit = i != 0xFFFFFFFFu;
+    const QueryHit h = query_hit(hit, i, t, K.geom[hit ? i : 0u], ro, rd);
+    float* const out = hits + (size_t)r * 11;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) out[k] = h.f[k];
+}
+
+// Interval queries of a mesh scene (spt_trace_rays_range): trace_rays with the ray's keys.  BVH = the exact hierarchy
+// (closest_triangle_bvh_range), else the exhaustive loop (closest_triangle_range).
+template <bool BVH>
+__global__ __launch_bounds__(kMeshBlock) void trace_rays_range(const MParams M, const float* __restrict__ rays, uint64_t nrays, float* __restrict__ hits)
+{
+    extern __shared__ float4 s_tile[];
+    const uint64_t i = (uint64_t)blockIdx.x * kMeshBlock + threadIdx.x;
+    const bool active = i < nrays;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    RangeKeys rk{1u, 0u};
+    if (active) {
+        const float4* q = reinterpret_cast<const float4*>(rays) + 2 * i;
+        const float4 a = q[0], b = q[1];
+        ro = mk(a.x, a.y, a.z); rd = mk(b.x, b.y, b.z);
+        rk = range_triangle_keys(a.w, b.w);
+    }
+    float t;
+    const uint32_t tri = BVH ? closest_triangle_bvh_range(M, reinterpret_cast<uint32_t*>(s_tile), rk.bound != 0u, ro, rd, rk, t)
+                             : closest_triangle_range(M.tris, M.ntris, s_tile, active, ro, rd, rk, t);
+    if (!active) return;
+    float* h = hits + 11 * i;
+    if (tri == 0xFFFFFFFFu) {                                                    // Hit{}: dist = 1e20, the rest 0
+        h[0] = 1e20f;
+        for (int k = 1; k < 11; ++k) h[k] = 0.f;
+        return;
+    }
+    const MeshHit m = make_hit(M, tri, t, ro, rd);
+    h[0] = m.dist; h[1] = __uint_as_float(m.inst); h[2] = __uint_as_float(m.tri);
+    h[3] = m.x.x; h[4] = m.x.y; h[5] = m.x.z; h[6] = m.n.x; h[7] = m.n.y; h[8] = m.n.z; h[9] = m.u; h[10] = m.v;
 }
 
 // ---- path tracer over the mesh scene ------------------------------------------------------------------------------
@@ -903,5 +1056,24 @@ extern "C" hipError_t spt_mesh_occluded(const spt::MParams* M, const float* d_ra
     const uint64_t blocks = (nrays + spt::kMeshBlock - 1) / spt::kMeshBlock;
     if (M->bvh_nodes) hipLaunchKernelGGL(spt::occluded_rays<true>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *M, d_rays, d_tmax, nrays, d_occ);
     else hipLaunchKernelGGL(spt::occluded_rays<false>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *M, d_rays, d_tmax, nrays, d_occ);
+    return hipGetLastError();
+}
+
+// K: geom = the sphere table; M: the sphere hierarchy, as for spt_query_bvh_launch.  nrays <= kQuerySlice.
+extern "C" hipError_t spt_range_bvh_launch(const spt::KParams* K, const spt::MParams* M, const float* rays, uint32_t nrays, float* hits,
+                                           uint32_t* list, uint32_t* qcount, hipStream_t stream)
+{
+    if (nrays == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)nrays + spt::kMeshBlock - 1) / spt::kMeshBlock);
+    hipLaunchKernelGGL(spt::range_spheres_bvh, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, rays, nrays, hits, list, qcount);
+    return hipGetLastError();
+}
+
+// M as for spt_mesh_trace_rays; bvh_nodes set = the exact hierarchy (the caller passes its cones and trees).
+extern "C" hipError_t spt_mesh_trace_rays_range(const spt::MParams* M, const float* d_rays, uint64_t nrays, float* d_hits, hipStream_t stream)
+{
+    const uint64_t blocks = (nrays + spt::kMeshBlock - 1) / spt::kMeshBlock;
+    if (M->bvh_nodes) hipLaunchKernelGGL(spt::trace_rays_range<true>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *M, d_rays, nrays, d_hits);
+    else hipLaunchKernelGGL(spt::trace_rays_range<false>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *M, d_rays, nrays, d_hits);
     return hipGetLastError();
 }

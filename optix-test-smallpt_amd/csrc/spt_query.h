@@ -57,6 +57,29 @@ SPT_HD uint32_t occ_triangle_key(float tmax)          // key(t) = bits(t) - 1: r
     return b > 0.0f ? __builtin_bit_cast(uint32_t, b) - 1u : 0u;
 }
 
+// Closest-hit queries over a per-ray interval (spt_trace_*_range, spt_ray_range {o, tmin, d, tmax}).  lo = max(tmin, floor) -- floor = 1e-4
+// for spheres, +0 for triangles (a -0 or NaN tmin gives the floor) --, hi = occ_bound(tmax).  A report t lies in (lo, hi) exactly when
+//     key(t) = bits(t) - bias < bound,     bias = bits(lo) + 1,  bound = bits(hi) - bias     (unsigned 32-bit arithmetic)
+// and bound = 0 (no key beats it) when hi <= lo or either bound is NaN.  Why every other t loses, with lo < hi <= 1e20 (so bias <= bits(hi)):
+//   * +0 <= t <= lo: bits(t) < bias, the key wraps to >= 2^32 - bias >= 2^32 - 0x7F800001 > every bound (< 0x60AD78EC);
+//   * t >= hi, +inf, a negative root (sign bit set) or a NaN root (det < 0; bits >= 0x7F800001): bits(t) >= bits(hi) >= bias, no wrap,
+//     key >= bits(hi) - bias = bound.  (triIntersect's reject value 1e20 is >= hi.)
+// For a sphere, min(key1, key2) of the two roots t1 = b - det <= t2 = b + det is then the smaller root above lo when that is below hi, and
+// no report otherwise -- the same single compare as the fixed-bias keys.  At tmin <= floor and tmax >= 1e20 the pair is (bits(floor) + 1,
+// key of 1e20): the closest-hit kernels' constants, so the answer is the plain query's bit for bit.  The hit distance is bits(key + bias).
+struct RangeKeys { uint32_t bias, bound; };
+SPT_HD RangeKeys range_keys(float tmin, float tmax, float floor)
+{
+    const float lo = tmin > floor ? tmin : floor;       // NaN and -0 fail the compare
+    const float hi = occ_bound(tmax);
+    const uint32_t bias = __builtin_bit_cast(uint32_t, lo) + 1u;
+    const bool ok = (hi > lo) & (tmin == tmin);         // NaN hi fails the first, NaN tmin the second
+    return RangeKeys{bias, ok ? __builtin_bit_cast(uint32_t, hi) - bias : 0u};
+}
+SPT_HD RangeKeys range_sphere_keys(float tmin, float tmax) { return range_keys(tmin, tmax, 1e-4f); }
+SPT_HD RangeKeys range_triangle_keys(float tmin, float tmax) { return range_keys(tmin, tmax, 0.0f); }
+SPT_HD float range_key_t(uint32_t key, uint32_t bias) { return __builtin_bit_cast(float, key + bias); }
+
 #if defined(SPT_QUERY_DEVICE)      // the kernel translation units (spt_grid.hip, spt_mesh.hip: after spt_device.h)
 // Hit record of scene.h:31-43 for the sphere `g` = {centre, r*r} hit at t (Sphere::makeHit, scene.cpp:118-127): x = o + d t (scene.cpp:137),
 // n = normalize(x - centre) (:124; the guarded form: x may sit on the centre of a tiny sphere), triId = 0, uv = 0.  Miss: dist = 1e20, rest 0.
@@ -113,4 +136,14 @@ extern "C" hipError_t spt_occ_bvh_launch(const spt::KParams* K, const spt::MPara
                                          uint32_t* list, uint32_t* qcount, hipStream_t stream);
 // Mesh scenes (spt_occluded_rays*): M as for spt_mesh_trace_rays; bvh_nodes set = the exact hierarchy (the caller passes its cones and trees).
 extern "C" hipError_t spt_mesh_occluded(const spt::MParams* M, const float* d_rays, const float* d_tmax, uint64_t nrays, uint8_t* d_occ, hipStream_t stream);
+// Interval forms (spt_trace_*_range*): rays = nrays x 8 floats {o, tmin, d, tmax}, hits as for the closest-hit forms.  The walks write the Hit
+// of every ray they settle; the list form of the exhaustive loop writes the ones they hand over.
+extern "C" hipError_t spt_range_exhaustive_launch(const float4* geom, uint32_t n, const float* rays, uint32_t nrays, float* hits,
+                                                  const uint32_t* list, const uint32_t* qcount, uint32_t list_blocks, int guard_all, hipStream_t stream);
+extern "C" hipError_t spt_range_grid_launch(const float4* geom, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
+                                            const uint32_t* d_always, int where, const float* rays, uint32_t nrays, float* hits,
+                                            uint32_t* list, uint32_t* qcount, uint32_t blocks, hipStream_t stream);
+extern "C" hipError_t spt_range_bvh_launch(const spt::KParams* K, const spt::MParams* M, const float* rays, uint32_t nrays, float* hits,
+                                           uint32_t* list, uint32_t* qcount, hipStream_t stream);
+extern "C" hipError_t spt_mesh_trace_rays_range(const spt::MParams* M, const float* d_rays, uint64_t nrays, float* d_hits, hipStream_t stream);
 #endif

@@ -78,6 +78,7 @@ public:
     //   Vector<Hit> traceRays(const PathContrib*, size_t)    ->  traceRays(rays, n)
     //   cpuIntersectGlobalSpheres(pathBuffer, pathCount, hits) ->  traceSpheres(rays, n)
     //   RTP_QUERY_TYPE_ANY with OptixRay::tmax (:395-403,579)  ->  occludedSpheres / occludedRays(rays, tmax, n)
+    //   RTP_QUERY_TYPE_CLOSEST over OptixRay (:395-403,579)   ->  traceSpheresRange / traceRaysRange(optixRays, n)
     void setMeshes(const std::vector<TriMesh>& meshes, const std::vector<Material>& materials)
     {
         if (meshes.size() != materials.size()) throw std::runtime_error("setMeshes: one material per mesh instance");
@@ -148,6 +149,30 @@ public:
     void occludedRaysDevice(const void* dRays, const void* dTmax, size_t n, void* dOccluded, void* hipStream = nullptr)
     {
         check(spt_occluded_rays_device(ctx_, dRays, dTmax, (uint64_t)n, dOccluded, hipStream));
+    }
+
+    // Closest hit inside a per-ray interval, OptiX Prime's RTP_QUERY_TYPE_CLOSEST over OptixRay {origin, tmin, direction, tmax}
+    // (smallpt.cpp:395-403,559-569,579): the reference's optixRays buffer passes through as spt_ray_range (contract in include/smallpt_mi355x.h)
+    std::vector<Hit> traceSpheresRange(const spt_ray_range* rays, size_t n)
+    {
+        std::vector<Hit> hits(n);
+        check(spt_trace_spheres_range(ctx_, rays, (uint64_t)n, reinterpret_cast<spt_hit*>(hits.data())));
+        return hits;
+    }
+    void traceSpheresRangeDevice(const void* dRays, size_t n, void* dHits, void* hipStream = nullptr)
+    {
+        check(spt_trace_spheres_range_device(ctx_, dRays, (uint64_t)n, dHits, hipStream));
+    }
+    // the same against the current mesh scene
+    std::vector<Hit> traceRaysRange(const spt_ray_range* rays, size_t n)
+    {
+        std::vector<Hit> hits(n);
+        check(spt_trace_rays_range(ctx_, rays, (uint64_t)n, reinterpret_cast<spt_hit*>(hits.data())));
+        return hits;
+    }
+    void traceRaysRangeDevice(const void* dRays, size_t n, void* dHits, void* hipStream = nullptr)
+    {
+        check(spt_trace_rays_range_device(ctx_, dRays, (uint64_t)n, dHits, hipStream));
     }
 
     const spt_stats& stats() const { return stats_; }

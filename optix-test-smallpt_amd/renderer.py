@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import SptCamera, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
-from .scene import HIT_DTYPE, RAY_DTYPE, SPHERE_DTYPE
+from .scene import HIT_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
 FLAG_ONE_SHOT = 2          # scheduling only: no dispatch order used or recorded for this launch (include/smallpt_mi355x.h)
@@ -29,6 +29,54 @@ def _ray_array(rays):
     if a.ndim != 2 or a.shape[1] != 6:
         raise ValueError(f"rays: expected shape (n, 6), got {a.shape}")
     return np.ascontiguousarray(a, dtype=np.float32).view(RAY_DTYPE).reshape(-1)
+
+
+def _range_array(who, rays):
+    """RAY_RANGE_DTYPE[n], or floats of shape (n, 8) {o, tmin, d, tmax}, as a contiguous RAY_RANGE_DTYPE array; anything else is refused."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_RANGE_DTYPE:
+        if a.ndim != 1:
+            raise ValueError(f"{who}: expected a 1-D array of RAY_RANGE_DTYPE, got shape {a.shape}")
+        return np.ascontiguousarray(a)
+    if a.dtype.fields is not None or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{who}: expected RAY_RANGE_DTYPE or real numbers, got dtype {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"{who}: expected rays of shape (n, 8) {{o, tmin, d, tmax}}, got {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32).view(RAY_RANGE_DTYPE).reshape(-1)
+
+
+def _range_host(r, who, name, rays):
+    """Renderer.trace_spheres_range / trace_rays_range: the rays are checked before the library is called."""
+    rays = _range_array(who, rays)
+    n = len(rays)
+    hits = np.zeros(n, dtype=HIT_DTYPE)
+    r._check(getattr(r._lib, name)(r._h, rays.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)))
+    return hits
+
+
+def _range_device(r, who, name, rays_t, hits_t, stream):
+    """Renderer.trace_spheres_range_device / trace_rays_range_device: the same, for device tensors."""
+    import torch
+    if not (isinstance(rays_t, torch.Tensor) and rays_t.is_cuda and rays_t.dtype == torch.float32 and rays_t.is_contiguous()
+            and rays_t.dim() == 2 and rays_t.shape[1] == 8 and rays_t.data_ptr() % 16 == 0):
+        raise ValueError(f"{who}: rays_t must be a contiguous, 16-byte aligned float32 device tensor of shape (n, 8)")
+    n = rays_t.shape[0]
+    if hits_t is None:
+        hits_t = torch.empty((n, 11), dtype=torch.float32, device=rays_t.device)
+    elif not (isinstance(hits_t, torch.Tensor) and hits_t.device == rays_t.device and hits_t.dtype == torch.float32
+              and hits_t.is_contiguous() and tuple(hits_t.shape) == (n, 11)):
+        raise ValueError(f"{who}: hits_t must be a contiguous float32 tensor of shape (n, 11) on the rays' device")
+    fn = getattr(r._lib, name)
+    stream = stream if stream is not None else torch.cuda.current_stream(rays_t.device)
+    if stream.cuda_stream == 0:
+        # handle 0 would be the context's own stream, not ordered with torch's default one: as trace_spheres_device
+        side = torch.cuda.Stream(rays_t.device)
+        side.wait_stream(stream)
+        r._check(fn(r._h, C.c_void_p(rays_t.data_ptr()), n, C.c_void_p(hits_t.data_ptr()), C.c_void_p(side.cuda_stream)))
+        stream.wait_stream(side)
+        return hits_t
+    r._check(fn(r._h, C.c_void_p(rays_t.data_ptr()), n, C.c_void_p(hits_t.data_ptr()), C.c_void_p(stream.cuda_stream)))
+    return hits_t
 
 
 def _occluded_host(r, who, name, rays, tmax):
@@ -295,8 +343,27 @@ class Renderer:
         """spt_occluded_rays_device: as occluded_spheres_device, against the current mesh scene."""
         return _occluded_device(self, "occluded_rays_device", "spt_occluded_rays_device", rays_t, tmax_t, out_t, stream)
 
+    def trace_spheres_range(self, rays):
+        """Closest hit inside a per-ray interval against the current sphere table (spt_trace_spheres_range; OptiX Prime's
+        RTP_QUERY_TYPE_CLOSEST over OptixRay {o, tmin, d, tmax}, smallpt.cpp:395-403): rays = RAY_RANGE_DTYPE[n] or floats (n, 8); returns
+        HIT_DTYPE[n].  The report of a sphere is its smaller root above max(tmin, 1e-4) if that is below min(tmax, 1e20)."""
+        return _range_host(self, "trace_spheres_range", "spt_trace_spheres_range", rays)
+
+    def trace_rays_range(self, rays):
+        """The same against the current mesh scene (spt_trace_rays_range: triangles report max(tmin, 0) < t < min(tmax, 1e20))."""
+        return _range_host(self, "trace_rays_range", "spt_trace_rays_range", rays)
+
+    def trace_spheres_range_device(self, rays_t, hits_t=None, stream=None):
+        """spt_trace_spheres_range_device: rays_t = contiguous float32 device tensor (n, 8); returns the float32 tensor (n, 11) of Hit records
+        (hits_t if given), enqueued on `stream` (a torch stream; default: the current one)."""
+        return _range_device(self, "trace_spheres_range_device", "spt_trace_spheres_range_device", rays_t, hits_t, stream)
+
+    def trace_rays_range_device(self, rays_t, hits_t=None, stream=None):
+        """spt_trace_rays_range_device: as trace_spheres_range_device, against the current mesh scene."""
+        return _range_device(self, "trace_rays_range_device", "spt_trace_rays_range_device", rays_t, hits_t, stream)
+
     def last_query_path(self):
-        """What the last trace_spheres* / occluded_spheres* query ran through and how many of its rays the walk handed to the exhaustive loop:
+        """What the last trace_spheres* / trace_spheres_range* / occluded_spheres* query ran through and how many of its rays the walk handed to the exhaustive loop:
         ("exhaustive" | "grid" | "bvh" | None before the first query, fallback_rays).  Waits for that query."""
         fb = C.c_uint64(0)
         path = self._lib.spt_last_query_path(self._h, C.byref(fb))

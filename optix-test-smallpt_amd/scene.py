@@ -107,6 +107,8 @@ def spheres_from_json(text):
 HIT_DTYPE = np.dtype([("dist", "<f4"), ("instId", "<u4"), ("triId", "<u4"), ("x", "<f4", 3), ("n", "<f4", 3), ("uv", "<f4", 2)])   # Hit, scene.h:31-43
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3)])                                                                           # Ray, scene.h:58-62
 assert HIT_DTYPE.itemsize == 44 and RAY_DTYPE.itemsize == 24
+RAY_RANGE_DTYPE = np.dtype([("o", "<f4", 3), ("tmin", "<f4"), ("d", "<f4", 3), ("tmax", "<f4")])                                   # OptixRay, smallpt.cpp:395-403
+assert RAY_RANGE_DTYPE.itemsize == 32
 
 
 class TriMesh:
