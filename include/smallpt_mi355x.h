@@ -28,6 +28,8 @@
  *   OptiX Prime RTP_QUERY_TYPE_CLOSEST over OptixRay             spt_trace_spheres_range(), spt_trace_rays_range() (host),
  *     {origin, tmin, direction, tmax} (smallpt.cpp:395-403,     spt_trace_spheres_range_device(),
  *     559-569,579): closest hit inside a per-ray interval        spt_trace_rays_range_device() (device buffers, async)
+ *   rtpModelSetInstances with RTP_BUFFER_FORMAT_TRANSFORM_       spt_set_instances(), spt_instance_inverse()
+ *     FLOAT4x3 + INSTANCE_MODEL (smallpt.cpp:489-530)
  *   accumBuffer += outImage under accumBufferMutex and the      spt_progressive_begin / _frame / _snapshot / _end
  *     GL thread's copy of it (smallpt.cpp:881-883,924-940,       (accumulation buffer resident in HBM)
  *     955-959)
@@ -258,6 +260,51 @@ int  spt_trace_spheres_range(spt_ctx* ctx, const spt_ray_range* rays, uint64_t n
 int  spt_trace_spheres_range_device(spt_ctx* ctx, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream);
 int  spt_trace_rays_range(spt_ctx* ctx, const spt_ray_range* rays, uint64_t n, spt_hit* hits);
 int  spt_trace_rays_range_device(spt_ctx* ctx, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream);
+
+/* ---- mesh instances: OptixIntersector::build's instanced model (smallpt.cpp:489-530): one model per mesh, one
+ * RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 matrix and one RTP_BUFFER_FORMAT_INSTANCE_MODEL entry per instance (:514-529),
+ * rtpModelSetInstances(models, transforms).  56 bytes per instance. */
+typedef struct spt_instance { float transform[12]; uint32_t model; uint32_t pad; } spt_instance;
+#if defined(__cplusplus)
+static_assert(sizeof(spt_instance) == 56, "spt_instance: FLOAT4x3 + model index, 56 bytes");
+#else
+_Static_assert(sizeof(spt_instance) == 56, "spt_instance: FLOAT4x3 + model index, 56 bytes");
+#endif
+#define SPT_MAX_INSTANCES 65536u
+/* Makes an INSTANCED MESH SCENE current: models[m] are meshes as for spt_set_meshes, instances[i] places model instances[i].model with its
+ * transform, materials[i] belongs to instance i (ninst materials).  Each model's structures are built once, however many instances use it.
+ * spt_set_meshes and spt_set_scene switch away from it.  A failed call leaves the previous scene current (message in spt_last_error); a call
+ * fails on NULL buffers, model >= nmodels, ninst == 0 or > SPT_MAX_INSTANCES, a non-finite matrix entry, a rejected inverse
+ * (spt_instance_inverse) and everything spt_set_meshes rejects for a mesh or a material.
+ * Every mesh entry point takes the scene: spt_trace_rays*, spt_occluded_rays*, spt_trace_rays_range*, spt_render, spt_render_rows_device,
+ * spt_render_interleaved_device, spt_progressive_* and spt_render_aov*; spt_set_mesh_accel applies.  The multi-GPU front does not take it.
+ *
+ * Arithmetic (pinned bit for bit by the tests; csrc/spt_instance.h):
+ *   A = transform, row-major 3x4: x_world_i = A[i][0] x + A[i][1] y + A[i][2] z + A[i][3].
+ *   Identity: an instance whose 12 entries all compare equal, as floats, to the identity uses the ray and the Hit untransformed.
+ *   Inverse {W | w} (spt_instance_inverse), on the host in double: adj from the nine 2x2 cofactors, each a*b - c*d;
+ *     det = (a00 adj00 + a01 adj10) + a02 adj20; Wd = adj / det; W = (float)Wd; w_i = (float)(-((Wd[i][0] a03 + Wd[i][1] a13) + Wd[i][2] a23)).
+ *     Rejected when det == 0 or an entry of {W | w} is not finite in float.
+ *   Per instance, float32, one rounding per operation: o'_i = ((W[i][0] o.x + W[i][1] o.y) + W[i][2] o.z) + w[i],
+ *     d'_i = (W[i][0] d.x + W[i][1] d.y) + W[i][2] d.z; the object-space ray meets the model's triangles with triIntersect unchanged and a
+ *     report's dist is that t (the ray parameter means the same in both spaces).
+ *   Selection: the smallest dist over every (instance, triangle); ties go to the lowest instance, then the lowest triangle of the model.
+ *   Hit: x = A applied to makeHit's object-space point, ((A[i][0] x + A[i][1] y) + A[i][2] z) + A[i][3]; n = W^T applied to makeHit's
+ *     normal, (W[0][i] n.x + W[1][i] n.y) + W[2][i] n.z (not normalised); uv unchanged; instId = the instance; triId = the triangle within
+ *     the model.  Miss: dist = 1e20, every other field 0.
+ *   Range queries: lo = max(tmin, 0) and hi = min(tmax, 1e20) bound the object-space t as in spt_trace_rays_range.  Occlusion: the byte is
+ *     h.dist < 1e20 && h.dist < tmax for the instanced Hit h.  Renders shade the instanced Hit as they shade a spt_set_meshes Hit, with
+ *     materials[instId].
+ *   The answer is the same in every accel mode: SPT_ACCEL_BVH walks each model's exact hierarchy with the object-space ray,
+ *     SPT_ACCEL_EXHAUSTIVE loops over each model's triangles, SPT_ACCEL_BVH_FAST answers through the exact hierarchy, SPT_ACCEL_AUTO applies
+ *     its rule to the sum over instances of the model's triangle count.  The cost per ray is linear in the instance count.
+ *   Anchor: each mesh its own model, identity instances i -> model i and the same materials give every query, render, progressive frame
+ *     and AOV bit-identical to spt_set_meshes(meshes, materials), in every accel mode.  (In SPT_ACCEL_BVH_FAST that is the mesh scene's exact
+ *     answer: its plain hierarchy may differ on rays in a triangle's plane, see above; the instanced scene has no such exception.) */
+int  spt_set_instances(spt_ctx* ctx, const spt_mesh* models, uint32_t nmodels, const spt_instance* instances, uint32_t ninst,
+                       const spt_material* materials);
+/* Host-only: the inverse {W | w} that spt_set_instances uses (above), same 3x4 layout.  0 = ok, non-zero = rejected. */
+int  spt_instance_inverse(const float transform[12], float inverse[12]);
 /* Host-only helper: makeSphereTriMesh(origin, radius, subdivLongitude) (scene.cpp:3-48): fills (L+1)(2L+1) positions and
  * normals and 4L^2 triangles (L = subdiv_longitude, default 32 at scene.h:17); returns the triangle count. */
 uint32_t spt_make_sphere_trimesh(const float origin[3], float radius, uint32_t subdiv_longitude,

@@ -36,6 +36,10 @@ class SptMaterial(C.Structure):      # Material, scene.h:66-73
     _fields_ = [("emission", C.c_float * 3), ("color", C.c_float * 3), ("refl", C.c_int32), ("pad", C.c_uint32)]
 
 
+class SptInstance(C.Structure):      # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
+    _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # every symbol include/smallpt_mi355x.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -60,6 +64,8 @@ SYMBOLS = {
     "spt_occluded_spheres_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "spt_occluded_rays": (C.c_int, [_P, _P, _P, C.c_uint64, _P]),
     "spt_occluded_rays_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
+    "spt_set_instances": (C.c_int, [_P, C.POINTER(SptMesh), C.c_uint32, C.POINTER(SptInstance), C.c_uint32, C.POINTER(SptMaterial)]),
+    "spt_instance_inverse": (C.c_int, [_P, _P]),
     "spt_make_sphere_trimesh": (C.c_uint32, [C.c_float * 3, C.c_float, C.c_uint32, _P, _P, _P]),
     "spt_camera_smallpt": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(SptCamera)]),
     "spt_camera_pinhole": (C.c_int, [C.c_float * 3, C.c_float * 3, C.c_float * 3, C.c_float * 3, C.c_float, C.POINTER(SptCamera)]),

@@ -7,6 +7,7 @@
 #include "spt_kernel.h"
 #include "spt_query.h"
 #include "spt_aov.h"
+#include "spt_instance.h"
 
 #include <chrono>
 #include <cmath>
@@ -40,6 +41,22 @@ inline uint32_t mix32(uint32_t x)
 
 }  // namespace
 
+// An instanced mesh scene (spt_set_instances): per model its host triangle records and its device descriptor (the MParams of a
+// spt_set_meshes scene holding that model alone), the device copies of the descriptors, instance records and per-instance material rows,
+// and every device buffer it owns.
+struct InstScene {
+    std::vector<std::vector<float4>> tris;
+    std::vector<spt::MParams> models;
+    std::vector<void*> allocs;
+    spt::MParams* d_models = nullptr;
+    spt::InstRec* d_inst = nullptr;
+    float4* d_mats = nullptr;
+    uint32_t ninst = 0;
+    uint64_t tri_sum = 0;            // sum over instances of the model's triangles (SPT_ACCEL_AUTO)
+    bool specular = false;
+    bool accel_built = false;        // every model's hierarchy is in its descriptor
+};
+
 struct spt_ctx {
     int device = 0;
     int cu_count = 0;
@@ -55,7 +72,7 @@ struct spt_ctx {
     float* d_stack = nullptr;      // pool kernel: global-memory stack of pending transmitted children
     size_t stack_cap = 0;          // in floats
     bool last_was_pool = false;
-    int last_kernel = 0;           // 0 megakernel, 1 pool kernel, 2 mesh kernel (triangles; 6 / 7: through the exact / the plain hierarchy), 3 mesh kernel over a sphere hierarchy, 4 grid kernel (lanes own paths), 5 grid kernel with path pools
+    int last_kernel = 0;           // 0 megakernel, 1 pool kernel, 2 mesh kernel (triangles; 6 / 7: through the exact / the plain hierarchy), 3 mesh kernel over a sphere hierarchy, 4 grid kernel (lanes own paths), 5 grid kernel with path pools, 8 mesh kernel over instances
     // triangle-mesh scene (spt_set_meshes); mesh_scene selects it for spt_render*
     bool mesh_scene = false;
     bool mesh_specular = false;            // a mesh material is SPEC or REFR: long mirror / glass chains are possible (task dealing of the hierarchy kernel)
@@ -89,6 +106,8 @@ struct spt_ctx {
     float4* d_bvh_cones = nullptr; float4* d_plane_nodes = nullptr; float4* d_line_nodes = nullptr; bool have_planes = false, have_lines = false;   // spt_tribvh.h
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0;
     uint32_t ntris = 0, ninst = 0;
+    bool inst_scene = false;         // the current mesh scene is instanced (spt_set_instances): ntris = min(tri_sum, 2^32 - 1), ninst = instances
+    InstScene inst;
     float* d_accum = nullptr;      // spt_progressive_*: accumBuffer (smallpt.cpp:881-883) and the current frame, w*h*3 floats each
     float* d_frame = nullptr;
     uint32_t prog_w = 0, prog_h = 0;
@@ -244,6 +263,7 @@ void spt_destroy(spt_ctx* c)
     if (c->d_verts) (void)hipFree(c->d_verts);
     if (c->d_inst_first) (void)hipFree(c->d_inst_first);
     if (c->d_mesh_mats) (void)hipFree(c->d_mesh_mats);
+    for (void* p : c->inst.allocs) (void)hipFree(p);
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_mid) (void)hipEventDestroy(c->ev_mid);
@@ -281,6 +301,7 @@ int spt_set_tuning(spt_ctx* c, uint32_t blocks_per_cu, uint32_t variant)
 // IEEE operations on the host, bit-identical to evaluating them per bounce:
 //   r*r (scene.cpp:133), pmax = fmaxf(color) (smallpt.cpp:177), color*(1/pmax) (smallpt.cpp:192).
 static int set_scene_impl(spt_ctx* c, const spt_sphere* s, uint32_t n);
+static void free_inst_scene(spt_ctx* c);
 static int build_sphere_accel(spt_ctx* c);
 static int build_default_sphere_structure(spt_ctx* c);
 static int build_sphere_grid_tables(spt_ctx* c);
@@ -351,6 +372,7 @@ static int set_scene_impl(spt_ctx* c, const spt_sphere* s, uint32_t n)
     c->n = n;
     ++c->scene_gen;
     c->mesh_scene = false;
+    free_inst_scene(c);
     c->h_geom.assign(geom.begin(), geom.begin() + n);
     c->h_radius.resize(n);
     for (uint32_t i = 0; i < n; ++i) c->h_radius[i] = s[i].radius;
@@ -604,6 +626,7 @@ uint32_t spt_make_sphere_trimesh(const float origin[3], float radius, uint32_t s
 
 static int set_meshes_impl(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, const spt_material* materials);
 static int build_accel(spt_ctx* c);
+static int build_inst_accel(spt_ctx* c, InstScene& s, const char* who);
 
 int spt_set_meshes(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, const spt_material* materials)
 {
@@ -615,6 +638,41 @@ int spt_set_meshes(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, const spt
     }
 }
 
+// What spt_set_meshes / spt_set_instances reject for one mesh and one material (`who` names the call in the message).
+static int check_mesh(spt_ctx* c, const char* who, uint32_t i, const spt_mesh& m)
+{
+    if ((m.ntris && !m.indices) || (m.nverts && (!m.positions || !m.normals))) return c->fail("%s: mesh %u has NULL buffers", who, i);
+    for (uint64_t k = 0; k < (uint64_t)m.ntris * 3; ++k)
+        if (m.indices[k] >= m.nverts) return c->fail("%s: mesh %u index %u out of range (%u vertices)", who, i, m.indices[k], m.nverts);
+    return 0;
+}
+static int check_material(spt_ctx* c, const char* who, uint32_t i, const spt_material& mat)
+{
+    if (mat.refl < SPT_DIFF || mat.refl > SPT_REFR) return c->fail("%s: material %u has refl=%d", who, i, mat.refl);
+    return 0;
+}
+
+// Flattens one mesh: its vertices from vbase on, its triangles from t on (records with the per-call constants of triIntersect, scene.cpp:56-60,
+// evaluated once; index records {global vertex ids, instance}).  Advances t.
+static void flatten_mesh(const spt_mesh& m, uint32_t inst, size_t vbase, size_t& t, std::vector<float4>& tris, std::vector<uint4>& tidx,
+                         std::vector<float4>& verts)
+{
+    for (uint32_t v = 0; v < m.nverts; ++v) {
+        verts[2 * (vbase + v)] = make_float4(m.positions[3 * v], m.positions[3 * v + 1], m.positions[3 * v + 2], 0.f);
+        verts[2 * (vbase + v) + 1] = make_float4(m.normals[3 * v], m.normals[3 * v + 1], m.normals[3 * v + 2], 0.f);
+    }
+    for (uint32_t k = 0; k < m.ntris; ++k, ++t) {
+        const uint32_t i1 = m.indices[3 * k], i2 = m.indices[3 * k + 1], i3 = m.indices[3 * k + 2];
+        const HostF3 v0 = hld(m.positions + 3 * i1), v1 = hld(m.positions + 3 * i2), v2 = hld(m.positions + 3 * i3);
+        const HostF3 e1 = hsub(v1, v0), e2 = hsub(v2, v0);                          // scene.cpp:56-57
+        const HostF3 n = hcross(e1, e2);                                            // :60
+        tris[3 * t] = make_float4(v0.x, v0.y, v0.z, n.x);
+        tris[3 * t + 1] = make_float4(e1.x, e1.y, e1.z, n.y);
+        tris[3 * t + 2] = make_float4(e2.x, e2.y, e2.z, n.z);
+        tidx[t] = make_uint4((uint32_t)vbase + i1, (uint32_t)vbase + i2, (uint32_t)vbase + i3, inst);
+    }
+}
+
 static int set_meshes_impl(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, const spt_material* materials)
 {
     if (nmesh && (!meshes || !materials)) return c->fail("spt_set_meshes: NULL argument");
@@ -622,9 +680,7 @@ static int set_meshes_impl(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, c
     for (uint32_t i = 0; i < nmesh; ++i) {
         const spt_mesh& m = meshes[i];
         if ((m.ntris && !m.indices) || (m.nverts && (!m.positions || !m.normals))) return c->fail("spt_set_meshes: mesh %u has NULL buffers", i);
-        if (materials[i].refl < SPT_DIFF || materials[i].refl > SPT_REFR) return c->fail("spt_set_meshes: material %u has refl=%d", i, materials[i].refl);
-        for (uint64_t k = 0; k < (uint64_t)m.ntris * 3; ++k)
-            if (m.indices[k] >= m.nverts) return c->fail("spt_set_meshes: mesh %u index %u out of range (%u vertices)", i, m.indices[k], m.nverts);
+        if (check_material(c, "spt_set_meshes", i, materials[i]) || check_mesh(c, "spt_set_meshes", i, m)) return 1;
         ntris += m.ntris; nverts += m.nverts;
     }
     if (ntris > 0x7FFFFFFFull || nverts > 0x7FFFFFFFull) return c->fail("spt_set_meshes: too many triangles");
@@ -639,20 +695,7 @@ static int set_meshes_impl(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, c
     for (uint32_t i = 0; i < nmesh; ++i) {
         const spt_mesh& m = meshes[i];
         first[i] = (uint32_t)t;
-        for (uint32_t v = 0; v < m.nverts; ++v) {
-            verts[2 * (vbase + v)] = make_float4(m.positions[3 * v], m.positions[3 * v + 1], m.positions[3 * v + 2], 0.f);
-            verts[2 * (vbase + v) + 1] = make_float4(m.normals[3 * v], m.normals[3 * v + 1], m.normals[3 * v + 2], 0.f);
-        }
-        for (uint32_t k = 0; k < m.ntris; ++k, ++t) {
-            const uint32_t i1 = m.indices[3 * k], i2 = m.indices[3 * k + 1], i3 = m.indices[3 * k + 2];
-            const HostF3 v0 = hld(m.positions + 3 * i1), v1 = hld(m.positions + 3 * i2), v2 = hld(m.positions + 3 * i3);
-            const HostF3 e1 = hsub(v1, v0), e2 = hsub(v2, v0);                          // scene.cpp:56-57
-            const HostF3 n = hcross(e1, e2);                                            // :60
-            tris[3 * t] = make_float4(v0.x, v0.y, v0.z, n.x);
-            tris[3 * t + 1] = make_float4(e1.x, e1.y, e1.z, n.y);
-            tris[3 * t + 2] = make_float4(e2.x, e2.y, e2.z, n.z);
-            tidx[t] = make_uint4((uint32_t)vbase + i1, (uint32_t)vbase + i2, (uint32_t)vbase + i3, i);
-        }
+        flatten_mesh(m, i, vbase, t, tris, tidx, verts);
         vbase += m.nverts;
         material_rows(materials[i].emission, materials[i].color, materials[i].refl, &mats[3 * (size_t)i]);
         specular = specular || materials[i].refl != SPT_DIFF;
@@ -671,6 +714,7 @@ static int set_meshes_impl(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, c
     SPT_HIP(c, upload(c->d_inst_first, first.data(), first.size() * sizeof(uint32_t)));
     SPT_HIP(c, upload(c->d_mesh_mats, mats.data(), mats.size() * sizeof(float4)));
     c->ntris = (uint32_t)ntris; c->ninst = nmesh;
+    free_inst_scene(c);
     c->mesh_scene = true;
     c->mesh_specular = specular;
     c->mesh_ratio = -1.f;
@@ -711,6 +755,172 @@ static int build_accel(spt_ctx* c)
     return 0;
 }
 
+// ---- mesh instances (spt_set_instances; spt_instance.h) ----
+static void free_inst_scene(spt_ctx* c)
+{
+    for (void* p : c->inst.allocs) (void)hipFree(p);
+    c->inst = InstScene{};
+    c->inst_scene = false;
+}
+
+extern "C++" {
+template <typename T>
+static hipError_t inst_upload(InstScene& s, T*& dptr, const void* src, size_t bytes)
+{
+    dptr = nullptr;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    if (e != hipSuccess) return e;
+    s.allocs.push_back(p);
+    dptr = static_cast<T*>(p);
+    return bytes ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+}
+}
+
+// Builds every model's structures (build_accel's products, over the model alone) into its descriptor and uploads the descriptors again.
+static int build_inst_accel(spt_ctx* c, InstScene& s, const char* who)
+{
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+    for (size_t m = 0; m < s.models.size(); ++m) {
+        if (s.models[m].bvh_nodes) continue;
+        spt::MParams M = s.models[m];                                  // (stored only once complete)
+        spt::Bvh bvh;
+        spt::build_bvh(s.tris[m].data(), M.ntris, bvh);
+        hipError_t e = inst_upload(s, M.bvh_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float4));
+        if (e == hipSuccess) e = inst_upload(s, M.bvh_tris, bvh.tris.data(), bvh.tris.size() * sizeof(float4));
+        if (e == hipSuccess) e = inst_upload(s, M.bvh_index, bvh.index.data(), bvh.index.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = inst_upload(s, M.bvh_cones, bvh.cones.data(), bvh.cones.size() * sizeof(float4));
+        if (e == hipSuccess && !bvh.planes.empty()) e = inst_upload(s, M.plane_nodes, bvh.planes.data(), bvh.planes.size() * sizeof(float4));
+        if (e == hipSuccess && !bvh.lines.empty()) e = inst_upload(s, M.line_nodes, bvh.lines.data(), bvh.lines.size() * sizeof(float4));
+        if (e == hipSuccess && bvh.flat && bvh.thin_count) {
+            e = inst_upload(s, M.flat_lines, bvh.flat_lines.data(), bvh.flat_lines.size() * sizeof(float4));
+            if (e == hipSuccess) e = inst_upload(s, M.flat_line_index, bvh.flat_line_index.data(), bvh.flat_line_index.size() * sizeof(uint32_t));
+            M.nline_slots = (uint32_t)bvh.flat_lines.size();
+        }
+        if (e != hipSuccess) return c->fail("%s: %s", who, hipGetErrorString(e));
+        s.models[m] = M;
+    }
+    SPT_HIP(c, hipMemcpy(s.d_models, s.models.data(), s.models.size() * sizeof(spt::MParams), hipMemcpyHostToDevice));
+    s.accel_built = true;
+    return 0;
+}
+
+static int set_instances_impl(spt_ctx* c, const spt_mesh* models, uint32_t nmodels, const spt_instance* instances, uint32_t ninst,
+                              const spt_material* materials)
+{
+    static const char* who = "spt_set_instances";
+    if (!models || !instances || !materials) return c->fail("%s: NULL argument", who);
+    if (ninst == 0 || ninst > SPT_MAX_INSTANCES) return c->fail("%s: ninst = %u, must be 1 .. SPT_MAX_INSTANCES (%u)", who, ninst, SPT_MAX_INSTANCES);
+    for (uint32_t m = 0; m < nmodels; ++m) {
+        if (check_mesh(c, who, m, models[m])) return 1;
+        if (models[m].ntris > 0x7FFFFFFFu || models[m].nverts > 0x7FFFFFFFu) return c->fail("%s: mesh %u has too many triangles", who, m);
+    }
+    InstScene s;
+    std::vector<spt::InstRec> recs(ninst);
+    std::vector<float4> mats(3 * (size_t)ninst);
+    for (uint32_t i = 0; i < ninst; ++i) {
+        const spt_instance& in = instances[i];
+        if (in.model >= nmodels) return c->fail("%s: instance %u names model %u of %u", who, i, in.model, nmodels);
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(in.transform[k])) return c->fail("%s: instance %u has a non-finite matrix entry (%d)", who, i, k);
+        if (check_material(c, who, i, materials[i])) return 1;
+        spt::InstRec& r = recs[i];
+        std::memset(&r, 0, sizeof r);
+        std::memcpy(r.a, in.transform, sizeof r.a);
+        if (spt::inst_inverse(in.transform, r.w)) return c->fail("%s: instance %u has a singular matrix, or its inverse overflows float", who, i);
+        r.model = in.model;
+        r.identity = spt::inst_is_identity(in.transform) ? 1u : 0u;
+        material_rows(materials[i].emission, materials[i].color, materials[i].refl, &mats[3 * (size_t)i]);
+        s.specular = s.specular || materials[i].refl != SPT_DIFF;
+        s.tri_sum += models[in.model].ntris;
+    }
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+    // per model: the tables of a spt_set_meshes scene holding that model alone (instance field 0)
+    s.tris.resize(nmodels);
+    s.models.resize(nmodels);
+    auto fail_free = [&](hipError_t e) { for (void* p : s.allocs) (void)hipFree(p); return c->fail("%s: %s", who, hipGetErrorString(e)); };
+    for (uint32_t m = 0; m < nmodels; ++m) {
+        const spt_mesh& mesh = models[m];
+        std::vector<float4>& tris = s.tris[m];
+        tris.resize(3 * (size_t)(mesh.ntris ? mesh.ntris : 1));
+        std::vector<float4> verts(2 * (size_t)(mesh.nverts ? mesh.nverts : 1));
+        std::vector<uint4> tidx((size_t)(mesh.ntris ? mesh.ntris : 1));
+        size_t t = 0;
+        flatten_mesh(mesh, 0u, 0, t, tris, tidx, verts);
+        const uint32_t first[2] = {0u, mesh.ntris};
+        spt::MParams& M = s.models[m];
+        M = spt::MParams{};
+        hipError_t e = inst_upload(s, M.tris, tris.data(), tris.size() * sizeof(float4));
+        if (e == hipSuccess) e = inst_upload(s, M.tri_index, tidx.data(), tidx.size() * sizeof(uint4));
+        if (e == hipSuccess) e = inst_upload(s, M.verts, verts.data(), verts.size() * sizeof(float4));
+        if (e == hipSuccess) e = inst_upload(s, M.inst_first_tri, first, sizeof first);
+        if (e != hipSuccess) return fail_free(e);
+        M.ntris = mesh.ntris; M.ninst = 1;
+        tris.resize(3 * (size_t)mesh.ntris);
+    }
+    hipError_t e = inst_upload(s, s.d_models, s.models.data(), s.models.size() * sizeof(spt::MParams));
+    if (e == hipSuccess) e = inst_upload(s, s.d_inst, recs.data(), recs.size() * sizeof(spt::InstRec));
+    if (e == hipSuccess) e = inst_upload(s, s.d_mats, mats.data(), mats.size() * sizeof(float4));
+    if (e != hipSuccess) return fail_free(e);
+    s.ninst = ninst;
+    if (c->accel != SPT_ACCEL_EXHAUSTIVE) {
+        try {
+            if (build_inst_accel(c, s, who)) { for (void* p : s.allocs) (void)hipFree(p); return 1; }
+        } catch (...) {
+            for (void* p : s.allocs) (void)hipFree(p);
+            throw;
+        }
+    }
+    // commit: the instanced scene becomes current
+    free_inst_scene(c);
+    c->inst = std::move(s);
+    c->inst_scene = true;
+    c->mesh_scene = true;
+    c->mesh_specular = c->inst.specular;
+    c->ntris = c->inst.tri_sum > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c->inst.tri_sum;
+    c->ninst = ninst;
+    c->mesh_ratio = -1.f;
+    c->bvh_ready = c->inst.accel_built;
+    c->cam_valid = false;
+    ++c->scene_gen;
+    return 0;
+}
+
+int spt_set_instances(spt_ctx* c, const spt_mesh* models, uint32_t nmodels, const spt_instance* instances, uint32_t ninst, const spt_material* materials)
+{
+    if (!c) return 1;
+    try {
+        return set_instances_impl(c, models, nmodels, instances, ninst, materials);
+    } catch (const std::exception& e) {
+        return c->fail("spt_set_instances: %s", e.what());
+    }
+}
+
+int spt_instance_inverse(const float transform[12], float inverse[12])
+{
+    if (!transform || !inverse) return 1;
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(transform[k])) return 1;
+    return spt::inst_inverse(transform, inverse);
+}
+
+// Launch parameters of the current instanced scene: I for the kernels, M = the per-instance materials and the task dealing of renders.
+static spt::IParams inst_params(const spt_ctx* c)
+{
+    spt::IParams I{};
+    I.inst = c->inst.d_inst; I.models = c->inst.d_models; I.ninst = c->inst.ninst;
+    return I;
+}
+static spt::MParams inst_render_params(const spt_ctx* c)
+{
+    spt::MParams M{};
+    M.mats = c->inst.d_mats; M.ntris = c->ntris; M.ninst = c->ninst;
+    M.strips = c->mesh_specular ? 0u : 1u;
+    return M;
+}
+
 int spt_set_mesh_accel(spt_ctx* c, int accel)
 {
     if (!c) return 1;
@@ -718,6 +928,11 @@ int spt_set_mesh_accel(spt_ctx* c, int accel)
     c->accel = accel;
     if (accel == SPT_ACCEL_EXHAUSTIVE || !c->mesh_scene || c->bvh_ready) return 0;
     try {
+        if (c->inst_scene) {
+            if (build_inst_accel(c, c->inst, "spt_set_mesh_accel")) return 1;
+            c->bvh_ready = true;
+            return 0;
+        }
         return build_accel(c);
     } catch (const std::exception& e) {
         return c->fail("spt_set_mesh_accel: %s", e.what());
@@ -787,6 +1002,16 @@ static spt::MParams mesh_params(const spt_ctx* c, int mode)
     return M;
 }
 
+// Instanced scenes: the closest-hit query (range = 0: 6 floats per ray; 1: 8) through each model's exact hierarchy unless the mode is
+// SPT_ACCEL_EXHAUSTIVE (SPT_ACCEL_BVH_FAST included: the models carry no plain-hierarchy form).
+static int inst_trace_enqueue(spt_ctx* c, int range, const float* d_rays, uint64_t n, float* d_hits, hipStream_t st)
+{
+    if (c->last_mesh_mode == SPT_ACCEL_BVH_FAST) c->last_mesh_mode = SPT_ACCEL_BVH;
+    const spt::IParams I = inst_params(c);
+    SPT_HIP(c, spt_inst_trace_rays(&I, c->last_mesh_mode != SPT_ACCEL_EXHAUSTIVE, range, d_rays, n, d_hits, st));
+    return 0;
+}
+
 int spt_trace_rays_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream)
 {
     if (!c) return 1;
@@ -796,9 +1021,10 @@ int spt_trace_rays_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hi
     if (n > 0x7FFFFFFFull * 256ull) return c->fail("spt_trace_rays_device: too many rays for one call");
     SPT_HIP(c, hipSetDevice(c->device));
     c->last_mesh_mode = mesh_mode(c, false);
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (c->inst_scene) return inst_trace_enqueue(c, 0, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits), st);
     const spt::MParams M = mesh_params(c, c->last_mesh_mode);
-    SPT_HIP(c, spt_mesh_trace_rays(&M, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits),
-                                   hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream));
+    SPT_HIP(c, spt_mesh_trace_rays(&M, static_cast<const float*>(d_rays), n, static_cast<float*>(d_hits), st));
     return 0;
 }
 
@@ -832,6 +1058,15 @@ int spt_trace_rays(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
     float* const d_rays = c->d_trace_rays;
     float* const d_hits = c->d_trace_hits;
     c->last_mesh_mode = mesh_mode(c, false);
+    if (c->inst_scene) {
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * sizeof(spt_ray), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return c->fail("spt_trace_rays: %s", hipGetErrorString(e));
+        if (inst_trace_enqueue(c, 0, d_rays, n, d_hits, c->stream)) return 1;
+        e = hipMemcpyAsync(hits, d_hits, n * sizeof(spt_hit), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return c->fail("spt_trace_rays: %s", hipGetErrorString(e));
+        return 0;
+    }
     const spt::MParams M = mesh_params(c, c->last_mesh_mode);
     // 24 B per ray up and 44 B per hit down through the caller's pageable buffers: the host link is the bound (measured 176 Mrays/s
     // for 1 Mi rays against 1.3 Grays/s of the kernel on the shipped scene's hierarchy; chunks on two streams were tried and are
@@ -1013,6 +1248,11 @@ static int occluded_rays_enqueue(spt_ctx* c, const float* d_rays, const float* d
 {
     const int mode = mesh_mode(c, false);
     c->last_mesh_mode = mode == SPT_ACCEL_BVH_FAST ? SPT_ACCEL_BVH : mode;
+    if (c->inst_scene) {
+        const spt::IParams I = inst_params(c);
+        SPT_HIP(c, spt_inst_occluded(&I, c->last_mesh_mode != SPT_ACCEL_EXHAUSTIVE, d_rays, d_tmax, n, d_occ, st));
+        return 0;
+    }
     const spt::MParams M = mesh_params(c, c->last_mesh_mode);
     SPT_HIP(c, spt_mesh_occluded(&M, d_rays, d_tmax, n, d_occ, st));
     return 0;
@@ -1102,6 +1342,7 @@ static int trace_rays_range_enqueue(spt_ctx* c, const float* d_rays, uint64_t n,
 {
     const int mode = mesh_mode(c, false);
     c->last_mesh_mode = mode == SPT_ACCEL_BVH_FAST ? SPT_ACCEL_BVH : mode;
+    if (c->inst_scene) return inst_trace_enqueue(c, 1, d_rays, n, d_hits, st);
     const spt::MParams M = mesh_params(c, c->last_mesh_mode);
     SPT_HIP(c, spt_mesh_trace_rays_range(&M, d_rays, n, d_hits, st));
     return 0;
@@ -1410,6 +1651,9 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         if (sphere_bvh) {
             M.bvh_nodes = c->d_sbvh_nodes; M.bvh_tris = c->d_sbvh_geom; M.bvh_index = c->d_sbvh_index;
             M.always = c->d_sbvh_always; M.nalways = c->sbvh_nalways; M.sphere_mode = 1u;
+        } else if (c->inst_scene) {                              // (no camera-plane list: depth-0 rays walk each model's plane tree)
+            P.n = 0; P.n_pad = 1; P.geom = nullptr; P.mat = nullptr;
+            M = inst_render_params(c);
         } else {
             P.n = 0; P.n_pad = 1; P.geom = nullptr; P.mat = nullptr;
             M = mesh_params(c, mode);
@@ -1417,13 +1661,18 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         }
         SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
         SPT_HIP(c, hipEventRecord(c->ev_start, st));
-        SPT_HIP(c, spt_mesh_launch(&P, &M, (uint32_t)blocks, st));
+        if (c->inst_scene) {
+            const spt::IParams I = inst_params(c);
+            SPT_HIP(c, spt_inst_launch(&P, &M, &I, mode != SPT_ACCEL_EXHAUSTIVE, (uint32_t)blocks, st));
+        } else {
+            SPT_HIP(c, spt_mesh_launch(&P, &M, (uint32_t)blocks, st));
+        }
         SPT_HIP(c, hipEventRecord(c->ev_mid, st));
         SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
         SPT_HIP(c, hipEventRecord(c->ev_stop, st));
         c->pending = true;
         c->last_was_pool = false;
-        c->last_kernel = sphere_bvh ? 3 : (mode == SPT_ACCEL_BVH ? 6 : (mode == SPT_ACCEL_BVH_FAST ? 7 : 2));
+        c->last_kernel = sphere_bvh ? 3 : c->inst_scene ? 8 : (mode == SPT_ACCEL_BVH ? 6 : (mode == SPT_ACCEL_BVH_FAST ? 7 : 2));
         c->last = spt_stats{};
         c->last.samples = npix * 4ull * samps;
         c->last.grid_blocks = (uint32_t)blocks;
@@ -1599,7 +1848,7 @@ int spt_sync(spt_ctx* c, spt_stats* stats)
         c->last.kernel_ms = ms;
         c->last.bounces = ctr[0];
         c->last.max_depth_kills = ctr[1];
-        if (c->mesh_scene && (c->last_kernel == 2 || c->last_kernel == 6 || c->last_kernel == 7) && c->last.samples)
+        if (c->mesh_scene && (c->last_kernel == 2 || c->last_kernel == 6 || c->last_kernel == 7 || c->last_kernel == 8) && c->last.samples)
             c->mesh_ratio = (float)((double)c->last.bounces / (double)c->last.samples);
         if (c->variant & 0x100u) SPT_HIP(c, hipMemcpy(c->diag, c->d_counters + 2, sizeof c->diag, hipMemcpyDeviceToHost));
         c->pending = false;
@@ -1693,7 +1942,8 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
     int path = 0;                                    // 0 sphere table exhaustive, 1 grid, 2 sphere hierarchy, 3 meshes
     if (c->mesh_scene) {
         path = 3;
-        M = mesh_params(c, mesh_mode(c, false));     // (every ray is a camera ray: the bounce share of renders does not apply)
+        if (c->inst_scene) M = inst_render_params(c);
+        else M = mesh_params(c, mesh_mode(c, false));     // (every ray is a camera ray: the bounce share of renders does not apply)
         if (M.plane_nodes && camera_plane_list(c, cam, st, M)) return 1;
     } else if (c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready) {
         path = 1;
@@ -1713,7 +1963,10 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
     if (path == 0) SPT_HIP(c, spt_aov_exhaustive_launch(&P, aov, c->needs_guard ? 1 : 0, st));
     else if (path == 1) SPT_HIP(c, spt_aov_grid_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, c->grid_global, aov, blocks, st));
     else if (path == 2) SPT_HIP(c, spt_aov_sphere_bvh_launch(&P, &M, aov, st));
-    else SPT_HIP(c, spt_aov_mesh_launch(&P, &M, aov, st));
+    else if (c->inst_scene) {
+        const spt::IParams I = inst_params(c);
+        SPT_HIP(c, spt_aov_inst_launch(&P, &M, &I, mesh_mode(c, false) != SPT_ACCEL_EXHAUSTIVE, aov, st));
+    } else SPT_HIP(c, spt_aov_mesh_launch(&P, &M, aov, st));
     SPT_HIP(c, hipEventRecord(c->ev_mid, st));
     SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, 1.0f / (float)(4u * samps), (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
     SPT_HIP(c, hipEventRecord(c->ev_stop, st));
@@ -1842,7 +2095,8 @@ int spt_progressive_frame_async(spt_ctx* c, spt_ctx* owner, const spt_camera* ca
         return c->fail("spt_progressive_frame_async: call spt_progressive_attach(lane, owner) first");
     if (c->frame_in_flight) return c->fail("spt_progressive_frame_async: the lane's previous frame has not been waited for");
     // a lane renders ITS context's scene into the owner's accumBuffer: the caller keeps the scenes equal; what can be told apart cheaply is
-    if (c != owner && (c->mesh_scene != owner->mesh_scene || (!c->mesh_scene && c->n != owner->n) || (c->mesh_scene && (c->ntris != owner->ntris || c->ninst != owner->ninst))))
+    if (c != owner && (c->mesh_scene != owner->mesh_scene || (!c->mesh_scene && c->n != owner->n) || (c->mesh_scene && (c->ntris != owner->ntris || c->ninst != owner->ninst)) ||
+                       c->inst_scene != owner->inst_scene || (c->inst_scene && c->inst.models.size() != owner->inst.models.size())))
         return c->fail("spt_progressive_frame_async: the lane's scene differs from the owner's (kind or size); set the owner's scene on every lane");
     // :922 the frame is the UN-NORMALISED sum of Renderer::render, on the lane's stream
     c->frames_in_flight_hint = owner->lanes_attached + 1u;           // the owner and its lanes each keep a frame in flight

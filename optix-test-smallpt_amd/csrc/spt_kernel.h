@@ -109,6 +109,12 @@ extern "C" size_t spt_mesh_lds_bytes(int bvh);
 extern "C" size_t spt_mesh_stack_floats(uint32_t blocks);
 extern "C" hipError_t spt_mesh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t blocks, hipStream_t stream);
 extern "C" hipError_t spt_mesh_trace_rays(const spt::MParams* M, const float* d_rays, uint64_t nrays, float* d_hits, hipStream_t stream);
+// Instanced mesh scenes (spt_set_instances, spt_instance.h): bvh = 1 walks each model's exact hierarchy, 0 loops over each model's triangles.
+namespace spt { struct IParams; }
+extern "C" hipError_t spt_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t blocks, hipStream_t stream);
+extern "C" hipError_t spt_inst_trace_rays(const spt::IParams* I, int bvh, int range, const float* d_rays, uint64_t nrays, float* d_hits, hipStream_t stream);
+extern "C" hipError_t spt_inst_occluded(const spt::IParams* I, int bvh, const float* d_rays, const float* d_tmax, uint64_t nrays, uint8_t* d_occ, hipStream_t stream);
+extern "C" hipError_t spt_aov_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t kind, hipStream_t stream);
 extern "C" size_t spt_k_lds_bytes(uint32_t n_pad, int mat_lds, int big_block);
 extern "C" size_t spt_k_stack_floats(uint32_t blocks, int block_threads);
 extern "C" hipError_t spt_k_launch(const spt::KParams* P, uint32_t blocks, int mat_lds, int guard, int diag, int bign, int big_block, hipStream_t stream);

@@ -25,6 +25,7 @@
 #define SPT_QUERY_DEVICE
 #include "spt_query.h"
 #include "spt_aov.h"
+#include "spt_instance.h"
 
 namespace spt {
 
@@ -502,6 +503,155 @@ __device__ __forceinline__ MeshHit make_hit(const MParams& M, uint32_t tri, floa
     return h;
 }
 
+// ---- mesh instances (spt_set_instances; spt_instance.h, include/smallpt_mi355x.h) ----------------------------------------------------
+// One descriptor per model (the MParams of a spt_set_meshes scene holding that model alone, instance field 0) and one InstRec per instance.
+// The instance loop runs i = 0 .. ninst - 1 for every lane: ninst is a kernel argument and the records and descriptors are read through
+// the constant address space with a uniform index, so they come in through scalar loads and the loop is wave- and workgroup-uniform (the
+// exhaustive per-model loop stages block-wide LDS tiles).  Per instance the lane's ray is mapped to object space (unless the instance is
+// the identity) and the model's closest report strictly inside (lo, min(hi, best)) replaces the best: strict '<' across instances gives the
+// lowest instance among equal distances, the model's own rule the lowest triangle.  Every model structure is exact for any ray
+// (spt_tribvh.h), object-space rays included, so every mode returns the exhaustive answer.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) InstRec* CInstRec;
+typedef const __attribute__((address_space(4))) MParams* CModel;
+#else
+typedef const InstRec* CInstRec;                                  // (the host pass only parses the kernels)
+typedef const MParams* CModel;
+#endif
+
+__device__ __forceinline__ IParams inst_params() { return IParams{}; }
+__device__ __forceinline__ IParams inst_params(const IParams& I) { return I; }
+
+struct InstWin { uint32_t inst, tri; f3 o, d; };                 // the winning instance, its triangle and the object-space ray it was found with
+
+__device__ __forceinline__ void inst_ray(const CInstRec r, f3 ro, f3 rd, f3& o, f3& d)
+{
+    o = ro; d = rd;
+    if (!r->identity) {
+        float w[12], t[3];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) w[k] = r->w[k];
+        inst_point(w, ro.x, ro.y, ro.z, t); o = mk(t[0], t[1], t[2]);
+        inst_dir(w, rd.x, rd.y, rd.z, t); d = mk(t[0], t[1], t[2]);
+    }
+}
+
+// Closest report over every (instance, triangle) with key(t) = bits(t) - rk.bias < rk.bound; returns its t (the bound's t on a miss, win.tri =
+// 0xFFFFFFFF).  BVH = each model's exact hierarchy, else each model's exhaustive loop (all threads of the workgroup call this together).
+template <bool BVH>
+__device__ __forceinline__ float closest_instanced(const IParams& I, float4* s_tile, bool active, f3 ro, f3 rd, RangeKeys rk, InstWin& win)
+{
+    uint32_t near_key = rk.bound;
+    win.inst = 0xFFFFFFFFu; win.tri = 0xFFFFFFFFu; win.o = ro; win.d = rd;
+    const CInstRec ci = (CInstRec)I.inst;
+    const CModel cm = (CModel)I.models;
+    for (uint32_t i = 0; i < I.ninst; ++i) {
+        const CInstRec r = ci + i;
+        const MParams M = cm[r->model];
+        if (M.ntris == 0u) continue;                                     // (uniform: an empty model reports nothing)
+        f3 o, d;
+        inst_ray(r, ro, rd, o, d);
+        float t;
+        const RangeKeys k{rk.bias, near_key};
+        const uint32_t tri = BVH ? closest_triangle_bvh_range(M, reinterpret_cast<uint32_t*>(s_tile), active && near_key != 0u, o, d, k, t)
+                                 : closest_triangle_range(M.tris, M.ntris, s_tile, active, o, d, k, t);
+        if (tri != 0xFFFFFFFFu) { near_key = __float_as_uint(t) - rk.bias; win.inst = i; win.tri = tri; win.o = o; win.d = d; }
+    }
+    return range_key_t(near_key, rk.bias);
+}
+
+// Any report below bkey over every (instance, triangle): the lane stops at the first instance that reports.  BVH = each model's exact
+// hierarchy (a wave leaves the loop once all of its lanes are settled), else each model's exhaustive loop (the workgroup leaves it together).
+template <bool BVH>
+__device__ __forceinline__ bool any_instanced(const IParams& I, float4* s_tile, f3 ro, f3 rd, uint32_t bkey)
+{
+    bool occ = false;
+    const CInstRec ci = (CInstRec)I.inst;
+    const CModel cm = (CModel)I.models;
+    for (uint32_t i = 0; i < I.ninst; ++i) {
+        const bool open = !occ && bkey != 0u;
+        if (BVH) { if (__ballot(open) == 0ull) break; }
+        else if (__syncthreads_or(open ? 1 : 0) == 0) break;
+        const CInstRec r = ci + i;
+        const MParams M = cm[r->model];
+        if (M.ntris == 0u) continue;
+        f3 o, d;
+        inst_ray(r, ro, rd, o, d);
+        const bool hit = BVH ? any_triangle_bvh(M, reinterpret_cast<uint32_t*>(s_tile), open, o, d, bkey)
+                             : any_triangle(M.tris, M.ntris, s_tile, o, d, open ? bkey : 0u);
+        occ = occ || hit;
+    }
+    return occ;
+}
+
+// makeHit of the winner in its model's space, then x mapped by A and n by W^T (spt_instance.h); instId = the instance.
+__device__ __forceinline__ MeshHit make_inst_hit(const IParams& I, const InstWin& win, float t)
+{
+    const InstRec* r = I.inst + win.inst;
+    MeshHit h = make_hit(I.models[r->model], win.tri, t, win.o, win.d);
+    if (!r->identity) {
+        float a[12], w[12], x[3], n[3];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { a[k] = r->a[k]; w[k] = r->w[k]; }
+        inst_point(a, h.x.x, h.x.y, h.x.z, x);
+        inst_normal(w, h.n.x, h.n.y, h.n.z, n);
+        h.x = mk(x[0], x[1], x[2]); h.n = mk(n[0], n[1], n[2]);
+    }
+    h.inst = win.inst;
+    return h;
+}
+
+// Queries of an instanced scene: spt_trace_rays (RANGE = false: 6 floats per ray, the keys of (0, 1e20)) and spt_trace_rays_range (8 floats).
+template <bool BVH, bool RANGE>
+__global__ __launch_bounds__(kMeshBlock) void trace_rays_inst(const IParams I, const float* __restrict__ rays, uint64_t nrays, float* __restrict__ hits)
+{
+    extern __shared__ float4 s_tile[];
+    const uint64_t i = (uint64_t)blockIdx.x * kMeshBlock + threadIdx.x;
+    const bool active = i < nrays;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    RangeKeys rk{1u, RANGE ? 0u : kMeshInfKey};
+    if (active) {
+        if (RANGE) {
+            const float4* q = reinterpret_cast<const float4*>(rays) + 2 * i;
+            const float4 a = q[0], b = q[1];
+            ro = mk(a.x, a.y, a.z); rd = mk(b.x, b.y, b.z);
+            rk = range_triangle_keys(a.w, b.w);
+        } else {
+            ro = mk(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]); rd = mk(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+        }
+    }
+    InstWin win;
+    const float t = closest_instanced<BVH>(I, s_tile, active && rk.bound != 0u, ro, rd, rk, win);
+    if (!active) return;
+    float* h = hits + 11 * i;
+    if (win.tri == 0xFFFFFFFFu) {                                                // Hit{}: dist = 1e20, the rest 0
+        h[0] = 1e20f;
+        for (int k = 1; k < 11; ++k) h[k] = 0.f;
+        return;
+    }
+    const MeshHit m = make_inst_hit(I, win, t);
+    h[0] = m.dist; h[1] = __uint_as_float(m.inst); h[2] = __uint_as_float(m.tri);
+    h[3] = m.x.x; h[4] = m.x.y; h[5] = m.x.z; h[6] = m.n.x; h[7] = m.n.y; h[8] = m.n.z; h[9] = m.u; h[10] = m.v;
+}
+
+// Occlusion queries of an instanced scene (spt_occluded_rays): one byte per ray.
+template <bool BVH>
+__global__ __launch_bounds__(kMeshBlock) void occluded_rays_inst(const IParams I, const float* __restrict__ rays, const float* __restrict__ tmax, uint64_t nrays,
+                                                                 uint8_t* __restrict__ occ_out)
+{
+    extern __shared__ float4 s_tile[];
+    const uint64_t i = (uint64_t)blockIdx.x * kMeshBlock + threadIdx.x;
+    const bool active = i < nrays;
+    f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1);
+    uint32_t bkey = 0u;
+    if (active) {
+        ro = mk(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]); rd = mk(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+        bkey = occ_triangle_key(tmax ? tmax[i] : __builtin_inff());
+    }
+    const bool occ = any_instanced<BVH>(I, s_tile, ro, rd, bkey);
+    if (active) occ_out[i] = occ ? 1u : 0u;
+}
+
 // Intersector::traceRays (smallpt.cpp:460-470 / :553-587): one Hit (scene.h:31-43, 44 bytes) per ray.
 template <bool BVH>
 __global__ __launch_bounds__(kMeshBlock) void trace_rays(const MParams M, const float* __restrict__ rays, uint64_t nrays, float* __restrict__ hits)
@@ -661,11 +811,14 @@ __global__ __launch_bounds__(kMeshBlock) void trace_rays_range(const MParams M, 
 struct MPath { f3 o, d, w; uint32_t depth, branch, rbase; };
 
 // GEOM 0: triangles, exhaustive; 1: triangles through the hierarchy; 2: a sphere table through its hierarchy (staging a small
-// tree into LDS behind the stacks was measured: 30 % slower -- two workgroups per CU and conflicting per-lane ds_read_b128)
-template <int GEOM>
-__global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const MParams M)
+// tree into LDS behind the stacks was measured: 30 % slower -- two workgroups per CU and conflicting per-lane ds_read_b128);
+// 3 / 4: an instanced scene (I) through each model's exhaustive loop / exact hierarchy, M holding the per-instance materials
+// (The instance parameters come in as an optional trailing argument: GEOM 0-2 keep the signature and code they had before instances.)
+template <int GEOM, typename... IP>
+__global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const MParams M, const IP... ip)
 {
     extern __shared__ float4 s_tile[];
+    const IParams I = inst_params(ip...);
     const uint32_t lane = lane_id_m();
     const uint32_t gthread = blockIdx.x * kMeshBlock + threadIdx.x;
     float* const gstack = K.stack + (size_t)gthread * (3 * 12);                  // 3 pending children x 12 words per thread
@@ -690,7 +843,7 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
         if (!alive && s_gen == s_end && !queue_empty) {
             if (task_valid) K.cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f);
             uint32_t qpos = atomicAdd(K.queue, 1u);           // the triangle loop dwarfs this atomic
-            if (GEOM == 1 && M.strips) {
+            if ((GEOM == 1 || GEOM == 4) && M.strips) {
                 // through the triangle hierarchy the lanes of a wave hold an 8 x 8 TILE of pixels (spt_deal.h deal_task_tiles; scenes without
                 // mirror / glass materials, MParams::strips); a tile's part beyond the image is a hole inside the range: fetch again
                 const uint32_t S = 4u << K.nb_log2, rows = K.ntasks / (S * K.w), qend = deal_tiles_end(K.w, rows, S);
@@ -764,7 +917,7 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
         // exhaustive: the workgroup stages the triangle tiles together, so it leaves together; the traversals need no barrier and
         // a wave must not wait for the slowest ray of its three neighbours every bounce
         uint32_t nalive = 0;                                     // exhaustive mode: paths alive in the whole workgroup
-        if (GEOM == 0) { nalive = (uint32_t)__syncthreads_count(alive ? 1 : 0); if (nalive == 0u) break; }
+        if (GEOM == 0 || GEOM == 3) { nalive = (uint32_t)__syncthreads_count(alive ? 1 : 0); if (nalive == 0u) break; }
         else if (__ballot(alive) == 0ull) break;
 
         // ---- sphere table, a wave with only a few rays left (the end of a launch; a roulette-immune path -- colour (1,1,1) mirror or glass --
@@ -839,7 +992,9 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
             }
         }
         // ---- closest hit over all triangles (whole workgroup; idle lanes only help staging) ----
-        const uint32_t tri = GEOM == 2 ? (coop ? coop_tri : closest_sphere_bvh(K, M, M.bvh_nodes, M.bvh_tris, M.bvh_index, reinterpret_cast<uint32_t*>(s_tile), alive, p.o, p.d, t))
+        InstWin win;
+        if constexpr (GEOM >= 3) t = closest_instanced<GEOM == 4>(I, s_tile, alive, p.o, p.d, RangeKeys{1u, kMeshInfKey}, win);
+        const uint32_t tri = GEOM >= 3 ? win.tri : GEOM == 2 ? (coop ? coop_tri : closest_sphere_bvh(K, M, M.bvh_nodes, M.bvh_tris, M.bvh_index, reinterpret_cast<uint32_t*>(s_tile), alive, p.o, p.d, t))
                            : GEOM == 1 ? (coop ? coop_tri : closest_triangle_bvh<kMeshArgOffset>(M, reinterpret_cast<uint32_t*>(s_tile), alive, M.cam_cull != 0u && p.depth == 0u, p.o, p.d, t))
                            : nalive <= (uint32_t)kFewRays ? closest_triangle_few(M.tris, M.ntris, s_tile, nalive, alive, p.o, p.d, t)
                                        : closest_triangle(M.tris, M.ntris, s_tile, alive, p.o, p.d, t);
@@ -849,7 +1004,7 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
                 alive = false;                                                   // smallpt.cpp:168 miss (D13)
             } else {
                 // ---- shadePaths, smallpt.cpp:170-263 under D2-D6, D18, D19 ----
-                const MeshHit h = GEOM == 2 ? make_sphere_hit(K, tri, t, p.o, p.d) : make_hit(M, tri, t, p.o, p.d);
+                const MeshHit h = GEOM == 2 ? make_sphere_hit(K, tri, t, p.o, p.d) : GEOM >= 3 ? make_inst_hit(I, win, t) : make_hit(M, tri, t, p.o, p.d);
                 const float4* const mats = GEOM == 2 ? K.mat : M.mats;
                 const float4 me = mats[3 * h.inst + 0], mc = mats[3 * h.inst + 1];
                 const int refl = __float_as_int(me.w) & 3;
@@ -938,11 +1093,13 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
 // reasons of MParams::strips do not apply); per sample: the camera ray, its closest hit, acc += the selected value; then cells[task].
 // GEOM 0: triangles, exhaustive (the workgroup stages the tiles together: the sample loop runs to the workgroup's longest block);
 // 1: triangles through the hierarchy, every ray a depth-0 ray (the launch's camera-plane list replaces the plane tree); 2: a sphere table
-// through its hierarchy, rays that query_ray_route keeps out of the tree run the exhaustive loop in their lane over the global table.
-template <int GEOM>
-__global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MParams M, uint32_t kind)
+// through its hierarchy, rays that query_ray_route keeps out of the tree run the exhaustive loop in their lane over the global table;
+// 3 / 4: an instanced scene (I) through each model's exhaustive loop / exact hierarchy.
+template <int GEOM, typename... IP>
+__global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MParams M, uint32_t kind, const IP... ip)
 {
     extern __shared__ float4 s_tile[];
+    const IParams I = inst_params(ip...);
     const uint32_t S = 4u << K.nb_log2, qend = deal_tiles_end(K.w, K.row_count, S);
     const uint32_t q = blockIdx.x * kMeshBlock + threadIdx.x;
     uint32_t task = q < qend ? deal_task_tiles(q, K.w, K.row_count, S) : 0xFFFFFFFFu;
@@ -952,7 +1109,7 @@ __global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MP
     f3 acc = mk(0, 0, 0);
     for (uint32_t s = a.s_begin;; ++s) {
         const bool active = valid && s < a.s_end;
-        if (GEOM == 0) { if (__syncthreads_count(active ? 1 : 0) == 0) break; }   // workgroup-uniform: closest_triangle stages tiles
+        if (GEOM == 0 || GEOM == 3) { if (__syncthreads_count(active ? 1 : 0) == 0) break; }   // workgroup-uniform: closest_triangle stages tiles
         else if (__ballot(active) == 0ull) break;
         f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
         if (active) aov_camera_ray(K, a, s, o, d);
@@ -975,6 +1132,14 @@ __global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MP
                 const QueryHit h = query_hit(true, i, t, K.geom[i], o, d);
                 const float4 colour = kind == kAovAlbedo ? K.mat[3 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
                 acc = aov_add(acc, kind, mk(h.f[6], h.f[7], h.f[8]), colour, 0.0f, 0.0f, t);
+            }
+        } else if constexpr (GEOM >= 3) {
+            InstWin win;
+            t = closest_instanced<GEOM == 4>(I, s_tile, active, o, d, RangeKeys{1u, kMeshInfKey}, win);
+            if (active && win.tri != 0xFFFFFFFFu) {
+                const MeshHit h = make_inst_hit(I, win, t);
+                const float4 colour = kind == kAovAlbedo ? M.mats[3 * (size_t)h.inst + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = aov_add(acc, kind, h.n, colour, h.u, h.v, h.dist);
             }
         } else {
             const uint32_t tri = GEOM == 1 ? closest_triangle_bvh<kMeshArgOffset>(M, reinterpret_cast<uint32_t*>(s_tile), active, M.cam_cull != 0u, o, d, t)
@@ -1075,5 +1240,43 @@ extern "C" hipError_t spt_mesh_trace_rays_range(const spt::MParams* M, const flo
     const uint64_t blocks = (nrays + spt::kMeshBlock - 1) / spt::kMeshBlock;
     if (M->bvh_nodes) hipLaunchKernelGGL(spt::trace_rays_range<true>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *M, d_rays, nrays, d_hits);
     else hipLaunchKernelGGL(spt::trace_rays_range<false>, dim3((unsigned)blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *M, d_rays, nrays, d_hits);
+    return hipGetLastError();
+}
+
+// ---- instanced scenes (spt_set_instances): M = the per-instance materials (+ strips), I = the instance records and model descriptors;
+// bvh = 1: each model's exact hierarchy, 0: each model's exhaustive loop.
+extern "C" hipError_t spt_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t blocks, hipStream_t stream)
+{
+    if (bvh) hipLaunchKernelGGL((spt::meshkernel<4, spt::IParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, *I);
+    else hipLaunchKernelGGL((spt::meshkernel<3, spt::IParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, *I);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t spt_inst_trace_rays(const spt::IParams* I, int bvh, int range, const float* d_rays, uint64_t nrays, float* d_hits, hipStream_t stream)
+{
+    const unsigned blocks = (unsigned)((nrays + spt::kMeshBlock - 1) / spt::kMeshBlock);
+    const size_t lds = spt_mesh_lds_bytes(bvh);
+    if (range) {
+        if (bvh) hipLaunchKernelGGL((spt::trace_rays_inst<true, true>), dim3(blocks), dim3(spt::kMeshBlock), lds, stream, *I, d_rays, nrays, d_hits);
+        else hipLaunchKernelGGL((spt::trace_rays_inst<false, true>), dim3(blocks), dim3(spt::kMeshBlock), lds, stream, *I, d_rays, nrays, d_hits);
+    } else {
+        if (bvh) hipLaunchKernelGGL((spt::trace_rays_inst<true, false>), dim3(blocks), dim3(spt::kMeshBlock), lds, stream, *I, d_rays, nrays, d_hits);
+        else hipLaunchKernelGGL((spt::trace_rays_inst<false, false>), dim3(blocks), dim3(spt::kMeshBlock), lds, stream, *I, d_rays, nrays, d_hits);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t spt_inst_occluded(const spt::IParams* I, int bvh, const float* d_rays, const float* d_tmax, uint64_t nrays, uint8_t* d_occ, hipStream_t stream)
+{
+    const unsigned blocks = (unsigned)((nrays + spt::kMeshBlock - 1) / spt::kMeshBlock);
+    if (bvh) hipLaunchKernelGGL(spt::occluded_rays_inst<true>, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *I, d_rays, d_tmax, nrays, d_occ);
+    else hipLaunchKernelGGL(spt::occluded_rays_inst<false>, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *I, d_rays, d_tmax, nrays, d_occ);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t spt_aov_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t kind, hipStream_t stream)
+{
+    if (bvh) hipLaunchKernelGGL((spt::aov_mesh<4, spt::IParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind, *I);
+    else hipLaunchKernelGGL((spt::aov_mesh<3, spt::IParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, kind, *I);
     return hipGetLastError();
 }

@@ -95,6 +95,26 @@ public:
         }
         check(spt_set_meshes(ctx_, ms.data(), (uint32_t)ms.size(), mats.data()));
     }
+    // rtpModelSetInstances(models, transforms) of OptixIntersector::build (smallpt.cpp:489-530): models[m] once, instances[i] = {FLOAT4x3
+    // transform, model index}, materials[i] <-> instance i; contract in include/smallpt_mi355x.h (spt_set_instances)
+    void setInstances(const std::vector<TriMesh>& models, const std::vector<spt_instance>& instances, const std::vector<Material>& materials)
+    {
+        if (instances.size() != materials.size()) throw std::runtime_error("setInstances: one material per instance");
+        std::vector<spt_mesh> ms(models.size());
+        std::vector<spt_material> mats(materials.size());
+        for (size_t i = 0; i < models.size(); ++i) {
+            ms[i].positions = reinterpret_cast<const float*>(models[i].positionBuffer.data());
+            ms[i].normals = reinterpret_cast<const float*>(models[i].normalBuffer.data());
+            ms[i].indices = models[i].indexBuffer.data();
+            ms[i].nverts = (uint32_t)models[i].positionBuffer.size();
+            ms[i].ntris = (uint32_t)models[i].triangleCount();
+        }
+        for (size_t i = 0; i < materials.size(); ++i) {
+            const Material& m = materials[i];
+            mats[i] = spt_material{{m.emission.x, m.emission.y, m.emission.z}, {m.color.x, m.color.y, m.color.z}, (int32_t)m.refl, 0u};
+        }
+        check(spt_set_instances(ctx_, ms.data(), (uint32_t)ms.size(), instances.data(), (uint32_t)instances.size(), mats.data()));
+    }
     // the OptixIntersector's acceleration structure (rtpModelUpdate, smallpt.cpp:520-530: SPT_ACCEL_BVH, the default since round 4 -- the same
     // Hit as the loop for every ray) or the CPUIntersector's loop over every triangle (SPT_ACCEL_EXHAUSTIVE); contract in include/smallpt_mi355x.h
     void setMeshAccel(int accel) { check(spt_set_mesh_accel(ctx_, accel)); }

@@ -9,8 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SptCamera, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
-from .scene import HIT_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
+from ._lib import SptCamera, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
+from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
 FLAG_ONE_SHOT = 2          # scheduling only: no dispatch order used or recorded for this launch (include/smallpt_mi355x.h)
@@ -138,6 +138,26 @@ class SptError(RuntimeError):
     pass
 
 
+def instance_records(instances):
+    """INSTANCE_DTYPE[n] from a sequence of (model, 3x4 matrix), an INSTANCE_DTYPE array or ((n, 12) float32, (n,) ints)."""
+    if isinstance(instances, np.ndarray) and instances.dtype == INSTANCE_DTYPE:
+        return np.ascontiguousarray(instances)
+    if isinstance(instances, tuple) and len(instances) == 2 and np.asarray(instances[0]).ndim == 2:
+        mats, models = np.asarray(instances[0], dtype=np.float32).reshape(-1, 12), np.asarray(instances[1]).reshape(-1)
+    else:
+        pairs = list(instances)
+        mats = np.array([np.asarray(a, dtype=np.float32).reshape(12) for _, a in pairs], dtype=np.float32).reshape(-1, 12)
+        models = np.array([int(m) for m, _ in pairs], dtype=np.int64)
+    if len(mats) != len(models):
+        raise ValueError("instances: one model index per matrix")
+    if np.any(models < 0) or np.any(models > 0xFFFFFFFF):
+        raise ValueError("instances: model index out of range")
+    out = np.zeros(len(mats), dtype=INSTANCE_DTYPE)
+    out["transform"] = mats
+    out["model"] = models.astype(np.uint32)
+    return out
+
+
 def smallpt_camera(w, h):
     """Camera constants of cpuRender (smallpt.cpp:277-279) for a w x h image."""
     lib = load_library()
@@ -230,6 +250,8 @@ class Renderer:
         if st["scene"] is not None:
             if st["scene"][0] == "spheres":
                 other.set_scene(st["scene"][1])
+            elif st["scene"][0] == "instances":
+                other.set_instances(st["scene"][1], st["scene"][2], st["scene"][3])
             else:
                 other.set_meshes(st["scene"][1], st["scene"][2])
 
@@ -250,6 +272,28 @@ class Renderer:
         self._check(self._lib.spt_set_meshes(self._h, ms, len(meshes), mats))
         self._scene = None                                   # the sphere table is no longer the current scene
         self._state["scene"] = ("meshes", list(meshes), list(materials))
+        self._state_version += 1
+
+    def set_instances(self, models, instances, materials):
+        """rtpModelSetInstances (smallpt.cpp:489-530): models = TriMesh list, instances = a sequence of (model, 3x4 matrix), an
+        INSTANCE_DTYPE array, or a pair ((n, 12) float32 matrices, (n,) model indices); materials[i] = (emission, color, refl) of instance i.
+        Makes the instanced mesh scene current (include/smallpt_mi355x.h spt_set_instances)."""
+        recs = instance_records(instances)
+        ms = (SptMesh * max(1, len(models)))()
+        for i, m in enumerate(models):
+            ms[i].positions, ms[i].normals, ms[i].indices = m.positions.ctypes.data, m.normals.ctypes.data, m.indices.ctypes.data
+            ms[i].nverts, ms[i].ntris = len(m.positions), len(m.indices)
+        mats = (SptMaterial * max(1, len(materials)))()
+        for i, (e, col, refl) in enumerate(materials):
+            mats[i].emission = (C.c_float * 3)(*[float(v) for v in e])
+            mats[i].color = (C.c_float * 3)(*[float(v) for v in col])
+            mats[i].refl = int(refl)
+        if len(materials) < len(recs):
+            raise ValueError("set_instances: one material per instance")
+        self._check(self._lib.spt_set_instances(self._h, ms, len(models), recs.ctypes.data_as(C.POINTER(SptInstance)), len(recs), mats))
+        self._mesh_keepalive = list(models)
+        self._scene = None
+        self._state["scene"] = ("instances", list(models), recs.copy(), list(materials))
         self._state_version += 1
 
     def set_sphere_accel(self, accel):
@@ -446,8 +490,9 @@ class Renderer:
     def last_kernel(self):
         """'pool' (spt_pool.hip, material-sorted), 'mega' (spt_kernel.hip), 'mesh' (spt_mesh.hip, triangles), 'sbvh' (spt_mesh.hip over a
         sphere hierarchy), 'gpool' (spt_gpool.hip, uniform grid over a large sphere table driven by wave-private path pools: the default above 24
-        spheres) or 'grid' (spt_grid.hip, the same grid with lanes that own their path: tables that leave no LDS for the pools) for the last launch."""
-        return {0: "mega", 1: "pool", 2: "mesh", 3: "sbvh", 4: "grid", 5: "gpool", 6: "mesh_bvh", 7: "mesh_bvh_fast"}[self._lib.spt_last_kernel(self._h)]
+        spheres), 'grid' (spt_grid.hip, the same grid with lanes that own their path: tables that leave no LDS for the pools) or 'mesh_inst' (spt_mesh.hip
+        over an instanced scene, spt_set_instances) for the last launch."""
+        return {0: "mega", 1: "pool", 2: "mesh", 3: "sbvh", 4: "grid", 5: "gpool", 6: "mesh_bvh", 7: "mesh_bvh_fast", 8: "mesh_inst"}[self._lib.spt_last_kernel(self._h)]
 
     def render_interleaved_device(self, out_tensor, w, h, block_rows, world, rank, samps_per_cell, seed=0,
                                   normalise=False, camera=None, stream=None):

@@ -105,6 +105,7 @@ def spheres_from_json(text):
 
 # ---- triangle meshes (scene.h:6-15 TriMesh, scene.cpp:3-48 makeSphereTriMesh) ----
 HIT_DTYPE = np.dtype([("dist", "<f4"), ("instId", "<u4"), ("triId", "<u4"), ("x", "<f4", 3), ("n", "<f4", 3), ("uv", "<f4", 2)])   # Hit, scene.h:31-43
+INSTANCE_DTYPE = np.dtype([("transform", "<f4", 12), ("model", "<u4"), ("pad", "<u4")])                                          # spt_instance: FLOAT4x3 + model
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3)])                                                                           # Ray, scene.h:58-62
 assert HIT_DTYPE.itemsize == 44 and RAY_DTYPE.itemsize == 24
 RAY_RANGE_DTYPE = np.dtype([("o", "<f4", 3), ("tmin", "<f4"), ("d", "<f4", 3), ("tmax", "<f4")])                                   # OptixRay, smallpt.cpp:395-403
