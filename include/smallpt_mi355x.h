@@ -30,6 +30,8 @@
  *     559-569,579): closest hit inside a per-ray interval        spt_trace_rays_range_device() (device buffers, async)
  *   rtpModelSetInstances with RTP_BUFFER_FORMAT_TRANSFORM_       spt_set_instances(), spt_instance_inverse()
  *     FLOAT4x3 + INSTANCE_MODEL (smallpt.cpp:489-530)
+ *   the miss of shadePaths, `if (!hit) continue; // Here we      spt_set_environment()
+ *     could accumulate path.weight * envContrib` (smallpt.cpp:168)
  *   accumBuffer += outImage under accumBufferMutex and the      spt_progressive_begin / _frame / _snapshot / _end
  *     GL thread's copy of it (smallpt.cpp:881-883,924-940,       (accumulation buffer resident in HBM)
  *     955-959)
@@ -318,6 +320,26 @@ int  spt_camera_smallpt(uint32_t w, uint32_t h, spt_camera* out);
  * :885-899).  Selects SPT_SAMPLER_PINHOLE. */
 int  spt_camera_pinhole(const float vx[3], const float vy[3], const float vz[3], const float org[3],
                         float near_plane_distance, spt_camera* out);
+
+/* Radiance E gathered by a path that leaves the scene (smallpt.cpp:168, "path.weight * envContrib").  radiance = NULL or (0,0,0): black
+ * on a miss (D13, the default and the behaviour of every existing call).  Each component finite and >= 0, else the call fails and the
+ * previous value stays.
+ *   Where E is added: a render path of weight w whose closest-hit query finds nothing adds w * E to its block sum, per component, with
+ *   one float32 multiply and one add, at the place in the D9 order where a hit would add w * emission (the miss is the last event of the
+ *   path; no bounce follows it).  Camera rays (w = 1), bounce rays and both children of a glass split alike.  bounces and
+ *   max_depth_kills count what they count without E.
+ *   Enclosure anchor: for a scene whose geometry and every ray origin of the render lie strictly inside a sphere C, rendering with E gives
+ *   the image and statistics, bit for bit, of rendering with E = 0 after appending C as one more DIFF sphere of emission E and colour
+ *   (0,0,0) (a hit on C adds w * E; colour 0 ends the path through the roulette (pmax = 0) beyond depth 5 and through the zero-weight
+ *   cut (D19) before it, neither a depth-cap kill; C is last in the table, so it never wins a tie).
+ *   Scope: E belongs to the context and persists across spt_set_scene / spt_set_meshes / spt_set_instances and accel mode changes.  It
+ *   applies to spt_render, spt_render_rows_device, spt_render_interleaved_device and spt_progressive_frame(_async), for every scene kind
+ *   and accel mode; NOT to the first-hit feature buffers (spt_render_aov*: a miss still adds nothing) nor to the queries (spt_trace_*,
+ *   spt_occluded_*).  spt_progressive_attach / spt_progressive_frame_async refuse a lane whose E differs from its owner's.
+ *   E = 0 runs the kernels without the term (the same code as before this entry point existed). */
+int  spt_set_environment(spt_ctx* ctx, const float radiance[3]);
+/* The context's current E (0 = ok). */
+int  spt_get_environment(const spt_ctx* ctx, float radiance[3]);
 
 /* Renders the full w x h image and copies it to out_rgb (host, w*h*3 floats).  Blocking. */
 int  spt_render(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h,

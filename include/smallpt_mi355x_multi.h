@@ -65,6 +65,8 @@ int  spt_multi_set_scene(spt_multi* m, const spt_sphere* spheres, uint32_t n);
 int  spt_multi_set_meshes(spt_multi* m, const spt_mesh* meshes, uint32_t nmesh, const spt_material* materials);
 int  spt_multi_set_mesh_accel(spt_multi* m, int accel);
 int  spt_multi_set_sphere_accel(spt_multi* m, int accel);
+/* spt_set_environment on every device (each rank renders its band with the same E; the same validation). */
+int  spt_multi_set_environment(spt_multi* m, const float radiance[3]);
 
 /* Row band of rank `rank` of `world` for an image of height h: rows split as evenly as possible, the first h % world
  * ranks get one more row; bands are in rank order = row order. */

@@ -52,6 +52,8 @@ SYMBOLS = {
     "spt_set_meshes": (C.c_int, [_P, C.POINTER(SptMesh), C.c_uint32, C.POINTER(SptMaterial)]),
     "spt_set_mesh_accel": (C.c_int, [_P, C.c_int]),
     "spt_set_sphere_accel": (C.c_int, [_P, C.c_int]),
+    "spt_set_environment": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "spt_get_environment": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "spt_trace_rays": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "spt_trace_rays_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "spt_trace_spheres": (C.c_int, [_P, _P, C.c_uint64, _P]),
@@ -127,6 +129,7 @@ MULTI_SYMBOLS = {
     "spt_multi_set_meshes": (C.c_int, [_P, C.POINTER(SptMesh), C.c_uint32, C.POINTER(SptMaterial)]),
     "spt_multi_set_mesh_accel": (C.c_int, [_P, C.c_int]),
     "spt_multi_set_sphere_accel": (C.c_int, [_P, C.c_int]),
+    "spt_multi_set_environment": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "spt_multi_row_band": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "spt_multi_render": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                    C.c_uint32, _P, C.POINTER(SptMultiStats)]),

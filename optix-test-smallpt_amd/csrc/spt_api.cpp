@@ -86,6 +86,7 @@ struct spt_ctx {
     std::vector<float4> h_geom;      // host copy of the sphere table {centre, r*r} and the radii: its hierarchy is built on demand
     std::vector<float> h_radius;
     int sphere_accel = SPT_ACCEL_GRID;
+    float env[3] = {0.f, 0.f, 0.f};  // spt_set_environment: radiance of escaped paths; (0,0,0) = black, the kernels without the term
     // uniform grid over the sphere table (spt_grid.h): built in spt_set_scene for tables above the pool kernel's limit
     bool grid_ready = false;         // the tables below belong to the current sphere scene and the scene qualifies
     int grid_global = 0;             // ... 1: every table stays in global memory, 2: the sphere records do, the grid is staged in LDS (spt_grid.hip WHERE)
@@ -506,6 +507,26 @@ int spt_set_sphere_accel(spt_ctx* c, int accel)
         return c->fail("spt_set_sphere_accel: %s", e.what());
     }
 }
+
+int spt_set_environment(spt_ctx* c, const float radiance[3])
+{
+    if (!c) return 1;
+    const float e[3] = {radiance ? radiance[0] : 0.f, radiance ? radiance[1] : 0.f, radiance ? radiance[2] : 0.f};
+    for (int k = 0; k < 3; ++k)
+        if (!(e[k] >= 0.f && e[k] < INFINITY)) return c->fail("spt_set_environment: component %d is %g; each must be finite and >= 0", k, (double)e[k]);
+    for (int k = 0; k < 3; ++k) c->env[k] = e[k] == 0.f ? 0.f : e[k];   // (-0 is black)
+    return 0;
+}
+
+int spt_get_environment(const spt_ctx* c, float radiance[3])
+{
+    if (!c || !radiance) return 1;
+    for (int k = 0; k < 3; ++k) radiance[k] = c->env[k];
+    return 0;
+}
+
+static bool env_on(const spt_ctx* c) { return c->env[0] != 0.f || c->env[1] != 0.f || c->env[2] != 0.f; }
+static bool env_differs(const spt_ctx* a, const spt_ctx* b) { return std::memcmp(a->env, b->env, sizeof a->env) != 0; }
 
 // Host-only self-test of the grid builder (no device call).  out8 = {dim x, dim y, dim z, references, always-tested spheres, table bytes, usable, most references in one cell}.
 int spt_selftest_sphere_grid(const spt_sphere* s, uint32_t n, uint32_t cells_per_sphere, uint32_t* out8, char* why, uint32_t why_len)
@@ -1548,6 +1569,9 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
                                     std::fmax(std::fabs(cam->origin[2]), std::fabs(cam->push)));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     const float scale = 1.0f / (float)(4u * samps);   // smallpt.cpp:360 operator/=(float3, float)
+    // environment radiance (spt_set_environment): the kernels' environment variants, product builds only; E = 0 runs the kernels without the term
+    const float* const radiance = env_on(c) ? c->env : nullptr;
+    if (radiance && (c->variant & 0x100u)) return c->fail("spt_render_rows_device: the instrumented kernels (tuning bit 8) have no environment variant; set the environment to 0");
 
     // ---- large sphere table through its uniform grid (spt_grid.hip): the default above the pool kernel's limit ----
     if (!c->mesh_scene && c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready && cam_big <= 1e15f && !(c->variant & 0x400u)) {
@@ -1592,7 +1616,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
                 Q.S = S; Q.R = R; Q.drain = drain; Q.min_batch = minb; Q.walk_iters = witers ? witers : 1u;
                 SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
                 SPT_HIP(c, hipEventRecord(c->ev_start, st));
-                SPT_HIP(c, spt_gpool_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, &Q, blocks, threads, (c->variant & 0x100u) ? 1 : 0, st));
+                SPT_HIP(c, spt_gpool_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, &Q, blocks, threads, (c->variant & 0x100u) ? 1 : 0, st, radiance));
                 SPT_HIP(c, hipEventRecord(c->ev_mid, st));
                 SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
                 SPT_HIP(c, hipEventRecord(c->ev_stop, st));
@@ -1609,7 +1633,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
         SPT_HIP(c, hipEventRecord(c->ev_start, st));
         SPT_HIP(c, spt_grid_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, blocks, threads, lsel ? lsel - 1u : 16u, (c->variant & 0x100u) ? 1 : 0,
-                                   c->grid_global, st));
+                                   c->grid_global, st, radiance));
         SPT_HIP(c, hipEventRecord(c->ev_mid, st));
         SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
         SPT_HIP(c, hipEventRecord(c->ev_stop, st));
@@ -1663,9 +1687,9 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         SPT_HIP(c, hipEventRecord(c->ev_start, st));
         if (c->inst_scene) {
             const spt::IParams I = inst_params(c);
-            SPT_HIP(c, spt_inst_launch(&P, &M, &I, mode != SPT_ACCEL_EXHAUSTIVE, (uint32_t)blocks, st));
+            SPT_HIP(c, spt_inst_launch(&P, &M, &I, mode != SPT_ACCEL_EXHAUSTIVE, (uint32_t)blocks, st, radiance));
         } else {
-            SPT_HIP(c, spt_mesh_launch(&P, &M, (uint32_t)blocks, st));
+            SPT_HIP(c, spt_mesh_launch(&P, &M, (uint32_t)blocks, st, radiance));
         }
         SPT_HIP(c, hipEventRecord(c->ev_mid, st));
         SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
@@ -1684,7 +1708,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
     if (c->pool_ok && cam_big <= 1e15f && !(c->variant & 0x500u)) {
         const uint32_t psel = (c->variant >> 11) & 3u;
         const int pool = psel == 1 ? 96 : (psel == 2 ? 192 : (psel == 3 ? 128 : spt_pool_default_slots()));   // default: four workgroups per CU
-        const size_t lds = spt_pool_lds_bytes(P.n, pool);
+        const size_t lds = spt_pool_lds_bytes(P.n, pool) + (radiance ? 16u : 0u);   // (+ E behind the material table)
         uint32_t per_cu = c->blocks_per_cu;
         if (per_cu == 0) {
             const uint32_t by_lds = (uint32_t)((160u * 1024u) / lds);
@@ -1728,14 +1752,15 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         // its third launch on.  Results do not depend on the dispatch order.  Tuning bit 13 switches it off for this kernel (A/B),
         // SPT_FLAG_ONE_SHOT for one launch.
         const uint32_t nchunks = (uint32_t)((ntasks + 63) / 64);
-        std::vector<unsigned char> key(sizeof(spt_camera) + 10 * sizeof(uint32_t) + 2 * sizeof(uint64_t));
+        std::vector<unsigned char> key(sizeof(spt_camera) + 10 * sizeof(uint32_t) + 2 * sizeof(uint64_t) + sizeof c->env);
         {
             unsigned char* k = key.data();
             std::memcpy(k, cam, sizeof(spt_camera)); k += sizeof(spt_camera);
             const uint32_t words[10] = {w, h, row_begin, row_count, rb_log2, rb_stride, rb_mask, samps, c->variant, (uint32_t)blocks};
             std::memcpy(k, words, sizeof words); k += sizeof words;
             std::memcpy(k, &c->scene_gen, sizeof(uint64_t)); k += sizeof(uint64_t);
-            std::memcpy(k, &seed, sizeof(uint64_t));
+            std::memcpy(k, &seed, sizeof(uint64_t)); k += sizeof(uint64_t);
+            std::memcpy(k, c->env, sizeof c->env);
         }
         if (c->order_pending) { SPT_HIP(c, hipStreamWaitEvent(st, c->ev_order, 0)); c->order_pending = false; }
         // (not for the viewer's frames of a few samples per cell: a chunk's time is then the luck of 64 single paths, and the order kernel
@@ -1760,7 +1785,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         }
         SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
         SPT_HIP(c, hipEventRecord(c->ev_start, st));
-        SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st));
+        SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st, radiance));
         SPT_HIP(c, hipEventRecord(c->ev_mid, st));
         SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
         SPT_HIP(c, hipEventRecord(c->ev_stop, st));
@@ -1814,7 +1839,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
     }
     SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
     SPT_HIP(c, hipEventRecord(c->ev_start, st));
-    SPT_HIP(c, spt_k_launch(&P, (uint32_t)blocks, mat_lds, (c->needs_guard || !(cam_big <= 1e15f)) ? 1 : 0, (c->variant & 0x100u) ? 1 : 0, 1, big_block, st));
+    SPT_HIP(c, spt_k_launch(&P, (uint32_t)blocks, mat_lds, (c->needs_guard || !(cam_big <= 1e15f)) ? 1 : 0, (c->variant & 0x100u) ? 1 : 0, 1, big_block, st, radiance));
     SPT_HIP(c, hipEventRecord(c->ev_mid, st));
     SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
     SPT_HIP(c, hipEventRecord(c->ev_stop, st));
@@ -2068,6 +2093,7 @@ int spt_progressive_attach(spt_ctx* lane, spt_ctx* owner)
     if (lane == owner) return 0;
     if (!owner->d_accum) return lane->fail("spt_progressive_attach: call spt_progressive_begin on the owner first");
     if (lane->device != owner->device) return lane->fail("spt_progressive_attach: lane and owner are on different devices");
+    if (env_differs(lane, owner)) return lane->fail("spt_progressive_attach: the lane's environment differs from the owner's; set the owner's environment on every lane");
     if (int rc = spt_progressive_end(lane)) return rc;
     SPT_HIP(lane, hipSetDevice(lane->device));
     // a stream of another priority than the owner's (created at the default priority 0 by spt_create); further lanes take the
@@ -2098,6 +2124,8 @@ int spt_progressive_frame_async(spt_ctx* c, spt_ctx* owner, const spt_camera* ca
     if (c != owner && (c->mesh_scene != owner->mesh_scene || (!c->mesh_scene && c->n != owner->n) || (c->mesh_scene && (c->ntris != owner->ntris || c->ninst != owner->ninst)) ||
                        c->inst_scene != owner->inst_scene || (c->inst_scene && c->inst.models.size() != owner->inst.models.size())))
         return c->fail("spt_progressive_frame_async: the lane's scene differs from the owner's (kind or size); set the owner's scene on every lane");
+    if (c != owner && env_differs(c, owner))
+        return c->fail("spt_progressive_frame_async: the lane's environment differs from the owner's; set the owner's environment on every lane");
     // :922 the frame is the UN-NORMALISED sum of Renderer::render, on the lane's stream
     c->frames_in_flight_hint = owner->lanes_attached + 1u;           // the owner and its lanes each keep a frame in flight
     const int rrc = spt_render_rows_device(c, cam, c->prog_w, c->prog_h, 0, c->prog_h, samps, seed, 0u, c->d_frame, nullptr);

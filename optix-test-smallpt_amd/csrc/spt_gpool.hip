@@ -113,10 +113,13 @@ enum { QC_GEN = 0, QC_HIT = 1, QC_HITR = 2 };
 // what only the GEN batches (one in nine) and emissive hits touch in the second: Q4 {task + 1, next sample, -, -}  Q5 {block sum xyz, -}.
 // (old layout, for the record:) Q3 {rbase, task + 1, next sample, -}
 //                                Q4 {near key, near index, -, -}  Q5 {block sum xyz, -}
-template <bool STATS>
+// EP: empty, or EParams for the environment variant (a miss adds w * E to the slot's block sum Q5; spt_set_environment)
+template <bool STATS, typename... EP>
 __global__ __launch_bounds__(kQBlock) void gpoolkernel(const KParams K, const GridParams G, const uint32_t* __restrict__ g_cells,
-                                                       const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always, const QParams Q)
+                                                       const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always, const QParams Q,
+                                                       const EP... env)
 {
+    constexpr bool ENV = kHasEnv<EP...>;
     // LDS of the workgroup: [cell references, always-tested list][sphere records][cell headers][materials][wave regions].
     // The references come first so that a walker's cur / end are BYTE addresses that fit the 16-bit halves of a staged cell header, and
     // a reference holds sphere index + gb16 (gb16 = offset of the sphere records / 16): the record's address is reference << 4, one
@@ -591,6 +594,12 @@ __global__ __launch_bounds__(kQBlock) void gpoolkernel(const KParams K, const Gr
                     else if (!(w.x == 0.f && w.y == 0.f && w.z == 0.f)) { has_ray = true; to_gen = false; }
                     if (!(__builtin_fabsf(w.x) < __builtin_inff() && __builtin_fabsf(w.y) < __builtin_inff() && __builtin_fabsf(w.z) < __builtin_inff())) branchf |= 8u;
                 }
+            } else if constexpr (ENV) {
+                if (live) {                                                                 // :168 miss: + w * E, the path's last event
+                    const EParams E = env_params(env...);
+                    const float4 a = sq[5];
+                    sq[5] = make_float4(a.x + w.x * E.e[0], a.y + w.y * E.e[1], a.z + w.z * E.e[2], 0.f);
+                }
             }
             if (has_ray) {
                 sq[2] = make_float4(w.x, w.y, w.z, __uint_as_float(k1));
@@ -727,14 +736,17 @@ extern "C" size_t spt_gpool_slot_floats(uint32_t blocks, uint32_t waves, uint32_
 extern "C" size_t spt_gpool_stack_floats(uint32_t blocks, uint32_t waves, uint32_t S) { return (size_t)blocks * waves * S * (3u * spt::kQStackF4 * 4u); }
 
 extern "C" hipError_t spt_gpool_launch(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
-                                       const uint32_t* d_always, const spt::QParams* Q, uint32_t blocks, uint32_t threads, int stats, hipStream_t stream)
+                                       const uint32_t* d_always, const spt::QParams* Q, uint32_t blocks, uint32_t threads, int stats, hipStream_t stream,
+                                       const float* env)
 {
     if (threads == 0 || threads > (uint32_t)spt::kQBlock || (threads & 63u)) return hipErrorInvalidValue;
     if (Q->S == 0 || Q->S > 256u || (Q->S & 15u) || (Q->R & 3u) || Q->R == 0 || Q->R > 0xFFFFu || Q->drain == 0 || Q->drain > 64u || G->nrefs >= 0x7FFEu) return hipErrorInvalidValue;
     if ((((size_t)G->nrefs + G->nalways + 1u) * 2u + 15u) / 16u + G->n > 0xFFFFu) return hipErrorInvalidValue;   // references (index + gb16) are 16 bits
     const size_t lds = spt_gpool_lds_bytes(G, threads / 64u, Q->S, Q->R);
     if (lds > (size_t)160 * 1024) return hipErrorInvalidValue;
-    const void* fn = stats ? reinterpret_cast<const void*>(&spt::gpoolkernel<true>) : reinterpret_cast<const void*>(&spt::gpoolkernel<false>);
+    if (stats && env) return hipErrorInvalidValue;              // (environment variant: product build only)
+    const void* fn = stats ? reinterpret_cast<const void*>(&spt::gpoolkernel<true>)
+                   : env ? reinterpret_cast<const void*>(&spt::gpoolkernel<false, spt::EParams>) : reinterpret_cast<const void*>(&spt::gpoolkernel<false>);
     hipFuncAttributes fa{};
     hipError_t e = hipFuncGetAttributes(&fa, fn);
     if (e != hipSuccess) return e;
@@ -742,6 +754,8 @@ extern "C" hipError_t spt_gpool_launch(const spt::KParams* K, const spt::GridPar
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     if (stats) hipLaunchKernelGGL(spt::gpoolkernel<true>, dim3(blocks), dim3(threads), lds, stream, *K, *G, d_cells, d_refs, d_always, *Q);
+    else if (env) hipLaunchKernelGGL((spt::gpoolkernel<false, spt::EParams>), dim3(blocks), dim3(threads), lds, stream, *K, *G, d_cells, d_refs, d_always, *Q,
+                                     spt::EParams{{env[0], env[1], env[2]}});
     else hipLaunchKernelGGL(spt::gpoolkernel<false>, dim3(blocks), dim3(threads), lds, stream, *K, *G, d_cells, d_refs, d_always, *Q);
     return hipGetLastError();
 }

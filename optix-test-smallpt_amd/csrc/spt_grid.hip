@@ -58,10 +58,13 @@ struct GPath { f3 o, d, w; uint32_t depth, branch, rbase; };
 // walk, the same proof, spt_grid.h) instead of falling to the one-lane-per-path hierarchy.  The always-tested list is read from its own array.
 // WHERE = 2: the sphere records stay in global memory, the cell headers and references -- two of the walk's three lookups per sphere --
 // in LDS: tables whose records alone exceed the LDS but whose grid fits it.
-template <bool STATS, int WHERE>
+// EP: empty, or EParams for the environment variant (a miss adds w * E; spt_set_environment)
+template <bool STATS, int WHERE, typename... EP>
 __global__ __launch_bounds__(kGridBlock) void gridkernel(const KParams K, const GridParams G, const uint32_t* __restrict__ g_cells,
-                                                         const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always, uint32_t leave_q)
+                                                         const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always, uint32_t leave_q,
+                                                         const EP... env)
 {
+    constexpr bool ENV = kHasEnv<EP...>;
     constexpr bool GLOBAL_TABLES = WHERE == 1, GLOBAL_GEOM = WHERE != 0;
     extern __shared__ float4 s_lds_geom[];                       // n sphere records (WHERE 0), then the grid tables (WHERE 0, 2)
     uint32_t* const s_lds_cells = reinterpret_cast<uint32_t*>(s_lds_geom + (GLOBAL_GEOM ? 0u : (G.n ? G.n : 1u)));
@@ -419,6 +422,9 @@ __global__ __launch_bounds__(kGridBlock) void gridkernel(const KParams K, const 
                     if (p.depth >= SPT_K_MAX_DEPTH) ++nkill;
                     else if (!(p.w.x == 0.f && p.w.y == 0.f && p.w.z == 0.f)) mode = M_FRESH;
                 }
+            } else if constexpr (ENV) {                                                // :168 miss: + w * E, the path's last event
+                const EParams E = env_params(env...);
+                acc = acc + p.w * mk(E.e[0], E.e[1], E.e[2]);
             }
         }
         GSTAMP(4)
@@ -1139,8 +1145,19 @@ extern "C" size_t spt_grid_lds_bytes_tables(const spt::GridParams* G)
 
 template <bool STATS, int WHERE>
 static hipError_t launch_grid(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs, const uint32_t* d_always,
-                              uint32_t blocks, uint32_t threads, uint32_t leave_q, size_t lds, hipStream_t stream)
+                              uint32_t blocks, uint32_t threads, uint32_t leave_q, size_t lds, hipStream_t stream, const float* env)
 {
+    if constexpr (!STATS) {
+        if (env) {                                               // the environment variant (product builds only)
+            const spt::EParams E{{env[0], env[1], env[2]}};
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::gridkernel<STATS, WHERE, spt::EParams>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((spt::gridkernel<STATS, WHERE, spt::EParams>), dim3(blocks), dim3(threads), lds, stream, *K, *G, d_cells, d_refs, d_always, leave_q, E);
+            return hipGetLastError();
+        }
+    } else if (env) {
+        return hipErrorInvalidValue;
+    }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::gridkernel<STATS, WHERE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((spt::gridkernel<STATS, WHERE>), dim3(blocks), dim3(threads), lds, stream, *K, *G, d_cells, d_refs, d_always, leave_q);
@@ -1149,13 +1166,14 @@ static hipError_t launch_grid(const spt::KParams* K, const spt::GridParams* G, c
 
 // where: 0 = every table in LDS, 1 = every table in global memory, 2 = sphere records in global memory, cell headers and references in LDS
 extern "C" hipError_t spt_grid_launch(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
-                                      const uint32_t* d_always, uint32_t blocks, uint32_t threads, uint32_t leave_q, int stats, int where, hipStream_t stream)
+                                      const uint32_t* d_always, uint32_t blocks, uint32_t threads, uint32_t leave_q, int stats, int where, hipStream_t stream,
+                                      const float* env)
 {
     if (threads == 0 || threads > (uint32_t)spt::kGridBlock || (threads & 63u) || where < 0 || where > 2) return hipErrorInvalidValue;
     const size_t lds = where == 1 ? 0 : (where == 2 ? spt_grid_lds_bytes_tables(G) : spt_grid_lds_bytes(G));
-    if (where == 0) return stats ? launch_grid<true, 0>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream) : launch_grid<false, 0>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream);
-    if (where == 1) return stats ? launch_grid<true, 1>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream) : launch_grid<false, 1>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream);
-    return stats ? launch_grid<true, 2>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream) : launch_grid<false, 2>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream);
+    if (where == 0) return stats ? launch_grid<true, 0>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream, env) : launch_grid<false, 0>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream, env);
+    if (where == 1) return stats ? launch_grid<true, 1>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream, env) : launch_grid<false, 1>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream, env);
+    return stats ? launch_grid<true, 2>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream, env) : launch_grid<false, 2>(K, G, d_cells, d_refs, d_always, blocks, threads, leave_q, lds, stream, env);
 }
 
 extern "C" hipError_t spt_query_exhaustive_launch(const float4* geom, uint32_t n, const float* rays, uint32_t nrays, float* hits,

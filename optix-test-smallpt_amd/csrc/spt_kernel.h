@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "spt_tribvh.h"
 #include <stdint.h>
+#include <type_traits>
 
 #define SPT_K_MAX_DEPTH 4096u
 
@@ -91,6 +92,17 @@ struct QParams {
     uint32_t walk_iters;           // walk iterations between the issue of a batch's loads and the batch's code
 };
 
+// Environment radiance E of spt_set_environment.  The render kernels' environment variants take it as an optional trailing kernel
+// argument (a template pack, empty when E = 0), so the launches without it keep the signature and code they had before.  A path of
+// weight w whose closest-hit query finds nothing adds w * E to its block sum: one multiply and one add per component (smallpt.cpp:168).
+struct EParams { float e[3]; };
+
+#ifdef __HIPCC__
+template <typename... T> constexpr bool kHasEnv = (false || ... || std::is_same<T, EParams>::value);
+__device__ __forceinline__ EParams env_params() { return EParams{{0.f, 0.f, 0.f}}; }
+__device__ __forceinline__ EParams env_params(const EParams& E) { return E; }
+#endif
+
 }  // namespace spt
 
 namespace spt { struct GridParams; }
@@ -98,37 +110,41 @@ extern "C" size_t spt_gpool_lds_bytes(const spt::GridParams* G, uint32_t waves, 
 extern "C" size_t spt_gpool_slot_floats(uint32_t blocks, uint32_t waves, uint32_t S);
 extern "C" size_t spt_gpool_stack_floats(uint32_t blocks, uint32_t waves, uint32_t S);
 extern "C" hipError_t spt_gpool_launch(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
-                                       const uint32_t* d_always, const spt::QParams* Q, uint32_t blocks, uint32_t threads, int stats, hipStream_t stream);
+                                       const uint32_t* d_always, const spt::QParams* Q, uint32_t blocks, uint32_t threads, int stats, hipStream_t stream,
+                                       const float* env = nullptr);
 extern "C" size_t spt_grid_lds_bytes(const spt::GridParams* G);
 extern "C" int spt_grid_block_threads(void);
 extern "C" size_t spt_grid_stack_floats(uint32_t blocks, uint32_t threads);
 extern "C" hipError_t spt_grid_launch(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
-                                      const uint32_t* d_always, uint32_t blocks, uint32_t threads, uint32_t leave_q, int stats, int where, hipStream_t stream);
+                                      const uint32_t* d_always, uint32_t blocks, uint32_t threads, uint32_t leave_q, int stats, int where, hipStream_t stream,
+                                      const float* env = nullptr);
 extern "C" size_t spt_grid_lds_bytes_tables(const spt::GridParams* G);
 extern "C" size_t spt_mesh_lds_bytes(int bvh);
 extern "C" size_t spt_mesh_stack_floats(uint32_t blocks);
-extern "C" hipError_t spt_mesh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t blocks, hipStream_t stream);
+extern "C" hipError_t spt_mesh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t blocks, hipStream_t stream, const float* env = nullptr);
 extern "C" hipError_t spt_mesh_trace_rays(const spt::MParams* M, const float* d_rays, uint64_t nrays, float* d_hits, hipStream_t stream);
 // Instanced mesh scenes (spt_set_instances, spt_instance.h): bvh = 1 walks each model's exact hierarchy, 0 loops over each model's triangles.
 namespace spt { struct IParams; }
-extern "C" hipError_t spt_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t blocks, hipStream_t stream);
+extern "C" hipError_t spt_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t blocks, hipStream_t stream,
+                                      const float* env = nullptr);
 extern "C" hipError_t spt_inst_trace_rays(const spt::IParams* I, int bvh, int range, const float* d_rays, uint64_t nrays, float* d_hits, hipStream_t stream);
 extern "C" hipError_t spt_inst_occluded(const spt::IParams* I, int bvh, const float* d_rays, const float* d_tmax, uint64_t nrays, uint8_t* d_occ, hipStream_t stream);
 extern "C" hipError_t spt_aov_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t kind, hipStream_t stream);
 extern "C" size_t spt_k_lds_bytes(uint32_t n_pad, int mat_lds, int big_block);
 extern "C" size_t spt_k_stack_floats(uint32_t blocks, int block_threads);
-extern "C" hipError_t spt_k_launch(const spt::KParams* P, uint32_t blocks, int mat_lds, int guard, int diag, int bign, int big_block, hipStream_t stream);
+extern "C" hipError_t spt_k_launch(const spt::KParams* P, uint32_t blocks, int mat_lds, int guard, int diag, int bign, int big_block, hipStream_t stream,
+                                   const float* env = nullptr);
 extern "C" hipError_t spt_pool_chunk_order(const uint32_t* chunk_clock, uint32_t nchunks, uint32_t ntasks, uint32_t* chunk_order, uint32_t* work512, hipStream_t stream);
 extern "C" hipError_t spt_k_finalize(const float4* cells, float* out, uint32_t npix, float scale, int normalise, uint32_t nb, hipStream_t stream);
 extern "C" int spt_k_block_threads(void);
 extern "C" int spt_k_block_threads_for(int mat_lds, int big_block);
 extern "C" hipError_t spt_k_selftest(int op, const float* d_in, float* d_out, uint32_t n, uint32_t w, hipStream_t stream);
-extern "C" size_t spt_pool_lds_bytes(uint32_t n, int pool);
+extern "C" size_t spt_pool_lds_bytes(uint32_t n, int pool);   // (+ 16 bytes for an environment launch)
 extern "C" size_t spt_pool_stack_floats(uint32_t blocks, int pool);
 extern "C" size_t spt_pool_state_bytes(uint32_t blocks, int pool);
 extern "C" int spt_pool_max_spheres(void);
 extern "C" int spt_pool_default_slots(void);
 extern "C" int spt_pool_has_size(int pool);
-extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream);
+extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env = nullptr);
 extern "C" hipError_t spt_k_selftest_range(int op, uint32_t first, uint32_t count, unsigned long long* d_mismatches, uint32_t* d_first_bad, hipStream_t stream);
 extern "C" hipError_t spt_k_accumulate(float* accum, const float* frame, size_t n, int clear, hipStream_t stream);

@@ -89,9 +89,11 @@ __device__ __forceinline__ bool extend(Path& p, f3 no, f3 nd, f3 nf, uint32_t& n
         tlast = now__;                                                         \
     }
 
-template <bool MAT_LDS, bool GUARD, bool DIAG, bool BIGN, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void megakernel(const KParams P)
+// EP: empty, or EParams for the environment variant (a miss adds w * E; spt_set_environment)
+template <bool MAT_LDS, bool GUARD, bool DIAG, bool BIGN, int BLOCK, typename... EP>
+__global__ __launch_bounds__(BLOCK) void megakernel(const KParams P, const EP... env)
 {
+    constexpr bool ENV = kHasEnv<EP...>;
     unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tlast = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
     unsigned long long iters = 0, lanes_d1 = 0, lanes_d2 = 0, lanes_d3 = 0, runs_d3 = 0, runs_c1 = 0, lanes_c1 = 0;
@@ -402,8 +404,15 @@ __global__ __launch_bounds__(BLOCK) void megakernel(const KParams P)
             }
             const float nearest = near_key == kInfKey ? kInf : __uint_as_float(near_key + kEpsKeyBias);
             hit_t = nearest; hit_inst = inst;
-            if (nearest == kInf) alive = false;                                        // :168 miss (D13)
-            else shade = true;
+            if (nearest == kInf) {                                                     // :168 miss (D13)
+                if constexpr (ENV) {                                                   // + w * E, the path's last event
+                    const EParams E = env_params(env...);
+                    acc = acc + p.w * mk(E.e[0], E.e[1], E.e[2]);
+                }
+                alive = false;
+            } else {
+                shade = true;
+            }
         }
         SPT_STAMP(4)
         if (DIAG) { ++iters; lanes_d1 += __popcll(__ballot(shade || (!alive && hit_t == kInf))); lanes_d2 += __popcll(__ballot(shade)); }
@@ -670,8 +679,19 @@ extern "C" hipError_t spt_k_selftest(int op, const float* d_in, float* d_out, ui
 // ---- launch wrappers used by spt_api.cpp ----
 
 template <bool M, bool G, bool D, bool B, int BLOCK>
-static hipError_t launch_variant(const spt::KParams* P, uint32_t blocks, size_t lds, hipStream_t stream)
+static hipError_t launch_variant(const spt::KParams* P, uint32_t blocks, size_t lds, hipStream_t stream, const float* env)
 {
+    if constexpr (!D) {
+        if (env) {                                               // the environment variant (product builds only)
+            const spt::EParams E{{env[0], env[1], env[2]}};
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::megakernel<M, G, D, B, BLOCK, spt::EParams>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((spt::megakernel<M, G, D, B, BLOCK, spt::EParams>), dim3(blocks), dim3(BLOCK), lds, stream, *P, E);
+            return hipGetLastError();
+        }
+    } else if (env) {
+        return hipErrorInvalidValue;
+    }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::megakernel<M, G, D, B, BLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((spt::megakernel<M, G, D, B, BLOCK>), dim3(blocks), dim3(BLOCK), lds, stream, *P);
@@ -693,20 +713,21 @@ extern "C" size_t spt_k_lds_bytes(uint32_t n_pad, int mat_lds, int big_block)
 
 extern "C" size_t spt_k_stack_floats(uint32_t blocks, int block_threads) { return (size_t)blocks * (size_t)block_threads * spt::kStackEntries * 16u; }
 
-extern "C" hipError_t spt_k_launch(const spt::KParams* P, uint32_t blocks, int mat_lds, int guard, int diag, int bign, int big_block, hipStream_t stream)
+extern "C" hipError_t spt_k_launch(const spt::KParams* P, uint32_t blocks, int mat_lds, int guard, int diag, int bign, int big_block, hipStream_t stream,
+                                   const float* env)
 {
     const size_t lds = spt_k_lds_bytes(P->n_pad, mat_lds, big_block);
     const bool b512 = !mat_lds && big_block == 512;
     constexpr int B0 = spt::kBlock;
     if (diag) {
-        if (mat_lds) return launch_variant<true, false, true, false, B0>(P, blocks, lds, stream);
-        return b512 ? launch_variant<false, false, true, true, 512>(P, blocks, lds, stream) : launch_variant<false, false, true, true, 256>(P, blocks, lds, stream);
+        if (mat_lds) return launch_variant<true, false, true, false, B0>(P, blocks, lds, stream, env);
+        return b512 ? launch_variant<false, false, true, true, 512>(P, blocks, lds, stream, env) : launch_variant<false, false, true, true, 256>(P, blocks, lds, stream, env);
     }
     (void)bign;   // product launches always take the grouped closest-hit loop: the unrolled small-table form (n <= 24) spilled 26 scalar
                   // registers and only served scenes the pool kernel refuses (range-guarded square root, colours outside [0,1])
-    if (mat_lds) return guard ? launch_variant<true, true, false, true, B0>(P, blocks, lds, stream) : launch_variant<true, false, false, true, B0>(P, blocks, lds, stream);
-    if (b512) return guard ? launch_variant<false, true, false, true, 512>(P, blocks, lds, stream) : launch_variant<false, false, false, true, 512>(P, blocks, lds, stream);
-    return guard ? launch_variant<false, true, false, true, 256>(P, blocks, lds, stream) : launch_variant<false, false, false, true, 256>(P, blocks, lds, stream);
+    if (mat_lds) return guard ? launch_variant<true, true, false, true, B0>(P, blocks, lds, stream, env) : launch_variant<true, false, false, true, B0>(P, blocks, lds, stream, env);
+    if (b512) return guard ? launch_variant<false, true, false, true, 512>(P, blocks, lds, stream, env) : launch_variant<false, false, false, true, 512>(P, blocks, lds, stream, env);
+    return guard ? launch_variant<false, true, false, true, 256>(P, blocks, lds, stream, env) : launch_variant<false, false, false, true, 256>(P, blocks, lds, stream, env);
 }
 
 extern "C" hipError_t spt_k_finalize(const float4* cells, float* out, uint32_t npix, float scale, int normalise, uint32_t nb, hipStream_t stream)

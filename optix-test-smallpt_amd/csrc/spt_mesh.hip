@@ -521,6 +521,12 @@ typedef const MParams* CModel;
 
 __device__ __forceinline__ IParams inst_params() { return IParams{}; }
 __device__ __forceinline__ IParams inst_params(const IParams& I) { return I; }
+// The render kernel's environment variants: EParams alone (GEOM 0-2), or the instance parameters and E as one record (GEOM 3 / 4)
+struct InstEnvParams { IParams I; EParams E; };
+template <typename... T> constexpr bool kMeshEnv = kHasEnv<T...> || (false || ... || std::is_same<T, InstEnvParams>::value);
+__device__ __forceinline__ IParams inst_params(const EParams&) { return IParams{}; }
+__device__ __forceinline__ IParams inst_params(const InstEnvParams& p) { return p.I; }
+__device__ __forceinline__ EParams env_params(const InstEnvParams& p) { return p.E; }
 
 struct InstWin { uint32_t inst, tri; f3 o, d; };                 // the winning instance, its triangle and the object-space ray it was found with
 
@@ -813,10 +819,12 @@ struct MPath { f3 o, d, w; uint32_t depth, branch, rbase; };
 // GEOM 0: triangles, exhaustive; 1: triangles through the hierarchy; 2: a sphere table through its hierarchy (staging a small
 // tree into LDS behind the stacks was measured: 30 % slower -- two workgroups per CU and conflicting per-lane ds_read_b128);
 // 3 / 4: an instanced scene (I) through each model's exhaustive loop / exact hierarchy, M holding the per-instance materials
-// (The instance parameters come in as an optional trailing argument: GEOM 0-2 keep the signature and code they had before instances.)
+// (The instance parameters come in as an optional trailing argument: GEOM 0-2 keep the signature and code they had before instances.
+// The environment variants take EParams there, or InstEnvParams for GEOM 3 / 4: a miss adds w * E, spt_set_environment.)
 template <int GEOM, typename... IP>
 __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const MParams M, const IP... ip)
 {
+    constexpr bool ENV = kMeshEnv<IP...>;
     extern __shared__ float4 s_tile[];
     const IParams I = inst_params(ip...);
     const uint32_t lane = lane_id_m();
@@ -1002,6 +1010,10 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
             ++nbounce;
             if (tri == 0xFFFFFFFFu) {
                 alive = false;                                                   // smallpt.cpp:168 miss (D13)
+                if constexpr (ENV) {                                             // + w * E, the path's last event
+                    const EParams E = env_params(ip...);
+                    acc = acc + p.w * mk(E.e[0], E.e[1], E.e[2]);
+                }
             } else {
                 // ---- shadePaths, smallpt.cpp:170-263 under D2-D6, D18, D19 ----
                 const MeshHit h = GEOM == 2 ? make_sphere_hit(K, tri, t, p.o, p.d) : GEOM >= 3 ? make_inst_hit(I, win, t) : make_hit(M, tri, t, p.o, p.d);
@@ -1160,8 +1172,15 @@ __global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MP
 extern "C" size_t spt_mesh_lds_bytes(int bvh) { return bvh ? (size_t)spt::kMeshBlock * 32u * 4u : (size_t)spt::kTile * 48u; }
 extern "C" size_t spt_mesh_stack_floats(uint32_t blocks) { return (size_t)blocks * spt::kMeshBlock * 36u; }
 
-extern "C" hipError_t spt_mesh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t blocks, hipStream_t stream)
+extern "C" hipError_t spt_mesh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t blocks, hipStream_t stream, const float* env)
 {
+    if (env) {                                                   // the environment variants
+        const spt::EParams E{{env[0], env[1], env[2]}};
+        if (M->sphere_mode) hipLaunchKernelGGL((spt::meshkernel<2, spt::EParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, E);
+        else if (M->bvh_nodes) hipLaunchKernelGGL((spt::meshkernel<1, spt::EParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, E);
+        else hipLaunchKernelGGL((spt::meshkernel<0, spt::EParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, E);
+        return hipGetLastError();
+    }
     if (M->sphere_mode) hipLaunchKernelGGL(spt::meshkernel<2>, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M);
     else if (M->bvh_nodes) hipLaunchKernelGGL(spt::meshkernel<1>, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M);
     else hipLaunchKernelGGL(spt::meshkernel<0>, dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M);
@@ -1245,8 +1264,15 @@ extern "C" hipError_t spt_mesh_trace_rays_range(const spt::MParams* M, const flo
 
 // ---- instanced scenes (spt_set_instances): M = the per-instance materials (+ strips), I = the instance records and model descriptors;
 // bvh = 1: each model's exact hierarchy, 0: each model's exhaustive loop.
-extern "C" hipError_t spt_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t blocks, hipStream_t stream)
+extern "C" hipError_t spt_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t blocks, hipStream_t stream,
+                                      const float* env)
 {
+    if (env) {                                                   // the environment variants
+        const spt::InstEnvParams IE{*I, spt::EParams{{env[0], env[1], env[2]}}};
+        if (bvh) hipLaunchKernelGGL((spt::meshkernel<4, spt::InstEnvParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, IE);
+        else hipLaunchKernelGGL((spt::meshkernel<3, spt::InstEnvParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, IE);
+        return hipGetLastError();
+    }
     if (bvh) hipLaunchKernelGGL((spt::meshkernel<4, spt::IParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, *I);
     else hipLaunchKernelGGL((spt::meshkernel<3, spt::IParams>), dim3(blocks), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, *I);
     return hipGetLastError();

@@ -309,6 +309,19 @@ int spt_multi_set_sphere_accel(spt_multi* m, int accel)
     }
 }
 
+int spt_multi_set_environment(spt_multi* m, const float radiance[3])
+{
+    if (!m) return 1;
+    try {
+    return m->on_all([m, radiance](int i) {
+        Rank& r = m->ranks[(size_t)i];
+        if (spt_set_environment(r.ctx, radiance)) r.error = spt_last_error(r.ctx);
+    });
+    } catch (const std::exception& e) {
+        return m->fail("spt_multi_set_environment: %s", e.what());
+    }
+}
+
 // Test hook (csrc/spt_internal.h): kernel watchdog of ONE rank's context -- lets a test make exactly one rank's render fail
 int spt_multi_set_rank_watchdog(spt_multi* m, uint32_t rank, double seconds)
 {

@@ -71,9 +71,12 @@ __device__ __forceinline__ uint32_t pack_path(uint32_t depth, uint32_t branchf, 
 
 enum { C_GEN = 0, C_DIFF = 1, C_REFR = 2 };
 
-template <int P, int NG>
-__global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K)
+// EP: empty, or EParams for the environment variant: E is staged in one LDS entry behind the material table and read on a miss only
+// (the bounce loop's constants come from the kernel-argument segment; E is not kept in scalar registers across it)
+template <int P, int NG, typename... EP>
+__global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const EP... env)
 {
+    constexpr bool ENV = kHasEnv<EP...>;
     static_assert(P % 16 == 0 && P <= 256, "pool size");
     extern __shared__ float4 lds[];
     constexpr int kWaveF4 = (kSlotBytes * P) / 16;               // float4 per wave region
@@ -98,6 +101,9 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K)
         s_mat[3 * i + 0] = real ? K.mat[3 * i + 0] : make_float4(0.f, 0.f, 0.f, 0.f);
         s_mat[3 * i + 1] = real ? K.mat[3 * i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
         s_mat[3 * i + 2] = real ? K.mat[3 * i + 2] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if constexpr (ENV) {
+        if (threadIdx.x == 0) { const EParams E = env_params(env...); s_mat[9 * NG] = make_float4(E.e[0], E.e[1], E.e[2], 0.f); }
     }
     // every slot starts on the GEN list as a finished, task-less slot
     const uint32_t wave_gid = blockIdx.x * (kPoolBlock / 64) + wave;
@@ -524,6 +530,9 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K)
                         next = refl == 2u ? C_REFR : C_DIFF;
                     }
                 }
+            } else if constexpr (ENV) {                                                     // :168 miss: + w * E, the path's last event
+                const float4 e = s_mat[9 * NG];
+                ACX[slot] = ACX[slot] + w.x * e.x; ACY[slot] = ACY[slot] + w.y * e.y; ACZ[slot] = ACZ[slot] + w.z * e.z;
             }
         }
         PH_STAMP(3)
@@ -665,8 +674,16 @@ extern "C" int spt_pool_max_spheres(void) { return spt::kMaxUnroll; }
 extern "C" int spt_pool_default_slots(void) { return spt::kTaskLds ? 144 : 160; }
 
 template <int P, int NG>
-static hipError_t launch_pool(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream)
+static hipError_t launch_pool(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env)
 {
+    if (env) {
+        const spt::EParams E{{env[0], env[1], env[2]}};
+        lds += 16u;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG, spt::EParams>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((spt::poolkernel<P, NG, spt::EParams>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K, E);
+        return hipGetLastError();
+    }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((spt::poolkernel<P, NG>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K);
@@ -674,17 +691,17 @@ static hipError_t launch_pool(const spt::KParams* K, uint32_t blocks, size_t lds
 }
 
 template <int P>
-static hipError_t launch_pool_ng(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream)
+static hipError_t launch_pool_ng(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env)
 {
     switch (K->n == 0 ? 1u : (K->n + 2u) / 3u) {
-    case 1: return launch_pool<P, 1>(K, blocks, lds, stream);
-    case 2: return launch_pool<P, 2>(K, blocks, lds, stream);
-    case 3: return launch_pool<P, 3>(K, blocks, lds, stream);
-    case 4: return launch_pool<P, 4>(K, blocks, lds, stream);
-    case 5: return launch_pool<P, 5>(K, blocks, lds, stream);
-    case 6: return launch_pool<P, 6>(K, blocks, lds, stream);
-    case 7: return launch_pool<P, 7>(K, blocks, lds, stream);
-    case 8: return launch_pool<P, 8>(K, blocks, lds, stream);
+    case 1: return launch_pool<P, 1>(K, blocks, lds, stream, env);
+    case 2: return launch_pool<P, 2>(K, blocks, lds, stream, env);
+    case 3: return launch_pool<P, 3>(K, blocks, lds, stream, env);
+    case 4: return launch_pool<P, 4>(K, blocks, lds, stream, env);
+    case 5: return launch_pool<P, 5>(K, blocks, lds, stream, env);
+    case 6: return launch_pool<P, 6>(K, blocks, lds, stream, env);
+    case 7: return launch_pool<P, 7>(K, blocks, lds, stream, env);
+    case 8: return launch_pool<P, 8>(K, blocks, lds, stream, env);
     default: return hipErrorInvalidValue;
     }
 }
@@ -698,15 +715,15 @@ extern "C" int spt_pool_has_size(int pool)
     return pool == 128 || pool == 144 || pool == 160;
 }
 
-extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream)
+extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env)
 {
     const size_t lds = spt_pool_lds_bytes(K->n, pool);
-    if (pool == 128) return launch_pool_ng<128>(K, blocks, lds, stream);
-    if (pool == 160) return launch_pool_ng<160>(K, blocks, lds, stream);
-    if (pool == 144) return launch_pool_ng<144>(K, blocks, lds, stream);
+    if (pool == 128) return launch_pool_ng<128>(K, blocks, lds, stream, env);
+    if (pool == 160) return launch_pool_ng<160>(K, blocks, lds, stream, env);
+    if (pool == 144) return launch_pool_ng<144>(K, blocks, lds, stream, env);
 #ifdef SPT_POOL_SIZES
-    if (pool == 96) return launch_pool_ng<96>(K, blocks, lds, stream);
-    if (pool == 192) return launch_pool_ng<192>(K, blocks, lds, stream);
+    if (pool == 96) return launch_pool_ng<96>(K, blocks, lds, stream, env);
+    if (pool == 192) return launch_pool_ng<192>(K, blocks, lds, stream, env);
 #endif
     return hipErrorInvalidValue;
 }

@@ -120,6 +120,8 @@ public:
     void setMeshAccel(int accel) { check(spt_set_mesh_accel(ctx_, accel)); }
     // the same switch for sphere tables above 24 spheres (exhaustive-equivalent by construction, include/smallpt_mi355x.h)
     void setSphereAccel(int accel) { check(spt_set_sphere_accel(ctx_, accel)); }
+    // radiance of escaped paths (smallpt.cpp:168 "path.weight * envContrib", spt_set_environment): (0,0,0) = black, the default
+    void setEnvironment(const float3& e) { const float v[3] = {e.x, e.y, e.z}; check(spt_set_environment(ctx_, v)); }
     std::vector<Hit> traceRays(const Ray* rays, size_t n)
     {
         std::vector<Hit> hits(n);
@@ -248,6 +250,7 @@ public:
     }
     void setMeshAccel(int accel) { check(spt_multi_set_mesh_accel(m_, accel)); }
     void setSphereAccel(int accel) { check(spt_multi_set_sphere_accel(m_, accel)); }
+    void setEnvironment(const float3& e) { const float v[3] = {e.x, e.y, e.z}; check(spt_multi_set_environment(m_, v)); }
     std::vector<float3> render(const spt_camera& camera, size_t imageWidth, size_t imageHeight,
                                size_t sampleCountPerJitterCell, size_t seed, bool normalise = false)
     {

@@ -274,6 +274,12 @@ Scene load_scene_json(const std::string& text)
         sc.spheres.emplace_back((float)number(member(*e, "radius"), "radius"), vec3(member(*e, "center"), "center"),
                                 vec3(member(*e, "emission"), "emission"), vec3(member(*e, "color"), "color"), refl);
     }
+    if (root->obj.count("environment")) {
+        sc.environment = vec3(member(*root, "environment"), "environment");
+        const float e[3] = {sc.environment.x, sc.environment.y, sc.environment.z};
+        for (float v : e)
+            if (!(v >= 0.f && v < INFINITY)) throw std::runtime_error("scene JSON: \"environment\" components must be finite and >= 0");
+    }
     auto cit = root->obj.find("camera");
     if (cit != root->obj.end() && cit->second->kind == JValue::Object) {
         const JValue& c = *cit->second;
@@ -353,6 +359,7 @@ std::string scene_to_json(const Scene& scene)
         }
         o << "]";
     }
+    if (scene.environment.x != 0.f || scene.environment.y != 0.f || scene.environment.z != 0.f) { o << ", \"environment\": "; v3(scene.environment); }
     o << "}";
     return o.str();
 }

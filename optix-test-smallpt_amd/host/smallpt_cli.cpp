@@ -9,12 +9,15 @@
 //                  [--aov normal|albedo|uv|dist]                  first-hit feature buffer instead of radiance (spt_render_aov); with
 //                                                              --single-triangle --aov normal: the reference program's own image (smallpt.cpp:179-183)
 //                  [--devices 0,1,...] [--self-exchange]      row bands over several GPUs + RCCL exchange (MultiRenderer)
+//                  [--env r,g,b] [--print-environment]         radiance of escaped paths (overrides the scene file's "environment"); print it
+//                                                              as loaded and overridden, then exit (host only)
 //   smallpt_mi355x [spp] --viewer [--frames N] [--request JSON] [--frames-after M] [--threaded] [--org x,y,z]
 //                  [--pipeline L] [--bench-frames N]           L frames in flight (one context each); frames/s of N frames as JSON
 //                  [--dump-raw accum.bin]                      main()'s progressive loop (smallpt.cpp:840-1005) without the
 //                                                              window: N frames, then the request(s), then M frames; writes the
 //                                                              normalised image like the exit path (:995-1004)
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,6 +50,8 @@ int main(int argc, char* argv[])
     std::string dump_raw;
     float org[3] = {0, -1, 0};
     bool have_org = false;
+    float env[3] = {0, 0, 0};
+    bool have_env = false, print_env = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value after %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -79,14 +84,23 @@ int main(int argc, char* argv[])
         else if (a == "--request") requests.push_back(next());
         else if (a == "--dump-raw") dump_raw = next();
         else if (a == "--org") { if (std::sscanf(next(), "%f,%f,%f", &org[0], &org[1], &org[2]) != 3) { std::fprintf(stderr, "--org x,y,z\n"); return 2; } have_org = true; }
+        else if (a == "--env") {
+            if (std::sscanf(next(), "%f,%f,%f", &env[0], &env[1], &env[2]) != 3 || !(env[0] >= 0.f && env[1] >= 0.f && env[2] >= 0.f && env[0] < INFINITY && env[1] < INFINITY && env[2] < INFINITY)) {
+                std::fprintf(stderr, "--env r,g,b (each finite and >= 0)\n"); return 2;
+            }
+            have_env = true;
+        }
+        else if (a == "--print-environment") print_env = true;
         else if (a == "--devices") { const char* p = next(); while (*p) { devices.push_back((int)std::strtol(p, const_cast<char**>(&p), 10)); if (*p == ',') ++p; } }
         else if (a[0] != '-') spp = std::atoi(a.c_str());
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
         Scene scene = scene_path.empty() ? cornell9() : (scene_path == "shipped-meshes" ? shipped_two_sphere_mesh_scene() : load_scene_file(scene_path));
+        if (have_env) scene.environment = make_float3(env[0], env[1], env[2]);
         realize_meshes(scene);
-        auto upload = [&](Renderer& rr) {          // spheres, or the Intersector seam for a mesh scene
+        auto upload = [&](Renderer& rr) {          // spheres, or the Intersector seam for a mesh scene; the environment
+            rr.setEnvironment(scene.environment);
             if (scene.meshes.empty()) { if (accel >= 0) rr.setSphereAccel(accel); rr.setScene(scene.spheres); return; }
             if (accel == SPT_ACCEL_GRID) throw std::runtime_error("--accel grid applies to sphere scenes");
             if (accel >= 0) rr.setMeshAccel(accel);
@@ -98,6 +112,7 @@ int main(int argc, char* argv[])
             std::ofstream f(dump_path);
             f << scene_to_json(scene) << "\n";
         }
+        if (print_env) { std::printf("environment %.9g %.9g %.9g\n", scene.environment.x, scene.environment.y, scene.environment.z); return 0; }
         if (parse_only) {   // host-only path (no GPU): used by the CPU tests of the JSON loader
             const std::vector<spt_sphere> abi = to_abi(scene.spheres);
             std::fwrite(abi.data(), sizeof(spt_sphere), abi.size(), stdout);
@@ -110,8 +125,9 @@ int main(int argc, char* argv[])
             Renderer renderer(device);
             std::vector<std::unique_ptr<Renderer>> extra;           // --pipeline N: one more context (same device, same scene) per further frame in flight
             for (int k = 1; k < pipeline; ++k) extra.emplace_back(new Renderer(device));
-            auto setup = [&](Renderer& rr, bool probe_it) {
+            auto setup = [&](Renderer& rr, bool probe_it) {   // (every lane of the render thread gets the scene and its environment)
                 if (!single_triangle) { upload(rr); return; }
+                rr.setEnvironment(scene.environment);
                 TriMesh triangle;                                                     // smallpt.cpp:826-828
                 triangle.positionBuffer = {make_float3(-0.5f, -0.5f, -2), make_float3(0.5f, -0.5f, -2), make_float3(0, 0.5f, -2)};
                 triangle.normalBuffer = {make_float3(1, 0, 0), make_float3(0, 1, 0), make_float3(0, 0, 1)};
@@ -175,6 +191,7 @@ int main(int argc, char* argv[])
         if (aov >= 0 && !devices.empty()) throw std::runtime_error("--aov renders on one device (no --devices)");
         if (!devices.empty()) {
             MultiRenderer multi(devices, self_exchange);
+            multi.setEnvironment(scene.environment);
             multi.setScene(scene.spheres);
             std::vector<float3> c = multi.render(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, /*normalise=*/true);
             const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();

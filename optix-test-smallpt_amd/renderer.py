@@ -190,6 +190,20 @@ def _stats_dict(st):
             "grid_blocks": int(st.grid_blocks), "block_threads": int(st.block_threads)}
 
 
+def environment_radiance(rgb):
+    """The radiance E of spt_set_environment as three float32 values: None = black; each component finite and >= 0 (ValueError otherwise,
+    before any device call)."""
+    if rgb is None:
+        return np.zeros(3, dtype=np.float32)
+    e = np.asarray(rgb, dtype=np.float64)
+    if e.shape != (3,):
+        raise ValueError(f"environment: three components (r, g, b) expected, got shape {e.shape}")
+    e = e.astype(np.float32)
+    if not (np.all(np.isfinite(e)) and np.all(e >= 0)):
+        raise ValueError(f"environment: each component must be finite and >= 0, got {e.tolist()}")
+    return e
+
+
 class Renderer:
     """One context = one HIP device (spt_create)."""
 
@@ -247,6 +261,8 @@ class Renderer:
             other.set_sphere_accel(st["sphere_accel"])
         if st["mesh_accel"] is not None:
             other.set_mesh_accel(st["mesh_accel"])
+        if st.get("environment") is not None:
+            other.set_environment(st["environment"])
         if st["scene"] is not None:
             if st["scene"][0] == "spheres":
                 other.set_scene(st["scene"][1])
@@ -302,6 +318,21 @@ class Renderer:
         self._check(self._lib.spt_set_sphere_accel(self._h, int(accel)))
         self._state["sphere_accel"] = int(accel)
         self._state_version += 1
+
+    def set_environment(self, rgb):
+        """Radiance E gathered by a render path that leaves the scene (smallpt.cpp:168 "path.weight * envContrib"): a miss adds w * E to
+        the path's sample.  rgb = (r, g, b), each finite and >= 0; None or (0, 0, 0) = black (the default).  Renders and progressive frames
+        only -- not the first-hit feature buffers, not the queries (include/smallpt_mi355x.h spt_set_environment)."""
+        e = environment_radiance(rgb)
+        self._check(self._lib.spt_set_environment(self._h, e.ctypes.data_as(C.POINTER(C.c_float))))
+        self._state["environment"] = e.copy()
+        self._state_version += 1
+
+    def environment(self):
+        """The context's current E as float32[3]."""
+        e = np.zeros(3, dtype=np.float32)
+        self._check(self._lib.spt_get_environment(self._h, e.ctypes.data_as(C.POINTER(C.c_float))))
+        return e
 
     def set_mesh_accel(self, accel):
         """ACCEL_AUTO (default: the faster of the two exact modes per launch), ACCEL_BVH (the role of the reference's OptiX Prime model,
@@ -597,6 +628,11 @@ class MultiRenderer:
 
     def set_sphere_accel(self, accel):
         self._check(self._lib.spt_multi_set_sphere_accel(self._h, int(accel)))
+
+    def set_environment(self, rgb):
+        """spt_multi_set_environment: Renderer.set_environment on every device."""
+        e = environment_radiance(rgb)
+        self._check(self._lib.spt_multi_set_environment(self._h, e.ctypes.data_as(C.POINTER(C.c_float))))
 
     def set_rank_watchdog(self, rank, seconds):
         """Test hook (csrc/spt_internal.h): kernel watchdog of one rank's context."""

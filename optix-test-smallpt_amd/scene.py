@@ -83,14 +83,27 @@ def random_spheres(total=1024, seed=1024):
 
 # ---- JSON scene file: vectors are 3-number arrays like the reference's
 # request messages (smallpt.cpp:913,983); field order = Sphere ctor (scene.h:91) ----
-def spheres_to_json(spheres, camera=None):
+def spheres_to_json(spheres, camera=None, environment=None):
+    """Scene file of a sphere table; environment = (r, g, b) writes the optional "environment" key (spt_set_environment)."""
     doc = {"spheres": [
         {"radius": float(s["radius"]), "center": [float(x) for x in s["center"]],
          "emission": [float(x) for x in s["emission"]], "color": [float(x) for x in s["color"]],
          "refl": REFL_NAMES[int(s["refl"])]} for s in spheres]}
     if camera is not None:
         doc["camera"] = camera
+    if environment is not None:
+        doc["environment"] = [float(np.float32(v)) for v in environment]
     return json.dumps(doc)
+
+
+def environment_from_json(text):
+    """The optional "environment": [r, g, b] of a scene file (either kind) as float32[3]; absent = black (0, 0, 0)."""
+    e = json.loads(text).get("environment")
+    if e is None:
+        return np.zeros(3, dtype=np.float32)
+    if not isinstance(e, list) or len(e) != 3:
+        raise ValueError('scene JSON: "environment" must be [r, g, b]')
+    return np.array([float(v) for v in e], dtype=np.float32)
 
 
 def spheres_from_json(text):
@@ -147,10 +160,10 @@ def single_triangle_scene():
     return [mesh], [((1, 0, 0), (0, 0, 0), DIFF)]
 
 
-def meshes_to_json(meshes, materials, generators=None, camera=None, spheres=None):
+def meshes_to_json(meshes, materials, generators=None, camera=None, spheres=None, environment=None):
     """Scene file with a "meshes" array (host/scene.hpp): entry i is {"sphere": {"center", "radius", "subdiv"}} when
     generators[i] = (center, radius, subdiv) (re-tessellated by the loader with makeSphereTriMesh) or explicit
-    "positions"/"normals"/"indices" buffers, plus the instance's material."""
+    "positions"/"normals"/"indices" buffers, plus the instance's material; environment = (r, g, b): the optional "environment" key."""
     out = []
     for i, (m, (e, col, refl)) in enumerate(zip(meshes, materials)):
         ent = {}
@@ -171,6 +184,8 @@ def meshes_to_json(meshes, materials, generators=None, camera=None, spheres=None
         doc["spheres"] = json.loads(spheres_to_json(spheres))["spheres"]
     if camera is not None:
         doc["camera"] = camera
+    if environment is not None:
+        doc["environment"] = [float(np.float32(v)) for v in environment]
     return json.dumps(doc)
 
 
