@@ -2,6 +2,7 @@
 // Host-side only: scene upload, launch geometry, HIP-event timing, statistics, image output.
 #include "../../include/smallpt_mi355x.h"
 #include "spt_internal.h"
+#include "spt_share.h"
 #include "spt_bvh.h"
 #include "spt_grid.h"
 #include "spt_kernel.h"
@@ -69,6 +70,8 @@ struct spt_ctx {
     uint32_t scene_cap = 0;
     bool needs_guard = false;      // r*r < 2^-60 or coordinates above 1e15: the hot-loop sqrt keeps its range guard
     bool pool_ok = false;          // scene qualifies for the material-sorted pool kernel (spt_pool.hip)
+    int share = 0;                 // sharing pattern of the pool kernel's closest hit that every claim of holds on this table (spt_share.h)
+    int last_share = 0;            // ... the one the last pool launch ran
     float* d_stack = nullptr;      // pool kernel: global-memory stack of pending transmitted children
     size_t stack_cap = 0;          // in floats
     bool last_was_pool = false;
@@ -307,6 +310,17 @@ static int build_sphere_accel(spt_ctx* c);
 static int build_default_sphere_structure(spt_ctx* c);
 static int build_sphere_grid_tables(spt_ctx* c);
 
+// The pool kernel's sharing pattern for a table: the most specific compiled one whose claims hold bitwise on the padded table the
+// kernel stages (3 NG slots, padding centred at +0; spt_share.h).
+static int table_share(const float4* geom, uint32_t n)
+{
+    if (n > (uint32_t)spt::kShareSlots) return spt::kShareNone;
+    const int ng = n == 0 ? 1 : (int)((n + 2u) / 3u);
+    float c[3 * spt::kShareSlots] = {};
+    for (uint32_t i = 0; i < n; ++i) { c[3 * i + 0] = geom[i].x; c[3 * i + 1] = geom[i].y; c[3 * i + 2] = geom[i].z; }
+    return spt::share_select(c, ng);
+}
+
 int spt_set_scene(spt_ctx* c, const spt_sphere* s, uint32_t n)
 {
     if (!c) return 1;
@@ -383,6 +397,7 @@ static int set_scene_impl(spt_ctx* c, const spt_sphere* s, uint32_t n)
     // Pool kernel: unrolled closest hit (<= 24 spheres), un-guarded sqrt, and path weights that only the glass factors
     // can push out of the finite range (colours in [0,1], finite emission) -- it tracks that case with a flag.
     c->pool_ok = n <= (uint32_t)spt_pool_max_spheres() && !c->needs_guard;
+    c->share = table_share(geom.data(), n);
     for (uint32_t i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k)
             if (!(s[i].color[k] >= 0.f && s[i].color[k] <= 1.f) || !(std::fabs(s[i].emission[k]) <= 3e38f)) c->pool_ok = false;
@@ -1785,7 +1800,10 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         }
         SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
         SPT_HIP(c, hipEventRecord(c->ev_start, st));
-        SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st, radiance));
+        // sharing pattern of the closest hit (spt_share.h): compiled for the default pool size; tuning bit 14 forces the generic test
+        const int share = !(c->variant & 0x4000u) && spt_pool_share_compiled(pool, P.n, c->share) ? c->share : spt::kShareNone;
+        SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st, radiance, share));
+        c->last_share = share;
         SPT_HIP(c, hipEventRecord(c->ev_mid, st));
         SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
         SPT_HIP(c, hipEventRecord(c->ev_stop, st));
@@ -2188,6 +2206,7 @@ int spt_diag(spt_ctx* c, unsigned long long* out24)
     if (!c || !out24) return 1;
     if (c->last_was_pool || c->last_kernel == 4 || c->last_kernel == 5) {
         std::memcpy(out24, c->pool_stats, sizeof c->pool_stats);
+        if (c->last_was_pool) out24[23] = (unsigned long long)c->last_share;
         return 0;
     }
     std::memcpy(out24, c->diag, sizeof c->diag);
@@ -2202,6 +2221,15 @@ int spt_set_watchdog(spt_ctx* c, double seconds)
 }
 
 int spt_last_kernel(spt_ctx* c) { return c ? c->last_kernel : -1; }
+
+int spt_selftest_share(const spt_sphere* spheres, uint32_t n, int* pattern)
+{
+    if ((!spheres && n) || !pattern) return 1;
+    std::vector<float4> geom(n ? n : 1);
+    for (uint32_t i = 0; i < n; ++i) geom[i] = make_float4(spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], 0.f);
+    *pattern = table_share(geom.data(), n);
+    return 0;
+}
 
 // Numerics self-test: runs device helper `op` (0 sqrt_fix, 2 sqrt_exact, 3 rcp_exact, 10 sqrt_rsq,
 // 4 double division by w, 5/6 sin/cos(2*pi*x), 7 rng_draw(bits(x))) over n host floats.

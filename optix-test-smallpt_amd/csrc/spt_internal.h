@@ -25,7 +25,8 @@ int  spt_set_tuning(spt_ctx* ctx, uint32_t blocks_per_cu, uint32_t variant);
  * batches of >= 32 while the walkers starve, 4 walk iterations behind a batch's loads).  Results never depend on these. */
 int  spt_set_grid_pools(spt_ctx* ctx, int lane_owned, uint32_t slots, uint32_t ready, uint32_t drain, uint32_t min_batch, uint32_t walk_iters);
 /* Pool kernel: bit 13 = hand the task chunks out in their static order (no cost-ordered dispatch, spt_kernel.h KParams::chunk_order; the
- * grid kernel reads bits 15:13 as its workgroup size). */
+ * grid kernel reads bits 15:13 as its workgroup size).  Bit 14 = the generic closest hit: no sharing pattern (csrc/spt_share.h) even
+ * where the table matches one (A/B; the grid kernel reads it as part of bits 15:13). */
 /* Pool kernel, cost-ordered dispatch: copies the chunk order that the last pool launch left for the next launch of the same view
  * (a permutation of 0 .. nchunks - 1, most expensive chunk first) to `order` (room for `cap` words).  *nchunks = 0 when that
  * launch recorded none (a few samples per cell, tuning bit 13, another kernel).  Synchronises with the device. */
@@ -43,7 +44,8 @@ int  spt_set_watchdog(spt_ctx* ctx, double seconds);
  * paths (spt_grid.hip), 5 = grid kernel with wave-private path pools (spt_gpool.hip), 8 = mesh kernel over an instanced scene (spt_set_instances).
  * After a grid launch spt_diag returns out24[0..1] = cell steps / sphere tests of the walks, [2..3] = wave iterations of either kind,
  * [4] = rays that took the exhaustive loop, [5] = rounds, [7] = shaded hits.
- * After a pool launch spt_diag returns out24[0..2] = batches per class (GEN, DIFF, REFR), [3..5] = lanes per class. */
+ * After a pool launch spt_diag returns out24[0..2] = batches per class (GEN, DIFF, REFR), [3..5] = lanes per class, [23] = the sharing
+ * pattern its closest hit ran (csrc/spt_share.h: 0 = generic, 1 = box prefix, 2 = Cornell-9). */
 int  spt_last_kernel(spt_ctx* ctx);
 
 /* Numerics self-test of the kernel's exact-math helpers (host arrays in/out, n elements):
@@ -77,6 +79,11 @@ int  spt_selftest_sphere_bvh(const spt_sphere* spheres, uint32_t n, uint32_t* ou
  * meets, that references are ascending and in range and that the ray test admits every origin inside the box.
  * out8 = {dim x, dim y, dim z, references, always-tested spheres, table bytes, usable, most references in one cell}; 0 = valid, 2 = not usable / invalid, 1 = builder error. */
 int  spt_selftest_sphere_grid(const spt_sphere* spheres, uint32_t n, uint32_t cells_per_sphere, uint32_t* out8, char* why, uint32_t why_len);
+
+/* Host-only: the sharing pattern of the pool kernel's closest hit that spt_set_scene would choose for this table (csrc/spt_share.h;
+ * 0 = generic, 1 = box prefix, 2 = Cornell-9), the same function on the same padded table.  The pattern runs where the default pool size
+ * does and tuning bit 14 is clear.  Returns 0, 1 = bad arguments. */
+int  spt_selftest_share(const spt_sphere* spheres, uint32_t n, int* pattern);
 
 /* spt_trace_spheres*: what the last query of this context ran through -- 0 = the exhaustive loop, 1 = the uniform grid, 2 = the sphere
  * hierarchy, -1 = no query yet -- and, in *fallback_rays (may be NULL), how many of its rays the grid or the hierarchy handed to the exhaustive

@@ -30,6 +30,7 @@
 //     arithmetic expression are those of spt_kernel.hip / the oracle: results are bit-identical.
 #include "spt_device.h"
 #include "spt_kernel.h"
+#include "spt_share.h"
 
 namespace spt {
 
@@ -47,6 +48,7 @@ constexpr int kMaxUnroll = 24;                                   // spheres hand
 #endif
 constexpr bool kTaskLds = SPT_POOL_TASK_LDS != 0;
 constexpr int kSlotBytes = kTaskLds ? 70 : 62;                   // LDS per pool slot (layout in poolkernel)
+constexpr int kSharePool = kTaskLds ? 144 : 160;                 // the default pool size: the only one compiled with sharing patterns
 
 __device__ __forceinline__ uint32_t lane_id_p() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ uint32_t rank_in(unsigned long long m)
@@ -73,7 +75,8 @@ enum { C_GEN = 0, C_DIFF = 1, C_REFR = 2 };
 
 // EP: empty, or EParams for the environment variant: E is staged in one LDS entry behind the material table and read on a miss only
 // (the bounce loop's constants come from the kernel-argument segment; E is not kept in scalar registers across it)
-template <int P, int NG, typename... EP>
+// SH: sharing pattern of the wide closest hit (spt_share.h; kShareNone = the generic test)
+template <int P, int NG, int SH, typename... EP>
 __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const EP... env)
 {
     constexpr bool ENV = kHasEnv<EP...>;
@@ -468,23 +471,57 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
             // nearest distances (:61 strict <).
             uint32_t nk[3 * NG + 1];
             nk[0] = kInfKeyP;
+            // SH: the sharing pattern (spt_share.h).  Where src[i][k] != i, op_k, op_k d_k and op_k^2 of sphere i are those of sphere
+            // src[i][k] -- the same IEEE operations on the same operands, held in registers -- and where srcxy[i] != i the x + y
+            // partial sums of both dots are those of sphere srcxy[i]; the dots stay left to right.  SH = kShareNone is the generic test.
+            constexpr Share S = ShareOf<SH>::value;
+            float opk[3 * NG][3], pd[3 * NG][3], pp[3 * NG][3], sd_xy[3 * NG], sp_xy[3 * NG];
             // the wave-uniform (broadcast) LDS reads of up to nine spheres are issued together ahead of their arithmetic
 #pragma unroll
             for (int base = 0; base < 3 * NG; base += 9) {
                 float4 g[9];
 #pragma unroll
-                for (int j = 0; j < 9; ++j)
-                    if (base + j < 3 * NG) g[j] = s_geom[base + j];
+                for (int j = 0; j < 9; ++j) {
+                    // (shared: a record stays one ds_read_b128 although some of its components go unused -- split reads cost
+                    // address arithmetic and scalar registers; volatile keeps the compiler from narrowing it)
+                    if constexpr (SH == kShareNone) { if (base + j < 3 * NG) g[j] = s_geom[base + j]; }
+                    else if (base + j < 3 * NG) {
+                        typedef float v4f __attribute__((ext_vector_type(4)));
+                        typedef __attribute__((address_space(3))) const volatile v4f* LdsV4;
+                        const v4f v = *(LdsV4)(&s_geom[base + j]);
+                        g[j] = make_float4(v.x, v.y, v.z, v.w);
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < 9; ++j) {
-                    if (base + j < 3 * NG) {
+                    const int i = base + j;
+                    if (i < 3 * NG && SH == kShareNone) {
                         const f3 op = mk(g[j].x - o.x, g[j].y - o.y, g[j].z - o.z);         // :132
                         const float bb = dot(op, d);                                        // :133
                         const float det = bb * bb - dot(op, op) + g[j].w;                   // :133 (g.w = r*r)
                         const float sd = sqrt_rsq(det);                                 // :134
                         const uint32_t key1 = __float_as_uint(bb - sd) - kEpsBias;          // :135
                         const uint32_t key2 = __float_as_uint(bb + sd) - kEpsBias;
-                        nk[base + j + 1] = umin3(nk[base + j], key1, key2);
+                        nk[i + 1] = umin3(nk[i], key1, key2);
+                    } else if (i < 3 * NG) {
+                        const float4 gj = g[j];
+                        const float ok[3] = {o.x, o.y, o.z}, dk[3] = {d.x, d.y, d.z}, ck[3] = {gj.x, gj.y, gj.z};
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            if (S.src[i][k] == i) {
+                                opk[i][k] = ck[k] - ok[k];                                  // :132
+                                pd[i][k] = opk[i][k] * dk[k];
+                                pp[i][k] = opk[i][k] * opk[i][k];
+                            }
+                        }
+                        const int ix = S.src[i][0], iy = S.src[i][1], iz = S.src[i][2], ixy = S.srcxy[i];
+                        if (ixy == i) { sd_xy[i] = pd[ix][0] + pd[iy][1]; sp_xy[i] = pp[ix][0] + pp[iy][1]; }
+                        const float bb = sd_xy[ixy] + pd[iz][2];                            // :133 dot(op, d)
+                        const float det = bb * bb - (sp_xy[ixy] + pp[iz][2]) + gj.w;        // :133 dot(op, op)
+                        const float sd = sqrt_rsq(det);                                 // :134
+                        const uint32_t key1 = __float_as_uint(bb - sd) - kEpsBias;          // :135
+                        const uint32_t key2 = __float_as_uint(bb + sd) - kEpsBias;
+                        nk[i + 1] = umin3(nk[i], key1, key2);
                     }
                 }
             }
@@ -671,37 +708,52 @@ extern "C" size_t spt_pool_state_bytes(uint32_t blocks, int pool) { return (size
 
 extern "C" int spt_pool_max_spheres(void) { return spt::kMaxUnroll; }
 // 160 slots per wave with the 62-byte slot, 144 with the 70-byte slot: four workgroups (16 waves) per CU either way
-extern "C" int spt_pool_default_slots(void) { return spt::kTaskLds ? 144 : 160; }
+extern "C" int spt_pool_default_slots(void) { return spt::kSharePool; }
 
-template <int P, int NG>
+template <int P, int NG, int SH>
 static hipError_t launch_pool(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env)
 {
     if (env) {
         const spt::EParams E{{env[0], env[1], env[2]}};
         lds += 16u;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG, spt::EParams>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG, SH, spt::EParams>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((spt::poolkernel<P, NG, spt::EParams>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K, E);
+        hipLaunchKernelGGL((spt::poolkernel<P, NG, SH, spt::EParams>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K, E);
         return hipGetLastError();
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((spt::poolkernel<P, NG>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K);
+    hipLaunchKernelGGL((spt::poolkernel<P, NG, SH>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K);
     return hipGetLastError();
 }
 
+// Sharing patterns are compiled for the default pool size only (the other sizes are tuning A/B arms) and for the NG each pattern fits
+// (spt::share_compiled): the Cornell-9 pattern at NG = 3, the box prefix at NG >= 2.  The host chose `share` with spt::share_select.
+template <int P, int NG>
+static hipError_t launch_pool_share(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env, int share)
+{
+    if constexpr (P == spt::kSharePool) {
+        if constexpr (spt::share_compiled(spt::kShareCornell9, NG))
+            if (share == spt::kShareCornell9) return launch_pool<P, NG, spt::kShareCornell9>(K, blocks, lds, stream, env);
+        if constexpr (spt::share_compiled(spt::kShareBox, NG))
+            if (share == spt::kShareBox) return launch_pool<P, NG, spt::kShareBox>(K, blocks, lds, stream, env);
+    }
+    if (share != spt::kShareNone) return hipErrorInvalidValue;
+    return launch_pool<P, NG, spt::kShareNone>(K, blocks, lds, stream, env);
+}
+
 template <int P>
-static hipError_t launch_pool_ng(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env)
+static hipError_t launch_pool_ng(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env, int share)
 {
     switch (K->n == 0 ? 1u : (K->n + 2u) / 3u) {
-    case 1: return launch_pool<P, 1>(K, blocks, lds, stream, env);
-    case 2: return launch_pool<P, 2>(K, blocks, lds, stream, env);
-    case 3: return launch_pool<P, 3>(K, blocks, lds, stream, env);
-    case 4: return launch_pool<P, 4>(K, blocks, lds, stream, env);
-    case 5: return launch_pool<P, 5>(K, blocks, lds, stream, env);
-    case 6: return launch_pool<P, 6>(K, blocks, lds, stream, env);
-    case 7: return launch_pool<P, 7>(K, blocks, lds, stream, env);
-    case 8: return launch_pool<P, 8>(K, blocks, lds, stream, env);
+    case 1: return launch_pool_share<P, 1>(K, blocks, lds, stream, env, share);
+    case 2: return launch_pool_share<P, 2>(K, blocks, lds, stream, env, share);
+    case 3: return launch_pool_share<P, 3>(K, blocks, lds, stream, env, share);
+    case 4: return launch_pool_share<P, 4>(K, blocks, lds, stream, env, share);
+    case 5: return launch_pool_share<P, 5>(K, blocks, lds, stream, env, share);
+    case 6: return launch_pool_share<P, 6>(K, blocks, lds, stream, env, share);
+    case 7: return launch_pool_share<P, 7>(K, blocks, lds, stream, env, share);
+    case 8: return launch_pool_share<P, 8>(K, blocks, lds, stream, env, share);
     default: return hipErrorInvalidValue;
     }
 }
@@ -715,15 +767,22 @@ extern "C" int spt_pool_has_size(int pool)
     return pool == 128 || pool == 144 || pool == 160;
 }
 
-extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env)
+// the sharing pattern a launch with this pool size and table size can use (spt::kShareNone: the generic kernel only)
+extern "C" int spt_pool_share_compiled(int pool, uint32_t n, int share)
+{
+    const int ng = n == 0 ? 1 : (int)((n + 2u) / 3u);
+    return share == spt::kShareNone || (pool == spt::kSharePool && spt::share_compiled(share, ng));
+}
+
+extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env, int share)
 {
     const size_t lds = spt_pool_lds_bytes(K->n, pool);
-    if (pool == 128) return launch_pool_ng<128>(K, blocks, lds, stream, env);
-    if (pool == 160) return launch_pool_ng<160>(K, blocks, lds, stream, env);
-    if (pool == 144) return launch_pool_ng<144>(K, blocks, lds, stream, env);
+    if (pool == 128) return launch_pool_ng<128>(K, blocks, lds, stream, env, share);
+    if (pool == 160) return launch_pool_ng<160>(K, blocks, lds, stream, env, share);
+    if (pool == 144) return launch_pool_ng<144>(K, blocks, lds, stream, env, share);
 #ifdef SPT_POOL_SIZES
-    if (pool == 96) return launch_pool_ng<96>(K, blocks, lds, stream, env);
-    if (pool == 192) return launch_pool_ng<192>(K, blocks, lds, stream, env);
+    if (pool == 96) return launch_pool_ng<96>(K, blocks, lds, stream, env, share);
+    if (pool == 192) return launch_pool_ng<192>(K, blocks, lds, stream, env, share);
 #endif
     return hipErrorInvalidValue;
 }
