@@ -302,7 +302,10 @@ _Static_assert(sizeof(spt_instance) == 56, "spt_instance: FLOAT4x3 + model index
  *     its rule to the sum over instances of the model's triangle count.  The cost per ray is linear in the instance count.
  *   Anchor: each mesh its own model, identity instances i -> model i and the same materials give every query, render, progressive frame
  *     and AOV bit-identical to spt_set_meshes(meshes, materials), in every accel mode.  (In SPT_ACCEL_BVH_FAST that is the mesh scene's exact
- *     answer: its plain hierarchy may differ on rays in a triangle's plane, see above; the instanced scene has no such exception.) */
+ *     answer: its plain hierarchy may differ on rays in a triangle's plane, see above; the instanced scene has no such exception.)
+ *     Renders of any instances -- images and the statistics samples, bounces and max_depth_kills, through render, row bands, interleaved
+ *     bands and progressive frames, with or without spt_set_environment -- are bit-identical to the CPU oracle's statement of this contract,
+ *     orc_render_instances (oracle/smallpt_oracle.c), in every accel mode: tests/test_gpu_instance_renders.py. */
 int  spt_set_instances(spt_ctx* ctx, const spt_mesh* models, uint32_t nmodels, const spt_instance* instances, uint32_t ninst,
                        const spt_material* materials);
 /* Host-only: the inverse {W | w} that spt_set_instances uses (above), same 3x4 layout.  0 = ok, non-zero = rejected. */

@@ -268,6 +268,24 @@ static inline int intersect_mesh(const orc_mesh* m, f3 ro, f3 rd, float* dist, f
     return minIdx;
 }
 
+/* MeshHit{} (dist = inf, every other field 0). */
+static inline void miss_hit(orc_hit* hit)
+{
+    hit->dist = ORC_INF; hit->instId = 0; hit->triId = 0;
+    st(hit->x, mk(0, 0, 0)); st(hit->n, mk(0, 0, 0)); hit->uv[0] = hit->uv[1] = 0;
+}
+
+/* makeHit(instId, mesh, meshHit), scene.cpp:73-93, for triangle tri of m hit at dist with barycentrics (u, v). */
+static inline void make_mesh_hit(const orc_mesh* m, uint32_t inst, uint32_t tri, float dist, float nu, float nv, orc_hit* hit)
+{
+    const float w = 1.f - nu - nv;                                             /* scene.cpp:82 */
+    const uint32_t i1 = m->indices[3 * tri], i2 = m->indices[3 * tri + 1], i3 = m->indices[3 * tri + 2];   /* :84-86 */
+    hit->dist = dist; hit->instId = inst; hit->triId = tri;                    /* :76-78 */
+    st(hit->x, add(add(scl(ld(m->positions + 3 * i1), w), scl(ld(m->positions + 3 * i2), nu)), scl(ld(m->positions + 3 * i3), nv)));   /* :88 */
+    st(hit->n, add(add(scl(ld(m->normals + 3 * i1), w), scl(ld(m->normals + 3 * i2), nu)), scl(ld(m->normals + 3 * i3), nv)));       /* :89 */
+    hit->uv[0] = nu; hit->uv[1] = nv;                                          /* :90 */
+}
+
 /* CPUIntersector::intersect (smallpt.cpp:443-458) + makeHit(instId, mesh, meshHit) (scene.cpp:73-93): nearest mesh hit
  * over the instances in order, strict '<'; x and n interpolated as w*A + u*B + v*C with w = 1 - u - v (the reference's
  * barycentric convention, smallpt.cpp:544-546); n is NOT normalised (scene.cpp:90).  A triangle hit at dist >= inf
@@ -284,16 +302,8 @@ static inline int intersect_meshes(const orc_mesh* meshes, uint32_t nmesh, f3 ro
             nearest = t; inst = (int)i; tri = k; nu = u; nv = v;               /* :450-451 */
         }
     }
-    hit->dist = ORC_INF; hit->instId = 0; hit->triId = 0;
-    st(hit->x, mk(0, 0, 0)); st(hit->n, mk(0, 0, 0)); hit->uv[0] = hit->uv[1] = 0;
-    if (nearest == ORC_INF) return -1;                                         /* :454-455 */
-    const orc_mesh* m = &meshes[inst];
-    const float w = 1.f - nu - nv;                                             /* scene.cpp:82 */
-    const uint32_t i1 = m->indices[3 * tri], i2 = m->indices[3 * tri + 1], i3 = m->indices[3 * tri + 2];   /* :84-86 */
-    hit->dist = nearest; hit->instId = (uint32_t)inst; hit->triId = (uint32_t)tri;   /* :76-78 */
-    st(hit->x, add(add(scl(ld(m->positions + 3 * i1), w), scl(ld(m->positions + 3 * i2), nu)), scl(ld(m->positions + 3 * i3), nv)));   /* :88 */
-    st(hit->n, add(add(scl(ld(m->normals + 3 * i1), w), scl(ld(m->normals + 3 * i2), nu)), scl(ld(m->normals + 3 * i3), nv)));       /* :89 */
-    hit->uv[0] = nu; hit->uv[1] = nv;                                          /* :90 */
+    if (nearest == ORC_INF) { miss_hit(hit); return -1; }                      /* :454-455 */
+    make_mesh_hit(&meshes[inst], (uint32_t)inst, (uint32_t)tri, nearest, nu, nv, hit);
     return inst;
 }
 
@@ -305,6 +315,140 @@ void orc_trace_rays(const orc_mesh* meshes, uint32_t nmesh, const orc_ray* rays,
 #endif
     for (int64_t i = 0; i < (int64_t)n; ++i)
         intersect_meshes(meshes, nmesh, ld(rays[i].o), ld(rays[i].d), &hits[i]);
+}
+
+/* ---------------------------------------------------------------- mesh instances ---------- */
+/* rtpModelSetInstances (smallpt.cpp:489-530) under the contract of spt_set_instances (include/smallpt_mi355x.h), restated:
+ * A = the instance's row-major 3x4 transform, x_world_i = A[i][0] x + A[i][1] y + A[i][2] z + A[i][3]. */
+typedef struct {
+    const orc_mesh* models;
+    const orc_instance* inst;
+    const float* winv;           /* ninst x 12: {W | w} of each instance */
+    const unsigned char* ident;  /* 1: the instance is the identity (ray and Hit untransformed) */
+    uint32_t ninst;
+} inst_scene;
+
+/* Identity: all 12 entries compare equal, as floats, to the identity (signed zeros are equal). */
+static int inst_is_identity(const float* a)
+{
+    int id = 1;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) id = id && a[4 * i + j] == (i == j ? 1.0f : 0.0f);
+    return id;
+}
+
+/* Inverse {W | w} in double: adj from the nine 2x2 cofactors (each a*b - c*d), det = (a00 adj00 + a01 adj10) + a02 adj20,
+ * Wd = adj / det, W = (float)Wd, w_i = (float)(-((Wd[i][0] a03 + Wd[i][1] a13) + Wd[i][2] a23)).  Rejected (1) when an entry of A is not
+ * finite, det == 0 or an entry of {W | w} is not finite in float. */
+int orc_instance_inverse(const float af[12], float out[12])
+{
+    double a[3][4], adj[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) {
+            if (!isfinite(af[4 * i + j])) return 1;
+            a[i][j] = (double)af[4 * i + j];
+        }
+    adj[0][0] = a[1][1] * a[2][2] - a[1][2] * a[2][1];
+    adj[0][1] = a[0][2] * a[2][1] - a[0][1] * a[2][2];
+    adj[0][2] = a[0][1] * a[1][2] - a[0][2] * a[1][1];
+    adj[1][0] = a[1][2] * a[2][0] - a[1][0] * a[2][2];
+    adj[1][1] = a[0][0] * a[2][2] - a[0][2] * a[2][0];
+    adj[1][2] = a[0][2] * a[1][0] - a[0][0] * a[1][2];
+    adj[2][0] = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+    adj[2][1] = a[0][1] * a[2][0] - a[0][0] * a[2][1];
+    adj[2][2] = a[0][0] * a[1][1] - a[0][1] * a[1][0];
+    const double det = (a[0][0] * adj[0][0] + a[0][1] * adj[1][0]) + a[0][2] * adj[2][0];
+    if (det == 0.0) return 1;
+    int ok = 1;
+    for (int i = 0; i < 3; ++i) {
+        const double wd0 = adj[i][0] / det, wd1 = adj[i][1] / det, wd2 = adj[i][2] / det;
+        out[4 * i + 0] = (float)wd0; out[4 * i + 1] = (float)wd1; out[4 * i + 2] = (float)wd2;
+        out[4 * i + 3] = (float)(-((wd0 * a[0][3] + wd1 * a[1][3]) + wd2 * a[2][3]));
+        for (int j = 0; j < 4; ++j) ok = ok && isfinite(out[4 * i + j]);
+    }
+    return ok ? 0 : 1;
+}
+
+/* ((m[i][0] v.x + m[i][1] v.y) + m[i][2] v.z) (+ m[i][3]) per row i, float32: the object-space origin (m = {W | w}), direction (no
+ * translation) and the world-space hit point (m = A). */
+static inline f3 rows34(const float* m, f3 v, int translate)
+{
+    float r[3];
+    for (int i = 0; i < 3; ++i) {
+        r[i] = (m[4 * i] * v.x + m[4 * i + 1] * v.y) + m[4 * i + 2] * v.z;
+        if (translate) r[i] = r[i] + m[4 * i + 3];
+    }
+    return mk(r[0], r[1], r[2]);
+}
+
+/* World normal: n_i = (W[0][i] n.x + W[1][i] n.y) + W[2][i] n.z (W transposed; not normalised). */
+static inline f3 normal34(const float* w, f3 n)
+{
+    return mk((w[0] * n.x + w[4] * n.y) + w[8] * n.z, (w[1] * n.x + w[5] * n.y) + w[9] * n.z, (w[2] * n.x + w[6] * n.y) + w[10] * n.z);
+}
+
+/* Closest hit over every (instance, triangle): per instance the object-space ray meets the model's triangles as intersect_mesh does (the
+ * report's dist is that t), the smallest dist wins, the lowest instance among equal ones (strict '<'); the Hit is makeHit in the model's
+ * space with x mapped by A and n by W^T, instId = the instance, triId = the triangle within the model.  Returns the instance or -1. */
+static inline int intersect_instances(const inst_scene* s, f3 ro, f3 rd, orc_hit* hit)
+{
+    float nearest = ORC_INF;
+    int inst = -1, tri = -1;
+    float nu = 0, nv = 0;
+    for (uint32_t i = 0; i < s->ninst; ++i) {
+        const float* w = s->winv + 12 * (size_t)i;
+        const f3 o = s->ident[i] ? ro : rows34(w, ro, 1), d = s->ident[i] ? rd : rows34(w, rd, 0);
+        float t, u, v;
+        const int k = intersect_mesh(&s->models[s->inst[i].model], o, d, &t, &u, &v);
+        if (k >= 0 && t > 0.f && t < nearest) {
+            nearest = t; inst = (int)i; tri = k; nu = u; nv = v;
+        }
+    }
+    if (nearest == ORC_INF) { miss_hit(hit); return -1; }
+    make_mesh_hit(&s->models[s->inst[inst].model], (uint32_t)inst, (uint32_t)tri, nearest, nu, nv, hit);
+    if (!s->ident[inst]) {
+        const float* w = s->winv + 12 * (size_t)inst;
+        st(hit->x, rows34(s->inst[inst].transform, ld(hit->x), 1));
+        st(hit->n, normal34(w, ld(hit->n)));
+    }
+    return inst;
+}
+
+/* Validates the instances (model < nmodels, accepted inverse) and fills s; the caller frees s->winv and s->ident (inst_release). */
+static int inst_prepare(const orc_mesh* models, uint32_t nmodels, const orc_instance* inst, uint32_t ninst, inst_scene* s)
+{
+    memset(s, 0, sizeof *s);
+    if (!models || !inst || ninst == 0) return 1;
+    float* winv = (float*)malloc(sizeof(float) * 12 * (size_t)ninst);
+    unsigned char* ident = (unsigned char*)malloc(ninst);
+    if (!winv || !ident) { free(winv); free(ident); return 1; }
+    for (uint32_t i = 0; i < ninst; ++i)
+        if (inst[i].model >= nmodels || orc_instance_inverse(inst[i].transform, winv + 12 * (size_t)i)) {
+            free(winv); free(ident); return 1;
+        } else {
+            ident[i] = (unsigned char)inst_is_identity(inst[i].transform);
+        }
+    s->models = models; s->inst = inst; s->winv = winv; s->ident = ident; s->ninst = ninst;
+    return 0;
+}
+
+static void inst_release(inst_scene* s)
+{
+    free((void*)s->winv); free((void*)s->ident);
+}
+
+int orc_trace_instances(const orc_mesh* models, uint32_t nmodels, const orc_instance* instances, uint32_t ninst,
+                        const orc_ray* rays, uint64_t n, orc_hit* hits)
+{
+    inst_scene s;
+    if (inst_prepare(models, nmodels, instances, ninst, &s)) return 1;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 16)
+#endif
+    for (int64_t i = 0; i < (int64_t)n; ++i)
+        intersect_instances(&s, ld(rays[i].o), ld(rays[i].d), &hits[i]);
+    inst_release(&s);
+    return 0;
 }
 
 /* ---------------------------------------------------------------- camera ------------------ */
@@ -391,6 +535,7 @@ typedef struct {
     const orc_mesh* meshes;      /* ... or a triangle-mesh scene (the reference's Intersector seam): one material per instance */
     const orc_material* mats;
     uint32_t nmesh;
+    const inst_scene* inst;      /* an instanced scene (meshes = its models, mats[instId]), else NULL */
     int zero_cut;
     uint64_t bounces;
     uint64_t depth_kills;
@@ -427,7 +572,7 @@ static void trace_sample(trace_ctx* tc, path_t cam_path, uint32_t k0, uint32_t k
             const orc_material* m;
             if (tc->meshes) {
                 orc_hit hit;
-                id = intersect_meshes(tc->meshes, tc->nmesh, p.o, p.d, &hit);
+                id = tc->inst ? intersect_instances(tc->inst, p.o, p.d, &hit) : intersect_meshes(tc->meshes, tc->nmesh, p.o, p.d, &hit);
                 if (id < 0) break;                             /* :168 */
                 hx = ld(hit.x); n = ld(hit.n);                 /* :172-173: the interpolated, un-normalised mesh normal */
                 mesh_mat = tc->mats[id];                       /* :170 materials[hit.instId] */
@@ -547,7 +692,7 @@ void orc_sample_blocks(uint32_t samps, uint32_t* nb, uint32_t* sb)
  * DFS pre-order) order; cell = ((B0 + B1) + B2) + ... in block order; pixel = ((c0 + c1) + c2) + c3.
  * (Up to 31 samples per cell there is one block: the classic per-subpixel accumulator of smallpt.) */
 static int render_scene(const orc_sphere* spheres, uint32_t n, const orc_mesh* meshes, uint32_t nmesh, const orc_material* mats,
-                        const orc_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                        const inst_scene* inst, const orc_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
                         uint32_t samps, uint64_t seed, uint32_t flags, int threads, float* out, orc_stats* stats);
 
 int orc_render(const orc_sphere* spheres, uint32_t n, const orc_camera* cam,
@@ -556,7 +701,7 @@ int orc_render(const orc_sphere* spheres, uint32_t n, const orc_camera* cam,
                float* out, orc_stats* stats)
 {
     if (!spheres && n) return 1;
-    return render_scene(spheres, n, NULL, 0, NULL, cam, w, h, row_begin, row_count, samps, seed, flags, threads, out, stats);
+    return render_scene(spheres, n, NULL, 0, NULL, NULL, cam, w, h, row_begin, row_count, samps, seed, flags, threads, out, stats);
 }
 
 /* The same render over a triangle-mesh scene: closest hit = CPUIntersector (smallpt.cpp:427-473), material = materials[instId]. */
@@ -566,11 +711,24 @@ int orc_render_meshes(const orc_mesh* meshes, uint32_t nmesh, const orc_material
 {
     static const orc_mesh none = {0, 0, 0, 0, 0};
     if (nmesh && (!meshes || !materials)) return 1;
-    return render_scene(NULL, 0, meshes ? meshes : &none, nmesh, materials, cam, w, h, row_begin, row_count, samps, seed, flags, threads, out, stats);
+    return render_scene(NULL, 0, meshes ? meshes : &none, nmesh, materials, NULL, cam, w, h, row_begin, row_count, samps, seed, flags, threads, out, stats);
+}
+
+/* The same render over an instanced mesh scene: closest hit = intersect_instances, material = materials[instId] (ninst materials). */
+int orc_render_instances(const orc_mesh* models, uint32_t nmodels, const orc_instance* instances, uint32_t ninst,
+                         const orc_material* materials, const orc_camera* cam,
+                         uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                         uint32_t samps, uint64_t seed, uint32_t flags, int threads, float* out, orc_stats* stats)
+{
+    inst_scene s;
+    if (!materials || inst_prepare(models, nmodels, instances, ninst, &s)) return 1;
+    const int rc = render_scene(NULL, 0, models, nmodels, materials, &s, cam, w, h, row_begin, row_count, samps, seed, flags, threads, out, stats);
+    inst_release(&s);
+    return rc;
 }
 
 static int render_scene(const orc_sphere* spheres, uint32_t n, const orc_mesh* meshes, uint32_t nmesh, const orc_material* mats,
-                        const orc_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                        const inst_scene* inst, const orc_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
                         uint32_t samps, uint64_t seed, uint32_t flags, int threads, float* out, orc_stats* stats)
 {
     if (!cam || !out || w == 0 || h == 0 || samps == 0) return 1;
@@ -592,7 +750,7 @@ static int render_scene(const orc_sphere* spheres, uint32_t n, const orc_mesh* m
 #endif
     for (int64_t pi = 0; pi < npix; ++pi) {
         trace_ctx tc;
-        tc.sph = spheres; tc.n = n; tc.meshes = meshes; tc.nmesh = nmesh; tc.mats = mats; tc.zero_cut = !(flags & ORC_FLAG_NO_ZERO_WEIGHT_CUT);
+        tc.sph = spheres; tc.n = n; tc.meshes = meshes; tc.nmesh = nmesh; tc.mats = mats; tc.inst = inst; tc.zero_cut = !(flags & ORC_FLAG_NO_ZERO_WEIGHT_CUT);
         tc.bounces = 0; tc.depth_kills = 0;
         const uint32_t r = (uint32_t)(pi / w);
         const uint32_t px = (uint32_t)(pi - (int64_t)r * w);                    /* :296 */

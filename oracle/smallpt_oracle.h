@@ -133,6 +133,23 @@ int orc_render_meshes(const orc_mesh* meshes, uint32_t nmesh, const orc_material
                       uint32_t samps_per_cell, uint64_t seed, uint32_t flags, int threads,
                       float* out, orc_stats* stats);
 
+/* --- mesh instances: the contract of spt_set_instances (include/smallpt_mi355x.h) restated --- */
+/* Same 56-byte layout as spt_instance: A = transform, row-major 3x4 (x_world_i = A[i][0] x + A[i][1] y + A[i][2] z + A[i][3]), the model. */
+typedef struct { float transform[12]; uint32_t model; uint32_t pad; } orc_instance;
+/* The inverse {W | w} in double, same layout; 0 = ok, 1 = rejected (an entry of A not finite, det == 0, an entry of {W | w} not finite). */
+int orc_instance_inverse(const float transform[12], float inverse[12]);
+/* Closest hit of n rays against the instanced scene: per instance the object-space ray (or the ray itself for an identity instance)
+ * against the model's triangles, smallest dist then lowest instance, Hit = makeHit with x by A and n by W^T (not normalised),
+ * instId = instance, triId = triangle of the model.  Returns 1 (nothing written) when an instance is rejected or names no model. */
+int orc_trace_instances(const orc_mesh* models, uint32_t nmodels, const orc_instance* instances, uint32_t ninst,
+                        const orc_ray* rays, uint64_t n, orc_hit* hits);
+/* orc_render_meshes over the instanced scene: materials[i] belongs to instance i (ninst materials). */
+int orc_render_instances(const orc_mesh* models, uint32_t nmodels, const orc_instance* instances, uint32_t ninst,
+                         const orc_material* materials, const orc_camera* cam,
+                         uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                         uint32_t samps_per_cell, uint64_t seed, uint32_t flags, int threads,
+                         float* out, orc_stats* stats);
+
 int orc_num_threads(void);
 
 #ifdef __cplusplus

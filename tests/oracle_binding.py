@@ -30,6 +30,7 @@ class OrcMaterial(C.Structure):
     _fields_ = [("emission", C.c_float * 3), ("color", C.c_float * 3), ("refl", C.c_int32), ("pad", C.c_uint32)]
 
 
+INSTANCE_DTYPE = np.dtype([("transform", "<f4", 12), ("model", "<u4"), ("pad", "<u4")])    # orc_instance = spt_instance, 56 bytes
 HIT_DTYPE = np.dtype([("dist", "<f4"), ("instId", "<u4"), ("triId", "<u4"), ("x", "<f4", 3), ("n", "<f4", 3), ("uv", "<f4", 2)])
 
 FLAG_NORMALISE = 1
@@ -71,6 +72,11 @@ def lib():
         L.orc_trace_rays.argtypes = [C.POINTER(OrcMesh), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
         L.orc_render_meshes.argtypes = [C.POINTER(OrcMesh), C.c_uint32, C.POINTER(OrcMaterial), C.POINTER(OrcCamera), C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(OrcStats)]
+        L.orc_instance_inverse.argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_trace_instances.argtypes = [C.POINTER(OrcMesh), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.orc_render_instances.argtypes = [C.POINTER(OrcMesh), C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(OrcMaterial), C.POINTER(OrcCamera),
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
+                                           C.POINTER(OrcStats)]
         _lib = L
     return _lib
 
@@ -123,17 +129,19 @@ def make_sphere_trimesh(origin, radius, subdiv=32):
     return pos, nor, idx
 
 
-def _mesh_args(meshes, materials):
+def _mesh_args(meshes, materials, geometry=True):
     ms = (OrcMesh * max(1, len(meshes)))()
     mats = (OrcMaterial * max(1, len(meshes)))()
     keep = []
     for i, (m, (e, col, refl)) in enumerate(zip(meshes, materials)):
+        mats[i].emission = f3(*[float(v) for v in e]); mats[i].color = f3(*[float(v) for v in col]); mats[i].refl = int(refl)
+        if not geometry:
+            continue
         p = np.ascontiguousarray(m.positions, dtype=np.float32); nn = np.ascontiguousarray(m.normals, dtype=np.float32)
         ix = np.ascontiguousarray(m.indices, dtype=np.uint32)
         keep += [p, nn, ix]
         ms[i].positions, ms[i].normals, ms[i].indices = p.ctypes.data, nn.ctypes.data, ix.ctypes.data
         ms[i].nverts, ms[i].ntris = len(p.reshape(-1, 3)), len(ix.reshape(-1, 3))
-        mats[i].emission = f3(*[float(v) for v in e]); mats[i].color = f3(*[float(v) for v in col]); mats[i].refl = int(refl)
     return ms, mats, keep
 
 
@@ -158,4 +166,54 @@ def render_meshes(meshes, materials, w, h, samps, seed=0, normalise=False, row_b
                                  FLAG_NORMALISE if normalise else 0, threads, out.ctypes.data, C.byref(st))
     if rc:
         raise RuntimeError(f"orc_render_meshes failed rc={rc}")
+    return out, {"samples": int(st.samples), "bounces": int(st.bounces), "max_depth_kills": int(st.max_depth_kills)}
+
+
+# ---- mesh instances (the contract of spt_set_instances restated in the oracle) ----
+def _instances(instances):
+    """INSTANCE_DTYPE[n] from any array with fields transform ((n, 12) or (n, 3, 4)) and model (e.g. the product's INSTANCE_DTYPE)."""
+    out = np.zeros(len(instances), dtype=INSTANCE_DTYPE)
+    out["transform"] = np.asarray(instances["transform"], dtype=np.float32).reshape(-1, 12)
+    out["model"] = np.asarray(instances["model"], dtype=np.uint32)
+    return out
+
+
+def instance_inverse(transform):
+    """(rc, {W | w} as 12 float32) of orc_instance_inverse; rc != 0 = rejected."""
+    a = np.ascontiguousarray(transform, dtype=np.float32).reshape(12)
+    out = np.zeros(12, dtype=np.float32)
+    rc = lib().orc_instance_inverse(a.ctypes.data, out.ctypes.data)
+    return rc, out
+
+
+def trace_instances(models, instances, rays):
+    """orc_trace_instances: HIT_DTYPE[n] for (n, 6) world rays."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    inst = _instances(instances)
+    ms, _, keep = _mesh_args(models, [((0, 0, 0), (0, 0, 0), 0)] * len(models))
+    hits = np.zeros(len(rays), dtype=HIT_DTYPE)
+    rc = lib().orc_trace_instances(ms, len(models), inst.ctypes.data, len(inst), rays.ctypes.data, len(rays), hits.ctypes.data)
+    if rc:
+        raise RuntimeError(f"orc_trace_instances failed rc={rc}")
+    return hits
+
+
+def render_instances(models, instances, materials, w, h, samps, seed=0, normalise=False, row_begin=0, row_count=None, threads=0, camera=None):
+    """orc_render_instances (materials[i] = (emission, color, refl) of instance i); returns ((rows, w, 3) float32, stats dict)."""
+    if row_count is None:
+        row_count = h - row_begin
+    cam = camera if camera is not None else camera_smallpt(w, h)
+    if not isinstance(cam, OrcCamera):
+        cam = camera_from(cam)
+    inst = _instances(instances)
+    if len(materials) != len(inst):
+        raise ValueError("render_instances: one material per instance")
+    ms, _, keep = _mesh_args(models, [((0, 0, 0), (0, 0, 0), 0)] * len(models))
+    _, mats, _ = _mesh_args([None] * len(materials), materials, geometry=False)
+    out = np.zeros((row_count, w, 3), dtype=np.float32)
+    st = OrcStats()
+    rc = lib().orc_render_instances(ms, len(models), inst.ctypes.data, len(inst), mats, C.byref(cam), w, h, row_begin, row_count, samps, seed,
+                                    FLAG_NORMALISE if normalise else 0, threads, out.ctypes.data, C.byref(st))
+    if rc:
+        raise RuntimeError(f"orc_render_instances failed rc={rc}")
     return out, {"samples": int(st.samples), "bounces": int(st.bounces), "max_depth_kills": int(st.max_depth_kills)}

@@ -6,8 +6,9 @@
   * Non-identity instances (rotated, translated, mirrored, sheared, overlapping, duplicated): queries and AOVs equal tests/instance_expected.py
     bit for bit in every accel mode, on >= 100k random rays plus rays in transformed triangles' planes, through shared edges and along
     the pole needles' lines; range peeling visits every report in order; occlusion flips exactly at the closest hit's dist.
-  * Renders of non-identity instances have no exact CPU statement: they are deterministic, a row band equals its rows of the full image, and
-    the image means agree with the host-flattened scene within 4 standard errors (estimated from independent seeds).
+  * Renders of non-identity instances are pinned bit for bit (image, samples, bounces, max_depth_kills) to the oracle's instanced render,
+    orc_render_instances, in tests/test_gpu_instance_renders.py.  Here: they are deterministic, a row band equals its rows of the full
+    image, and the image means agree with the host-flattened scene within 4 standard errors (estimated from independent seeds).
   * Rejected calls leave the previous scene current; switching away gives what a fresh context gives."""
 import ctypes as C
 
@@ -299,7 +300,7 @@ def test_nonidentity_aov_equals_statement(pkg, mode):
 def test_nonidentity_renders_deterministic_banded_and_unbiased(pkg):
     """Same seed twice -> the same bits; a row band -> the same rows of the full image; the image means of the instanced scene and of the
     same scene flattened on the host (a different triangle set to rounding, hence not bit-comparable) agree within 4 standard errors of their
-    difference, each estimated from 6 independent seeds at 256 spp."""
+    difference, each estimated from 6 independent seeds at 64 samples per jitter cell (256 spp)."""
     import torch
     models, inst, mats, flat, _, _ = _nonidentity_case(pkg)
     cam = pkg.pinhole_camera(org=(0, 0, 3))
