@@ -174,10 +174,14 @@ int  spt_set_meshes(spt_ctx* ctx, const spt_mesh* meshes, uint32_t nmesh, const 
  *     towards the exhaustive loop's cost (the error bound grows with the distance), never in result.
  *   SPT_ACCEL_EXHAUSTIVE: every triangle of every instance is tested, as CPUIntersector::intersect does (smallpt.cpp:443-458 over
  *     scene.cpp:95-116): the parity anchor.
- *   SPT_ACCEL_BVH_FAST (opt-in): the bounding-volume hierarchy alone, as in rounds 2-3 -- 1.05 ms for the pinhole frame above.  It
- *     returns the exhaustive Hit whenever the winning triangle's padded box is crossed within the current nearest distance; a ray
- *     lying (to ~1e-7 rad) in a triangle's plane, or crossing a needle's supporting line, may lose the noise "hit" the reference's
- *     arithmetic reports there.  Rendered images have never met the condition (tests compare them), constructed rays do.
+ *   SPT_ACCEL_BVH_FAST (opt-in): the bounding-volume hierarchy without the per-ray inflation and without the plane tree, plus the
+ *     table (or tree) of the thin triangles' lines, which hold every thin triangle (1 / sine of the angle at v0 above 32: needles and
+ *     slivers of any area) -- 1.05 ms for the pinhole frame above.  It returns the exhaustive Hit whenever the winner is a thin
+ *     triangle, or a regular one whose report lies inside its build-time padded box.  A report's error grows as the ray nears the
+ *     triangle's plane (csrc/spt_tribvh.h (1), (2)), so the exceptions are rays lying (nearly) in a REGULAR triangle's plane: they may
+ *     lose the noise "hit" the reference's arithmetic reports there.  Every difference the CPU harness and the GPU tests have met is
+ *     within tau = 2^-13 g of that plane (g = 1 / sine of the angle at v0, <= 32).  Rays along needles' and slivers' lines are exact.
+ *     Rendered images have never met the condition (tests compare them), constructed rays do.
  * Applies to spt_trace_rays and to spt_render* / spt_progressive_* of a mesh scene; may be changed at any time. */
 #define SPT_ACCEL_EXHAUSTIVE 0
 #define SPT_ACCEL_BVH        1

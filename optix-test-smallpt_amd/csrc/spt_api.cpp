@@ -1028,12 +1028,13 @@ static spt::MParams mesh_params(const spt_ctx* c, int mode)
     M.strips = c->mesh_specular ? 0u : 1u;
     if (mode != SPT_ACCEL_EXHAUSTIVE && c->bvh_ready) {
         M.bvh_nodes = c->d_bvh_nodes; M.bvh_tris = c->d_bvh_tris; M.bvh_index = c->d_bvh_index;
-        if (mode == SPT_ACCEL_BVH) {                           // (SPT_ACCEL_BVH_FAST: the spatial tree alone, no cones)
+        if (mode == SPT_ACCEL_BVH) {                           // (SPT_ACCEL_BVH_FAST: no cones, no plane tree)
             M.bvh_cones = c->d_bvh_cones;
             if (c->have_planes) M.plane_nodes = c->d_plane_nodes;
-            if (c->have_lines) M.line_nodes = c->d_line_nodes;
-            if (c->bvh_flat) { M.flat_lines = c->d_flat_lines; M.flat_line_index = c->d_flat_line_index; M.nline_slots = c->nline_slots; }
         }
+        // the thin triangles are in no spatial tree (spt_tribvh.h (3)): both modes scan / walk their lines
+        if (c->have_lines) M.line_nodes = c->d_line_nodes;
+        if (c->bvh_flat) { M.flat_lines = c->d_flat_lines; M.flat_line_index = c->d_flat_line_index; M.nline_slots = c->nline_slots; }
     }
     return M;
 }

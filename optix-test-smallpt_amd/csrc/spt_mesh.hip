@@ -18,7 +18,8 @@
 //   * SPT_ACCEL_BVH (the default of mesh scenes since round 4; spt_bvh.h, spt_tribvh.h): the same query through structures that provably reach
 //     every triangle whose report beats or ties the answer -- same triIntersect arithmetic on the triangles they reach, same selection rule
 //     (smallest t > 0, lowest global index among equal t) --: the stand-in for the OptiX Prime traversal of smallpt.cpp:475-603, and the
-//     exhaustive loop's Hit for every ray.  SPT_ACCEL_BVH_FAST: the spatial hierarchy alone.
+//     exhaustive loop's Hit for every ray.  SPT_ACCEL_BVH_FAST: the plain spatial hierarchy (no per-ray inflation, no plane tree) and the
+//     thin triangles' line table / tree: the exhaustive Hit except for rays lying (nearly) in a regular triangle's plane (spt_tribvh.h (2)).
 #include "spt_device.h"
 #include "spt_kernel.h"
 #define SPT_GRID_DEVICE_ONLY
@@ -191,12 +192,13 @@ __device__ __forceinline__ uint32_t closest_triangle_bvh(const MParams& M, uint3
             for (uint32_t k = 0; k < cnt; ++k) consider(M.bvh_tris + 3 * (size_t)(first + k), M.bvh_index[first + k]);
         };
         auto by_index = [&](uint32_t g) { consider(M.tris + 3 * (size_t)g, g); };
-        if (!M.bvh_cones) {                                        // SPT_ACCEL_BVH_FAST: the plain hierarchy (documented exceptions)
+        typedef const __attribute__((address_space(4))) MParams* MArgs;
+        MArgs mc = (MArgs)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + KOFF);
+        if (!M.bvh_cones) {                                        // SPT_ACCEL_BVH_FAST: the plain hierarchy and the thin triangles' lines
             tri_walk_boxes<false>(M.bvh_nodes, nullptr, ro.x, ro.y, ro.z, ivx, ivy, ivz, q.h[0], q.h[1], q.h[2], tcut, st, leaf);
+            asm volatile("" : "+s"(mc));
         } else {
             tri_walk_boxes<true>(M.bvh_nodes, M.bvh_cones, ro.x, ro.y, ro.z, ivx, ivy, ivz, q.h[0], q.h[1], q.h[2], tcut, st, leaf);
-            typedef const __attribute__((address_space(4))) MParams* MArgs;
-            MArgs mc = (MArgs)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + KOFF);
             asm volatile("" : "+s"(mc));
             if (camera_ray) {                                      // the planes through the camera point are listed (spt_bvh.h camera_planes)
                 const uint32_t ncam = mc->ncam;
@@ -205,9 +207,10 @@ __device__ __forceinline__ uint32_t closest_triangle_bvh(const MParams& M, uint3
             } else if (mc->plane_nodes) {
                 tri_walk_planes(mc->plane_nodes, q, st, by_index);
             }
-            if (mc->flat_lines) tri_scan_lines(mc->flat_lines, mc->flat_line_index, mc->nline_slots, q, st, by_index);
-            else if (mc->line_nodes) tri_walk_lines(mc->line_nodes, q, st, by_index);
         }
+        // (3) in both modes: the spatial tree holds the regular triangles only (spt_bvh.cpp build_bvh), a thin one is found here or nowhere
+        if (mc->flat_lines) tri_scan_lines(mc->flat_lines, mc->flat_line_index, mc->nline_slots, q, st, by_index);
+        else if (mc->line_nodes) tri_walk_lines(mc->line_nodes, q, st, by_index);
     }
     t_out = __uint_as_float(near_key + 1u);
     return near_tri;

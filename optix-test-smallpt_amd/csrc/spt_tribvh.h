@@ -68,10 +68,18 @@
 //       |a.m| <= kappa |m| + lam + 32 u |dp|.
 //     The needles of a pole are a fan of lines through one point: a ray's moment picks two azimuths of it, the walk is logarithmic.
 //
-// Float evaluation of the node tests: rdh carries 2 u; a.w = a.dp - s (a.rdh), |w|^2 = |dp|^2 - s^2 and dp x rdh cancel to within
-// 6 u |dp| -- both sides of (B) carry 16 u |dp| (tau >= 2^-13 makes the 2.002 -> 2.004 of its |dp| term 2.4e-7 |dp| more), the line
-// test 32 u |dp| (8.1 u |dp| of which is the bound's).  The builder works in double and rounds kappa, sigma, lam, te up against the
-// float axes and points it stores.
+// Float evaluation of the node tests.  They are written as one expression tree in which every product-plus-sum meant to fuse is
+// SPT_TRI_FMA(a, b, c): __builtin_fmaf by default (hipcc and g++ alike: the device and the CPU harness evaluate the same roundings), a * b + c
+// under -DSPT_TRI_UNFUSED (one rounding per operation).  Dot products are fma(z, z', fma(x, x', y y')), cross-product components
+// fma(a, b, -(c d)).  The fused form rounds once where the unfused form rounds twice: it drops the rounding of the product and adds
+// none, so the first-order error of each quantity -- the sum over its operations of u |exact result| -- is at most the unfused one.
+// Terms that lose a rounding: in |dp|^2, |m|^2, a.rdh, a.dp, s, a.m and the moment components two of the three products each; in
+// a.w = a.dp - s (a.rdh) and |w|^2 = |dp|^2 - s^2 the product s (a.rdh), s^2 (the cancelling terms); the thresholds' kappa |w| + sigma,
+// tau (2.004) + 2^-20, kappa (...) + lam and 2^-19 |dp| + ...; the pad p of (1), which is never rounded (the slab face is
+// fma(-(D + e') kTriPadK, 1 / m, lo)).  The budgets below were derived for the unfused form and hold for both: rdh carries 2 u;
+// a.w, |w|^2 and dp x rdh cancel to within 6 u |dp| -- both sides of (B) carry 16 u |dp| (tau >= 2^-13 makes the 2.002 -> 2.004 of its
+// |dp| term 2.4e-7 |dp| more), the line test 32 u |dp| (8.1 u |dp| of which is the bound's).  The builder works in double and rounds
+// kappa, sigma, lam, te up against the float axes and points it stores.
 #ifndef SPT_TRIBVH_H
 #define SPT_TRIBVH_H
 #include <hip/hip_runtime.h>
@@ -83,12 +91,12 @@
 #define SPT_THD inline
 #endif
 
-// The node tests are not the reference's arithmetic (tri_test is, and lives elsewhere): they may contract a * b + c into one fused operation
-// -- fewer VALU instructions, smaller rounding error; the thresholds' slack covers either form (the CPU harness runs the unfused one).
-#if defined(__clang__)
-#define SPT_TRI_FUSE _Pragma("clang fp contract(fast)")
+// The node tests are not the reference's arithmetic (tri_test is, and lives elsewhere): the products-plus-sums written SPT_TRI_FMA fuse --
+// fewer VALU instructions, smaller rounding error; the thresholds' slack covers either form (see above; the CPU harness runs both).
+#if defined(SPT_TRI_UNFUSED)
+#define SPT_TRI_FMA(a, b, c) ((a) * (b) + (c))
 #else
-#define SPT_TRI_FUSE
+#define SPT_TRI_FMA(a, b, c) __builtin_fmaf((a), (b), (c))
 #endif
 
 namespace spt {
@@ -121,11 +129,13 @@ SPT_THD float tri_sqrt(float x)
     return __builtin_sqrtf(x);
 #endif
 }
+// x x' + y y' + z z' and a b - c d in the fused form (the trees the compiler built for the contracted node tests on gfx950)
+SPT_THD float tri_dot(float x, float y, float z, float x2, float y2, float z2) { return SPT_TRI_FMA(z, z2, SPT_TRI_FMA(x, x2, y * y2)); }
+SPT_THD float tri_dif(float a, float b, float c, float d) { return SPT_TRI_FMA(a, b, -(c * d)); }
 
 SPT_THD void tri_query(float ox, float oy, float oz, float dx, float dy, float dz, TriQuery& q)
 {
-    SPT_TRI_FUSE
-    const float inv = tri_rsq(dx * dx + dy * dy + dz * dz);
+    const float inv = tri_rsq(tri_dot(dx, dy, dz, dx, dy, dz));
     q.o[0] = ox; q.o[1] = oy; q.o[2] = oz;
     q.h[0] = dx * inv; q.h[1] = dy * inv; q.h[2] = dz * inv;
 }
@@ -136,16 +146,15 @@ SPT_THD void tri_query(float ox, float oy, float oz, float dx, float dy, float d
 // An empty child has kappa = -1e30.  Float evaluation: a.w = a.dp - s (a.rdh) and |w|^2 = |dp|^2 - s^2 cancel: both sides carry 16 u |dp|.
 SPT_THD bool tri_plane_child(const TriQuery& q, float ax, float ay, float az, float kappa, float px, float py, float pz, float sigma, float tau, float te)
 {
-    SPT_TRI_FUSE
-    const float ah = ax * q.h[0] + ay * q.h[1] + az * q.h[2];
+    const float ah = tri_dot(ax, ay, az, q.h[0], q.h[1], q.h[2]);
     const float dx = px - q.o[0], dy = py - q.o[1], dz = pz - q.o[2];
-    const float s = dx * q.h[0] + dy * q.h[1] + dz * q.h[2];
-    const float d2 = dx * dx + dy * dy + dz * dz;
-    const float aw = (ax * dx + ay * dy + az * dz) - s * ah;
-    const float w = tri_sqrt(__builtin_fmaxf(d2 - s * s, 0.0f) + 0x1p-20f * d2);
+    const float s = tri_dot(dx, dy, dz, q.h[0], q.h[1], q.h[2]);
+    const float d2 = tri_dot(dx, dy, dz, dx, dy, dz);
+    const float aw = SPT_TRI_FMA(-s, ah, tri_dot(ax, ay, az, dx, dy, dz));
+    const float w = tri_sqrt(SPT_TRI_FMA(0x1p-20f, d2, __builtin_fmaxf(SPT_TRI_FMA(-s, s, d2), 0.0f)));
     const float d = tri_sqrt(d2);
-    const bool A = __builtin_fabsf(ah) <= kappa + tau * (1.0f + 0x1p-10f) + 0x1p-20f;
-    const bool B = __builtin_fabsf(aw) <= kappa * w + sigma + (2.004f * tau + 0x1p-20f) * d + te;
+    const bool A = __builtin_fabsf(ah) <= SPT_TRI_FMA(tau, 1.0f + 0x1p-10f, kappa) + 0x1p-20f;
+    const bool B = __builtin_fabsf(aw) <= SPT_TRI_FMA(SPT_TRI_FMA(2.004f, tau, 0x1p-20f), d, SPT_TRI_FMA(kappa, w, sigma)) + te;
     return A & B;
 }
 
@@ -154,13 +163,12 @@ SPT_THD bool tri_plane_child(const TriQuery& q, float ax, float ay, float az, fl
 //   |a.m| <= kappa |m| + lam + 32 u |dp|        (8.1 u |dp| of the bound, the rest for the float cross product)
 SPT_THD bool tri_line_child(const TriQuery& q, float ax, float ay, float az, float kappa, float px, float py, float pz, float lam)
 {
-    SPT_TRI_FUSE
     const float dx = px - q.o[0], dy = py - q.o[1], dz = pz - q.o[2];
-    const float mx = dy * q.h[2] - dz * q.h[1], my = dz * q.h[0] - dx * q.h[2], mz = dx * q.h[1] - dy * q.h[0];
-    const float am = ax * mx + ay * my + az * mz;
-    const float m = tri_sqrt(mx * mx + my * my + mz * mz);
-    const float d = tri_sqrt(dx * dx + dy * dy + dz * dz);
-    return __builtin_fabsf(am) <= kappa * (m * 1.001f + 0x1p-19f * d) + lam + 0x1p-19f * d;
+    const float mx = tri_dif(dy, q.h[2], dz, q.h[1]), my = tri_dif(dz, q.h[0], dx, q.h[2]), mz = tri_dif(dx, q.h[1], dy, q.h[0]);
+    const float am = tri_dot(ax, ay, az, mx, my, mz);
+    const float m = tri_sqrt(tri_dot(mx, my, mz, mx, my, mz));
+    const float d = tri_sqrt(tri_dot(dx, dy, dz, dx, dy, dz));
+    return __builtin_fabsf(am) <= SPT_TRI_FMA(0x1p-19f, d, SPT_TRI_FMA(kappa, SPT_TRI_FMA(0x1p-19f, d, m * 1.001f), lam));
 }
 
 // (1): one child of the spatial hierarchy against the ray segment [0, tcut]: entry parameter in `tn`.  The box [lo, hi] - ro is given
@@ -171,24 +179,26 @@ template <bool EXACT>
 SPT_THD bool tri_box_child(float l0x, float l1x, float l0y, float l1y, float l0z, float l1z, float ivx, float ivy, float ivz, float tcut,
                            float hx, float hy, float hz, float ax, float ay, float az, float kappa, float iq, float ee, float& tn)
 {
-    SPT_TRI_FUSE
-    float p = 0.0f;
     if (EXACT) {
         const float mx = __builtin_fmaxf(__builtin_fabsf(l0x), __builtin_fabsf(l1x));
         const float my = __builtin_fmaxf(__builtin_fabsf(l0y), __builtin_fabsf(l1y));
         const float mz = __builtin_fmaxf(__builtin_fabsf(l0z), __builtin_fabsf(l1z));
-        const float dfar = tri_sqrt(mx * mx + my * my + mz * mz) * 1.001f;                 // D (1 ulp sqrt)
-        const float c = (__builtin_fabsf(ax * hx + ay * hy + az * hz) - kappa) * iq;       // every triangle inside: |nh.rdh| / g >= c
+        const float de = SPT_TRI_FMA(tri_sqrt(tri_dot(mx, my, mz, mx, my, mz)), 1.001f, ee);    // D + e' (D: 1 ulp sqrt)
+        const float c = (__builtin_fabsf(tri_dot(ax, ay, az, hx, hy, hz)) - kappa) * iq;       // every triangle inside: |nh.rdh| / g >= c
         const float m = __builtin_fmaxf(c, (float)kTriBand);
 #if defined(__HIP_DEVICE_COMPILE__)
-        p = (dfar + ee) * kTriPadK * __builtin_amdgcn_rcpf(m);
+        const float im = __builtin_amdgcn_rcpf(m);
 #else
-        p = (dfar + ee) * kTriPadK / m;
+        const float im = 1.0f / m;
 #endif
+        const float pk = de * kTriPadK;                                                         // pad = pk im, never rounded: fused into the faces
+        l0x = SPT_TRI_FMA(-pk, im, l0x); l1x = SPT_TRI_FMA(pk, im, l1x);
+        l0y = SPT_TRI_FMA(-pk, im, l0y); l1y = SPT_TRI_FMA(pk, im, l1y);
+        l0z = SPT_TRI_FMA(-pk, im, l0z); l1z = SPT_TRI_FMA(pk, im, l1z);
     }
-    const float x0 = (l0x - p) * ivx, x1 = (l1x + p) * ivx;
-    const float y0 = (l0y - p) * ivy, y1 = (l1y + p) * ivy;
-    const float z0 = (l0z - p) * ivz, z1 = (l1z + p) * ivz;
+    const float x0 = l0x * ivx, x1 = l1x * ivx;
+    const float y0 = l0y * ivy, y1 = l1y * ivy;
+    const float z0 = l0z * ivz, z1 = l1z * ivz;
     tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(x0, x1), __builtin_fminf(y0, y1)), __builtin_fminf(z0, z1));
     const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(x0, x1), __builtin_fmaxf(y0, y1)), __builtin_fmaxf(z0, z1));
     return (tf >= 0.0f) & (tn <= tf * 1.0001f) & (tn <= tcut);      // an empty child (inverted box) gives tn = +inf or NaN: never entered
@@ -299,7 +309,6 @@ typedef const float4 tri_flat_t;
 template <class Stack, class Cand>
 SPT_THD void tri_scan_lines(const float4* __restrict__ flat_, const uint32_t* __restrict__ index_, uint32_t nslots, const TriQuery& q, Stack& st, Cand&& cand)
 {
-    SPT_TRI_FUSE
     tri_flat_t* flat = (tri_flat_t*)flat_;
 #if defined(__HIP_DEVICE_COMPILE__)
     const __attribute__((address_space(4))) uint32_t* index = (const __attribute__((address_space(4))) uint32_t*)index_;
@@ -311,11 +320,11 @@ SPT_THD void tri_scan_lines(const float4* __restrict__ flat_, const uint32_t* __
         const float4 h = flat[i];
         const uint32_t cnt = __builtin_bit_cast(uint32_t, h.w);
         const float dx = h.x - q.o[0], dy = h.y - q.o[1], dz = h.z - q.o[2];
-        const float mx = dy * q.h[2] - dz * q.h[1], my = dz * q.h[0] - dx * q.h[2], mz = dx * q.h[1] - dy * q.h[0];
-        const float thr = 0x1p-19f * tri_sqrt(dx * dx + dy * dy + dz * dz);
+        const float mx = tri_dif(dy, q.h[2], dz, q.h[1]), my = tri_dif(dz, q.h[0], dx, q.h[2]), mz = tri_dif(dx, q.h[1], dy, q.h[0]);
+        const float thr = 0x1p-19f * tri_sqrt(tri_dot(dx, dy, dz, dx, dy, dz));
         for (uint32_t k = 1; k <= cnt; ++k) {
             const float4 e = flat[i + k];
-            if (__builtin_fabsf(e.x * mx + e.y * my + e.z * mz) <= e.w + thr) {
+            if (__builtin_fabsf(tri_dot(e.x, e.y, e.z, mx, my, mz)) <= e.w + thr) {
                 st.push(sp, index[i + k]);
                 if (++sp == 32u) { while (sp) { --sp; cand(st.pop(sp)); } }
             }

@@ -337,7 +337,8 @@ class Renderer:
     def set_mesh_accel(self, accel):
         """ACCEL_AUTO (default: the faster of the two exact modes per launch), ACCEL_BVH (the role of the reference's OptiX Prime model,
         smallpt.cpp:475-603; the exhaustive loop's Hit for every ray, include/smallpt_mi355x.h), ACCEL_EXHAUSTIVE (every triangle, the reference's CPU loops: the parity anchor) or
-        ACCEL_BVH_FAST (the plain hierarchy of rounds 2-3: several times faster, but rays lying in a triangle's plane to rounding may differ)."""
+        ACCEL_BVH_FAST (the plain hierarchy of rounds 2-3 and the thin triangles' lines: faster, but rays lying in a regular triangle's plane to
+        rounding may differ)."""
         self._check(self._lib.spt_set_mesh_accel(self._h, int(accel)))
         self._state["mesh_accel"] = int(accel)
         self._state_version += 1

@@ -3,8 +3,13 @@
 // (scene.cpp:95-116 over triIntersect :52-70, smallest t > 0, lowest index among equal t), on random rays and on the rays built to
 // break a hierarchy: in a triangle's plane (anywhere in it, also far from the triangle), tilted out of it by 2^-6 ... 2^-26,
 // along edges, through vertices, along the supporting lines of needles far beyond their tips, axis-parallel, from far away.
-// Compile with -ffp-contract=off (tri_test is the reference's arithmetic: one rounding per operation).  argv[1] = rays per family
-// (default 3000).  Prints the walks' cost beside the result.
+// Two walks: the exact one (SPT_ACCEL_BVH: 0 mismatches) and the fast one (SPT_ACCEL_BVH_FAST: the plain spatial tree and the thin
+// triangles' lines; every difference must be its documented exception -- the exhaustive winner is a regular triangle in whose plane the
+// ray lies, |nh.rdh| < kTriBand g, spt_tribvh.h (2) (A) evaluated in double).  Knobs that must make it fail: TRIBVH_NO_PLANES and
+// TRIBVH_NO_LINES (exact walk), TRIBVH_FAST_NO_LINES (fast walk).
+// Compile with -ffp-contract=off (tri_test is the reference's arithmetic: one rounding per operation); the node tests fuse where they
+// say so (SPT_TRI_FMA, the device's form) unless -DSPT_TRI_UNFUSED.  argv[1] = rays per family (default 3000).  Prints the walks' cost
+// beside the result.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -87,8 +92,10 @@ struct HostStack {
 struct Cost { double box_nodes = 0, plane_nodes = 0, line_nodes = 0, tests = 0, rays = 0; };
 
 // the closest hit through the three structures, exactly as closest_triangle_bvh of spt_mesh.hip composes them (cam_list: the ray is one
-// of a pinhole camera whose origin's planes are listed, spt_bvh.h camera_planes)
-void closest_bvh(const Scene& s, const spt::Bvh& bvh, V3 ro, V3 rd, uint32_t& near_key, uint32_t& near_tri, Cost& cost, const std::vector<uint32_t>* cam_list = nullptr)
+// of a pinhole camera whose origin's planes are listed, spt_bvh.h camera_planes); fast: its SPT_ACCEL_BVH_FAST branch -- the spatial tree
+// without inflation, no plane tree, the line table / tree
+void closest_bvh(const Scene& s, const spt::Bvh& bvh, V3 ro, V3 rd, uint32_t& near_key, uint32_t& near_tri, Cost& cost, const std::vector<uint32_t>* cam_list = nullptr,
+                 bool fast = false)
 {
     near_key = kInfKey; near_tri = 0xFFFFFFFFu;
     float tcut = 1e20f;
@@ -110,14 +117,16 @@ void closest_bvh(const Scene& s, const spt::Bvh& bvh, V3 ro, V3 rd, uint32_t& ne
         for (uint32_t k = 0; k < cnt; ++k) consider(&bvh.tris[3 * (size_t)(first + k)], bvh.index[first + k]);
     };
     static const bool no_planes = std::getenv("TRIBVH_NO_PLANES") != nullptr, no_lines = std::getenv("TRIBVH_NO_LINES") != nullptr;   // to see what each structure is there for
-    spt::tri_walk_boxes<true>(bvh.nodes.data(), bvh.cones.data(), ro.x, ro.y, ro.z, ivx, ivy, ivz, q.h[0], q.h[1], q.h[2], tcut, st, leaf);
+    static const bool fast_no_lines = std::getenv("TRIBVH_FAST_NO_LINES") != nullptr;
     auto plane = [&](uint32_t g) { cost.plane_nodes += 1; consider(&s.recs[3 * (size_t)g], g); };
     auto line = [&](uint32_t g) { cost.line_nodes += 1; consider(&s.recs[3 * (size_t)g], g); };
-    if (!no_planes) {
+    if (fast) spt::tri_walk_boxes<false>(bvh.nodes.data(), nullptr, ro.x, ro.y, ro.z, ivx, ivy, ivz, q.h[0], q.h[1], q.h[2], tcut, st, leaf);
+    else spt::tri_walk_boxes<true>(bvh.nodes.data(), bvh.cones.data(), ro.x, ro.y, ro.z, ivx, ivy, ivz, q.h[0], q.h[1], q.h[2], tcut, st, leaf);
+    if (!fast && !no_planes) {
         if (cam_list) { for (uint32_t g : *cam_list) plane(g); }          // a pinhole camera's ray: the planes through its origin are listed
         else if (!bvh.planes.empty()) spt::tri_walk_planes(bvh.planes.data(), q, st, plane);
     }
-    if (!no_lines) {
+    if (fast ? !fast_no_lines : !no_lines) {
         if (bvh.flat) { if (bvh.thin_count) spt::tri_scan_lines(bvh.flat_lines.data(), bvh.flat_line_index.data(), (uint32_t)bvh.flat_lines.size(), q, st, line); }
         else if (!bvh.lines.empty()) spt::tri_walk_lines(bvh.lines.data(), q, st, line);
     }
@@ -132,6 +141,54 @@ void closest_exhaustive(const Scene& s, V3 ro, V3 rd, uint32_t& near_key, uint32
     for (uint32_t g = 0; g < n; ++g) {
         const uint32_t key = key_of(tri_test(&s.recs[3 * (size_t)g], ro, rd));
         if (key < near_key) { near_key = key; near_tri = g; }
+    }
+}
+
+// the documented exception of the fast walk: triangle g is regular (g <= kTriThinG) and the ray lies in its plane to within tau = kTriBand g,
+// |nh.rdh| < tau (spt_tribvh.h (2) (A)), in double with n* = e1 x e2 of the record as the builder computes it
+bool fast_exception(const Scene& s, uint32_t g, V3 rd)
+{
+    if (g >= s.ntris()) return false;
+    const float4* r = &s.recs[3 * (size_t)g];
+    const double e1[3] = {r[1].x, r[1].y, r[1].z}, e2[3] = {r[2].x, r[2].y, r[2].z};
+    const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    const double l1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), l2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]), E = l1 * l2;
+    if (!(E > 0.0) || !(nn > 0.0) || E / nn > spt::kTriThinG) return false;
+    const double d[3] = {rd.x, rd.y, rd.z}, dd = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    return std::fabs(n[0] * d[0] + n[1] * d[1] + n[2] * d[2]) / (nn * dd) < spt::kTriBand * (E / nn);
+}
+
+// A triangle of genuine area whose angle at v0 is below ~1 / 40 or above pi - 1 / 40 (g = 1 / sine of it in [gmin, gmax]): base A B of
+// length L, apex C at height h over a point of the base line (inside the base or beyond either end), the vertices in a random cyclic
+// order and orientation, the whole in a random frame.  Rejects until the record's g is in range.
+template <class R>
+void add_sliver(Scene& s, R& rng, V3 c, float L, double gmin, double gmax)
+{
+    std::uniform_real_distribution<float> U(-1.f, 1.f), U01(0.f, 1.f);
+    for (;;) {
+        V3 u{U(rng), U(rng), U(rng)}, w{U(rng), U(rng), U(rng)};
+        if (dot(u, u) < 1e-2f) continue;
+        u = u * (1.f / std::sqrt(dot(u, u)));
+        w = w - u * dot(w, u);
+        if (dot(w, w) < 1e-2f) continue;
+        w = w * (1.f / std::sqrt(dot(w, w)));
+        const float gt = (float)(gmin * std::pow(gmax / gmin, (double)U01(rng)));      // log-uniform target
+        const float f = -0.5f + 2.f * U01(rng);                                          // foot of the apex along the base
+        const float h = L / gt * (0.3f + U01(rng));
+        V3 p[3] = {c, c + u * L, c + u * (f * L) + w * h};
+        const int rot = (int)(rng() % 3);
+        if (rng() % 2) std::swap(p[1], p[2]);
+        Scene t;
+        t.add(p[rot], p[(rot + 1) % 3], p[(rot + 2) % 3]);
+        const float4* r = t.recs.data();
+        const double e1[3] = {r[1].x, r[1].y, r[1].z}, e2[3] = {r[2].x, r[2].y, r[2].z};
+        const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        const double g = std::sqrt((e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]) * (e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2])) /
+                         std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        if (!(g >= gmin && g <= gmax)) continue;
+        s.add(p[rot], p[(rot + 1) % 3], p[(rot + 2) % 3]);
+        return;
     }
 }
 
@@ -263,7 +320,23 @@ int main(int argc, char** argv)
         add_sphere(s, {0, 0, 0}, 1e-3f, 8); add_sphere(s, {0, -1e3f - 2.f, -6.f}, 1e3f, 16);
         scenes.push_back(s);
     }
-    size_t total = 0, mismatches = 0;
+    {   // thin triangles of genuine area only (no regular triangle: the fast walk has no exception here)
+        Scene s; s.name = "slivers (g 40 ... 1e4, area 1e-3 ... 3), random frames";
+        for (int i = 0; i < 400; ++i) add_sliver(s, rng, V3{10.f * U(rng), 10.f * U(rng), 10.f * U(rng)}, std::pow(10.f, 0.5f * U(rng) + 0.5f), 40.0, 1e4);
+        scenes.push_back(s);
+    }
+    {   // slivers, a regular soup and a tessellated sphere (its pole needles), 1e3 from the origin
+        Scene s; s.name = "slivers + regular soup + sphere (L = 16), 1e3 away";
+        const V3 o{1000.f, -700.f, 400.f};
+        for (int i = 0; i < 300; ++i) add_sliver(s, rng, o + V3{8.f * U(rng), 8.f * U(rng), 8.f * U(rng)}, std::pow(10.f, 0.5f * U(rng) + 0.3f), 40.0, 1e4);
+        for (int i = 0; i < 300; ++i) {
+            const V3 c = o + V3{8.f * U(rng), 8.f * U(rng), 8.f * U(rng)};
+            s.add(c + V3{U(rng), U(rng), U(rng)}, c + V3{U(rng), U(rng), U(rng)}, c + V3{U(rng), U(rng), U(rng)});
+        }
+        add_sphere(s, o + V3{1.f, 2.f, -1.f}, 3.f, 16);
+        scenes.push_back(s);
+    }
+    size_t total = 0, mismatches = 0, fast_diff = 0, fast_exc = 0, fast_bad = 0;
     for (int form = 1; form <= 2; ++form)
     for (const Scene& s0 : scenes) {
         Scene s = s0;
@@ -279,12 +352,26 @@ int main(int argc, char** argv)
         Cost cost;
         std::vector<Cost> fcost(names.size());
         const bool verbose = std::getenv("TRIBVH_VERBOSE") != nullptr;
+        Cost fcost_fast;
+        size_t s_fdiff = 0, s_fexc = 0, s_fbad = 0;
+        // the fast walk on the same ray: a difference is either the documented exception or a failure
+        auto fast_check = [&](V3 o, V3 d, uint32_t k0, uint32_t t0, const char* fam) {
+            uint32_t k2, t2;
+            closest_bvh(s, bvh, o, d, k2, t2, fcost_fast, nullptr, true);
+            if (k0 == k2 && t0 == t2) return;
+            ++s_fdiff;
+            if (fast_exception(s, t0, d)) { ++s_fexc; return; }
+            if (s_fbad++ < 2)
+                std::printf("  FAST MISMATCH %s / %s: ray (%.9g %.9g %.9g) (%.9g %.9g %.9g): exhaustive key %08x tri %u, fast key %08x tri %u\n", s.name.c_str(), fam,
+                            o.x, o.y, o.z, d.x, d.y, d.z, k0, t0, k2, t2);
+        };
         for (const Ray& r : rays) {
             uint32_t k0, t0, k1, t1;
             closest_exhaustive(s, r.o, r.d, k0, t0);
             closest_bvh(s, bvh, r.o, r.d, k1, t1, cost);
             if (verbose) { uint32_t k2, t2; closest_bvh(s, bvh, r.o, r.d, k2, t2, fcost[r.family]); }
             if (k0 < kInfKey) ++hits[r.family];
+            fast_check(r.o, r.d, k0, t0, names[r.family].c_str());
             if (k0 != k1 || t0 != t1) {
                 if (bad[r.family]++ < 2)
                     std::printf("  MISMATCH %s / %s: ray (%.9g %.9g %.9g) (%.9g %.9g %.9g): exhaustive key %08x tri %u, hierarchy key %08x tri %u\n", s.name.c_str(),
@@ -320,6 +407,7 @@ int main(int argc, char** argv)
                     closest_exhaustive(s, o, d, k0, t0);
                     closest_bvh(s, bvh, o, d, k1, t1, cost, &list);
                     if (k0 < kInfKey) ++hits[fam];
+                    fast_check(o, d, k0, t0, "camera rays");
                     if (k0 != k1 || t0 != t1) {
                         if (bad[fam]++ < 2) std::printf("  MISMATCH %s / pinhole: origin (%.9g %.9g %.9g) dir (%.9g %.9g %.9g): exhaustive key %08x tri %u, hierarchy key %08x tri %u (list of %zu)\n",
                                                         s.name.c_str(), o.x, o.y, o.z, d.x, d.y, d.z, k0, t0, k1, t1, list.size());
@@ -338,9 +426,13 @@ int main(int argc, char** argv)
                 std::printf("    %-40s box leaves %.1f, plane candidates %.2f, line candidates %.2f, tests %.1f\n", names[f].c_str(), fcost[f].box_nodes / fcost[f].rays,
                             fcost[f].plane_nodes / fcost[f].rays, fcost[f].line_nodes / fcost[f].rays, fcost[f].tests / fcost[f].rays);
         for (size_t f = 0; f < names.size(); ++f) if (bad[f]) std::printf("    %-40s %zu of %zu differ\n", names[f].c_str(), bad[f], per_family);
-        total += rays.size(); mismatches += b;
+        std::printf("    fast walk: %zu differ (%zu documented exceptions, %zu unexplained) | per ray: %.1f leaves, %.2f line candidates, %.1f tests\n",
+                    s_fdiff, s_fexc, s_fbad, fcost_fast.box_nodes / fcost_fast.rays, fcost_fast.line_nodes / fcost_fast.rays, fcost_fast.tests / fcost_fast.rays);
+        total += rays.size(); mismatches += b; fast_diff += s_fdiff; fast_exc += s_fexc; fast_bad += s_fbad;
     }
     std::printf("stack pushes per ray (all walks) %.1f\n", HostStack::pushes / (double)total);
-    std::printf("rays %zu, mismatches %zu, %s\n", total, mismatches, mismatches ? "tribvh harness FAILED" : "tribvh harness ok");
-    return mismatches ? 1 : 0;
+    std::printf("fast walk: rays %zu, differences %zu, documented exceptions %zu, unexplained %zu\n", total, fast_diff, fast_exc, fast_bad);
+    const bool failed = mismatches || fast_bad;
+    std::printf("rays %zu, mismatches %zu, %s\n", total, mismatches, failed ? "tribvh harness FAILED" : "tribvh harness ok");
+    return failed ? 1 : 0;
 }

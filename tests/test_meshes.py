@@ -388,8 +388,9 @@ def test_default_mode_picks_between_the_two_exact_modes(pkg, oracle):
 
 @pytest.mark.gpu
 def test_bvh_fast_mode_agrees_on_ordinary_rays(pkg, renderer):
-    """SPT_ACCEL_BVH_FAST (the spatial hierarchy alone, rounds 2-3; opt-in): random rays and rendered images agree with the exhaustive loop
-    -- only rays lying in a triangle's plane to rounding may differ, which is why it is not the default."""
+    """SPT_ACCEL_BVH_FAST (the plain spatial hierarchy of rounds 2-3 and the thin triangles' lines; opt-in): random rays and rendered images
+    agree with the exhaustive loop -- only rays lying in a regular triangle's plane to rounding may differ, which is why it is not the default
+    (scenes of slivers: tests/test_gpu_mesh_fast.py)."""
     S = pkg.make_sphere_trimesh
     meshes = [S((-1, 0, -4), 1.0), S((1.5, 0, -5), 1.0)]
     mats = [((0, 0, 0), (.5, .5, .5), pkg.DIFF)] * 2
@@ -416,7 +417,8 @@ def test_bvh_fast_mode_agrees_on_ordinary_rays(pkg, renderer):
 def test_mesh_scenes_of_degenerate_triangles_only(pkg):
     """Scenes in which one of the hierarchy's structures (or all of them) is empty: only triangles with an edge of length zero (in no
     structure), only needles (the line table alone), one of each, a single regular triangle -- every mode returns the exhaustive loop's
-    hits and image, nothing is read out of bounds."""
+    hits and image (SPT_ACCEL_BVH_FAST: its image always, its hits where no regular triangle can make an exception), nothing is read out
+    of bounds."""
     def mesh(tris):
         v = np.asarray(tris, dtype=np.float32).reshape(-1, 3)
         return pkg.TriMesh(v, np.tile(np.array([0, 1, 0], dtype=np.float32), (len(v), 1)), np.arange(len(v), dtype=np.uint32).reshape(-1, 3))
@@ -443,6 +445,8 @@ def test_mesh_scenes_of_degenerate_triangles_only(pkg):
             ref = out[pkg.ACCEL_EXHAUSTIVE]
             assert np.array_equal(out[pkg.ACCEL_BVH][0].view(np.uint8), ref[0].view(np.uint8)) and np.array_equal(out[pkg.ACCEL_BVH][1], ref[1]), name
             assert np.array_equal(out[pkg.ACCEL_BVH_FAST][1], ref[1]), name
+            if "regular" not in name:                        # no regular triangle: no exception of the fast mode, every Hit is exact
+                assert np.array_equal(out[pkg.ACCEL_BVH_FAST][0].view(np.uint8), ref[0].view(np.uint8)), name
             if "regular" in name:
                 assert (ref[0]["dist"] < 1e20).sum() > 100, name
 

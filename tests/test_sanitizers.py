@@ -1,6 +1,7 @@
 """ASan + UBSan over the code that runs on the CPU: the host C++ scene/JSON/request reader and the
 oracle.  GPU AddressSanitizer is not available on the pool, so device code is covered by the bit-exact parity tests."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -79,27 +80,63 @@ def _tribvh_harness(tmp_path, flags, name):
     return exe
 
 
+# per scene of the harness: the fast walk's differences, documented exceptions and unexplained ones
+_FAST = re.compile(r"^\[line (?:table|tree)\]\s+(.+?)\s{2,}\d+ triangles \((\d+) regular.*\n\s+fast walk: (\d+) differ \((\d+) documented exceptions, (\d+) unexplained\)",
+                   re.M)
+_SLIVERS = "slivers (g 40 ... 1e4, area 1e-3 ... 3), random frames"
+
+
+def _fast_rows(stdout):
+    return [(m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4)), int(m.group(5))) for m in _FAST.finditer(stdout)]
+
+
 def test_triangle_hierarchy_equals_the_exhaustive_loop_on_the_cpu(tmp_path):
     """SPT_ACCEL_BVH of a mesh scene is exhaustive-equivalent for EVERY ray (csrc/spt_tribvh.h): the host builder and the very walk /
-    node-test functions the gfx950 kernel calls, against the reference's exhaustive loop on seven scenes x 17 families of rays built to
+    node-test functions the gfx950 kernel calls, against the reference's exhaustive loop on nine scenes x 17 families of rays built to
     break a hierarchy (in a triangle's plane anywhere in it, tilted out of it by 2^-6 ... 2^-26, along edges, across the supporting
     lines of needles, from 300 scene sizes away, ...): 0 mismatches; and the harness is sensitive -- without the plane tree or without
-    the line tree it reports mismatches."""
-    exe = _tribvh_harness(tmp_path, ["-O2"], "tribvh")
-    r = subprocess.run([str(exe), "2000"], capture_output=True, text=True)
-    assert r.returncode == 0 and "mismatches 0, tribvh harness ok" in r.stdout, (r.stdout[-3000:], r.stderr[-2000:])
-    for knob in ("TRIBVH_NO_PLANES", "TRIBVH_NO_LINES"):
-        r = subprocess.run([str(exe), "1000"], capture_output=True, text=True, env=dict(os.environ, **{knob: "1"}))
-        assert r.returncode == 1 and "tribvh harness FAILED" in r.stdout, knob
+    the line tree it reports mismatches.  SPT_ACCEL_BVH_FAST (the plain spatial tree and the thin triangles' lines) on the same rays:
+    every difference is its documented exception (the exhaustive winner is a regular triangle in whose plane the ray lies), none on
+    the scenes without regular triangles (slivers of genuine area, g 40 ... 1e4), and without the lines it misses the slivers.
+    The node tests in the device's form: fused where SPT_TRI_FMA says so."""
+    _check_tribvh(tmp_path, [], "tribvh")
+
+
+def test_triangle_hierarchy_with_unfused_node_tests_equals_the_exhaustive_loop_on_the_cpu(tmp_path):
+    """The same harness and assertions with the node tests unfused (-DSPT_TRI_UNFUSED: one rounding per operation): the thresholds'
+    slack covers either evaluation (csrc/spt_tribvh.h, "Float evaluation of the node tests")."""
+    _check_tribvh(tmp_path, ["-DSPT_TRI_UNFUSED"], "tribvh_unfused")
+
+
+def _check_tribvh(tmp_path, flags, name):
+    exe = _tribvh_harness(tmp_path, ["-O2", *flags], name)
+    runs = {None: subprocess.Popen([str(exe), "2000"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)}
+    for knob in ("TRIBVH_NO_PLANES", "TRIBVH_NO_LINES", "TRIBVH_FAST_NO_LINES"):
+        runs[knob] = subprocess.Popen([str(exe), "1000"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=dict(os.environ, **{knob: "1"}))
+    out = {k: (p.communicate()[0], p.returncode) for k, p in runs.items()}
+    stdout, code = out[None]
+    assert code == 0 and "mismatches 0, tribvh harness ok" in stdout and "unexplained 0\n" in stdout, stdout[-3000:]
+    rows = _fast_rows(stdout)
+    assert len(rows) == 18 and sum(r[0] == _SLIVERS for r in rows) == 2, rows
+    for scene, regular, differ, documented, unexplained in rows:
+        assert unexplained == 0 and documented == differ, (scene, differ, documented, unexplained)
+        if regular == 0:
+            assert differ == 0, scene                        # nothing can be an exception without a regular triangle
+    for knob in ("TRIBVH_NO_PLANES", "TRIBVH_NO_LINES", "TRIBVH_FAST_NO_LINES"):
+        stdout, code = out[knob]
+        assert code == 1 and "tribvh harness FAILED" in stdout, knob
+    slivers = [r for r in _fast_rows(out["TRIBVH_FAST_NO_LINES"][0]) if r[0] == _SLIVERS]
+    assert len(slivers) == 2 and all(r[4] > 100 for r in slivers), slivers
 
 
 def test_triangle_hierarchy_walks_under_asan_ubsan(tmp_path):
-    """The same harness under ASan + UBSan (fewer rays): the ball-tree builder, the validator and the three walks."""
+    """The same harness under ASan + UBSan (fewer rays): the ball-tree builder, the validator and the three walks, exact and fast, in the
+    fused form the device evaluates."""
     if not _sanitizers_work(tmp_path):
         pytest.skip("libasan/libubsan not usable in this environment")
     exe = _tribvh_harness(tmp_path, SAN, "tribvh_san")
     r = subprocess.run([str(exe), "150"], capture_output=True, text=True, env=ENV)
-    assert r.returncode == 0 and "mismatches 0, tribvh harness ok" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
+    assert r.returncode == 0 and "mismatches 0, tribvh harness ok" in r.stdout and "unexplained 0\n" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
 
 
 def test_sphere_grid_builder_and_walk_under_asan_ubsan(tmp_path):
