@@ -1,7 +1,7 @@
 /*
  * smallpt_oracle.c -- CPU ORACLE (test infrastructure, NOT product code).  See smallpt_oracle.h
- * for the role and the parity-pin status ("parity unpinned by the reference's own tests";
- * pinned to the SURVEY.md 8(c) known-answer values).
+ * for the role and the parity-pin status (the geometry is compared with the reference's compiled scene.cpp,
+ * tests/test_reference_scene.py; the rest is pinned to the SURVEY.md 8(c) known-answer values).
  *
  * Plain C restatement of the reference algorithm.  Every function cites the reference lines it
  * follows (paths relative to /root/reference).  Arithmetic rules (DESIGN.md "Arithmetic spec"):
@@ -214,7 +214,7 @@ void orc_tri_intersect(const float ro_[3], const float rd_[3], const float v0_[3
 
 /* scene.cpp:3-48 makeSphereTriMesh (subdivLongitude default 32, scene.h:17): (discLong+1)*(discLat+1) vertices with
  * discLat = 2*discLong, 2*discLong*discLat triangles.  cos/sin are the C++ float overloads (cosf/sinf of the C library:
- * host-side table generation, not on the device path).  Buffers are caller-allocated; returns the triangle count. */
+ * host-side table generation, not on the device path; the reading is decided in DESIGN.md section 3 and checked against the compiled reference).  Buffers are caller-allocated; returns the triangle count. */
 uint32_t orc_make_sphere_trimesh(const float origin[3], float radius, uint32_t subdiv_longitude,
                                  float* positions, float* normals, uint32_t* indices)
 {
@@ -315,6 +315,47 @@ void orc_trace_rays(const orc_mesh* meshes, uint32_t nmesh, const orc_ray* rays,
 #endif
     for (int64_t i = 0; i < (int64_t)n; ++i)
         intersect_meshes(meshes, nmesh, ld(rays[i].o), ld(rays[i].d), &hits[i]);
+}
+
+/* ---- batched per-primitive reports: the counterparts of oracle/refshim/ref_scene_wrap.cpp, record for record, so that
+ * tests/test_reference_scene.py can compare the restatements above with the reference's compiled scene.cpp ---- */
+/* triIntersect per record: rays = n x (ro, rd), tris = n x (v0, v1, v2), out = n x (dist, u, v). */
+void orc_tri_intersect_batch(const float* rays, const float* tris, uint64_t n, float* out)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* r = rays + 6 * i;
+        const float* t = tris + 9 * i;
+        out[3 * i] = tri_intersect(ld(r), ld(r + 3), ld(t), ld(t + 3), ld(t + 6), &out[3 * i + 1], &out[3 * i + 2]);
+    }
+}
+
+/* makeHit(0, mesh, intersect(ro, rd, mesh)) of scene.cpp per ray, for one mesh of at least one triangle, BEFORE the selection of
+ * smallpt.cpp:449-455 turns dist >= inf into Hit{}: a winner at dist = inf keeps its triangle and barycentrics (:105 accepts it),
+ * and the MeshHit{} of :113 (dist = inf, u = v = 0, triId = 0) goes through makeHit like any other. */
+int orc_mesh_hits(const orc_mesh* m, const orc_ray* rays, uint64_t n, orc_hit* hits)
+{
+    if (m->ntris == 0) return 1;
+    for (uint64_t i = 0; i < n; ++i) {
+        float t = ORC_INF, u = 0, v = 0;
+        int k = intersect_mesh(m, ld(rays[i].o), ld(rays[i].d), &t, &u, &v);
+        if (k < 0) { k = 0; t = ORC_INF; u = 0; v = 0; }                       /* :113 MeshHit{} */
+        make_mesh_hit(m, 0, (uint32_t)k, t, u, v, &hits[i]);
+    }
+    return 0;
+}
+
+/* Sphere::makeHit(0, Sphere::intersectAnalytic(ray)) per record: spheres = n x (center, radius), rays = n x (o, d),
+ * out = n x (dist, x, n); a miss is SphereHit{} (dist = inf, x = 0) and its normal normalize(0 - center), scene.cpp:118-140. */
+void orc_sphere_reports(const float* spheres, const float* rays, uint64_t n, float* out)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* r = rays + 6 * i;
+        const f3 c = ld(spheres + 4 * i);
+        f3 x = mk(0, 0, 0);
+        out[7 * i] = intersect_analytic(c, spheres[4 * i + 3], ld(r), ld(r + 3), &x);
+        st(out + 7 * i + 1, x);
+        st(out + 7 * i + 4, normalize(sub(x, c)));                             /* :124 */
+    }
 }
 
 /* ---------------------------------------------------------------- mesh instances ---------- */

@@ -7,12 +7,12 @@
  * cpu_baseline leg of bench.py may load this library; the product path
  * (optix-test-smallpt_amd/) never links, includes or calls anything in oracle/.
  *
- * PARITY PIN STATUS: the reference ships no tests, fixtures or golden images
- * (SURVEY.md section 4), and it cannot be compiled in this image (it needs the NVIDIA
- * OptiX SDK headers, OptiX Prime and GLFW, none of which are present; no stand-ins are
- * written).  The oracle is therefore "parity unpinned by the reference's own tests"; it is
- * pinned instead against the known-answer values that SURVEY.md section 8(c) recorded from the
- * reference's own intersectAnalytic()/makeHit() (tests/golden/reference_kats.json).
+ * PARITY PIN STATUS: the reference ships no tests, fixtures or golden images.  Its smallpt.cpp
+ * cannot be compiled here (OptiX Prime, GLFW), so the path tracer stays "parity unpinned by the reference's own
+ * tests", pinned to the known-answer values of SURVEY.md section 8(c) (tests/golden/reference_kats.json).  Its
+ * scene.cpp CAN be compiled (oracle/Makefile target _ref, stand-in headers in oracle/refshim): the geometry here --
+ * makeSphereTriMesh, triIntersect, intersect + makeHit, intersectAnalytic + Sphere::makeHit -- is compared with that
+ * compiled code bit for bit by tests/test_reference_scene.py.
  */
 #ifndef SMALLPT_ORACLE_H
 #define SMALLPT_ORACLE_H
@@ -98,6 +98,14 @@ uint32_t orc_make_sphere_trimesh(const float origin[3], float radius, uint32_t s
                                  float* positions, float* normals, uint32_t* indices);
 /* Intersector::traceRays (smallpt.cpp:427-473: CPUIntersector::intersect = scene.cpp:95-116 per mesh + makeHit :73-93) */
 void  orc_trace_rays(const orc_mesh* meshes, uint32_t nmesh, const orc_ray* rays, uint64_t n, orc_hit* hits);
+/* Batched per-primitive reports with the layouts of oracle/refshim/ref_scene_wrap.cpp (the reference's compiled scene.cpp):
+ * triIntersect per (ray, triangle) record, out = n x (dist, u, v) */
+void  orc_tri_intersect_batch(const float* rays, const float* tris, uint64_t n, float* out);
+/* makeHit(0, mesh, intersect(ro, rd, mesh)) per ray as scene.cpp returns it (a winner at dist = inf and MeshHit{} included, before the
+ * selection of smallpt.cpp:449-455 makes them Hit{}); returns 1 for a mesh without triangles */
+int   orc_mesh_hits(const orc_mesh* mesh, const orc_ray* rays, uint64_t n, orc_hit* hits);
+/* Sphere::makeHit(0, Sphere::intersectAnalytic(ray)) per (ray, sphere) record: spheres = n x (center, radius), out = n x (dist, x, n) */
+void  orc_sphere_reports(const float* spheres, const float* rays, uint64_t n, float* out);
 /* D7 counter-based RNG */
 uint32_t orc_mix32(uint32_t x);
 void  orc_sample_keys(uint64_t seed, uint32_t pixel_idx, uint32_t sample_idx, uint32_t* k0, uint32_t* k1);

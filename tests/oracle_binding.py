@@ -77,6 +77,11 @@ def lib():
         L.orc_render_instances.argtypes = [C.POINTER(OrcMesh), C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(OrcMaterial), C.POINTER(OrcCamera),
                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
                                            C.POINTER(OrcStats)]
+        L.orc_tri_intersect_batch.restype = None
+        L.orc_tri_intersect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.orc_mesh_hits.argtypes = [C.POINTER(OrcMesh), C.c_void_p, C.c_uint64, C.c_void_p]
+        L.orc_sphere_reports.restype = None
+        L.orc_sphere_reports.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -151,6 +156,37 @@ def trace_rays(meshes, rays):
     hits = np.zeros(len(rays), dtype=HIT_DTYPE)
     lib().orc_trace_rays(ms, len(meshes), rays.ctypes.data, len(rays), hits.ctypes.data)
     return hits
+
+
+# ---- batched per-primitive reports, record for record the layouts of tests/reference_binding.py ----
+def tri_intersect_batch(rays, tris):
+    """orc_tri_intersect_batch: rays (n, 6), tris (n, 9) -> (n, 3) = dist, u, v."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+    assert len(rays) == len(tris)
+    out = np.zeros((len(rays), 3), dtype=np.float32)
+    lib().orc_tri_intersect_batch(rays.ctypes.data, tris.ctypes.data, len(rays), out.ctypes.data)
+    return out
+
+
+def mesh_hits(mesh, rays):
+    """orc_mesh_hits: makeHit(0, mesh, intersect(ro, rd, mesh)) per ray as scene.cpp returns it, HIT_DTYPE[n]."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    ms, _, keep = _mesh_args([mesh], [((0, 0, 0), (0, 0, 0), 0)])
+    hits = np.zeros(len(rays), dtype=HIT_DTYPE)
+    if lib().orc_mesh_hits(ms, rays.ctypes.data, len(rays), hits.ctypes.data):
+        raise ValueError("orc_mesh_hits: a mesh without triangles")
+    return hits
+
+
+def sphere_reports(spheres, rays):
+    """orc_sphere_reports: spheres (n, 4) = centre, radius; rays (n, 6) -> (n, 7) = dist, x, n."""
+    spheres = np.ascontiguousarray(spheres, dtype=np.float32).reshape(-1, 4)
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    assert len(spheres) == len(rays)
+    out = np.zeros((len(rays), 7), dtype=np.float32)
+    lib().orc_sphere_reports(spheres.ctypes.data, rays.ctypes.data, len(rays), out.ctypes.data)
+    return out
 
 
 def render_meshes(meshes, materials, w, h, samps, seed=0, normalise=False, row_begin=0, row_count=None, threads=0, camera=None):
