@@ -104,6 +104,7 @@ INTERNAL_SYMBOLS = {
     "spt_set_grid_pools": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "spt_diag": (C.c_int, [_P, C.POINTER(C.c_uint64 * 24)]),
     "spt_selftest_share": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int)]),
+    "spt_selftest_row_divisor": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "spt_selftest_math": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32, C.c_uint32]),
     "spt_selftest_range": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "spt_set_watchdog": (C.c_int, [_P, C.c_double]),

@@ -1572,6 +1572,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
     P.w = w; P.h = h; P.row_begin = row_begin; P.row_count = row_count;
     P.rb_log2 = rb_log2; P.rb_stride = rb_stride; P.rb_mask = rb_mask;
     P.inv_w = 1.0 / (double)w; P.inv_h = 1.0 / (double)h;
+    spt::row_divisor(w, &P.wdiv_mul, &P.wdiv_shift);    // (valid below 2^32 / 2 cell ids: the bound on sample blocks above)
     P.samps = samps; P.ntasks = (uint32_t)ntasks;
     P.nb_log2 = nb_log2; P.sb = (samps + nb - 1u) / nb;
     P.park_threshold = (c->variant & 0xFFu) ? (c->variant & 0xFFu) : 8u;
@@ -1803,7 +1804,8 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
         SPT_HIP(c, hipEventRecord(c->ev_start, st));
         // sharing pattern of the closest hit (spt_share.h): compiled for the default pool size; tuning bit 14 forces the generic test
         const int share = !(c->variant & 0x4000u) && spt_pool_share_compiled(pool, P.n, c->share) ? c->share : spt::kShareNone;
-        SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st, radiance, share));
+        // tuning bit 15: the bounce loop's bookkeeping as it was before it was trimmed (A/B, default pool size)
+        SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st, radiance, share, (c->variant & 0x8000u) && spt_pool_has_old_loop(pool) ? 1 : 0));
         c->last_share = share;
         SPT_HIP(c, hipEventRecord(c->ev_mid, st));
         SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
@@ -2222,6 +2224,14 @@ int spt_set_watchdog(spt_ctx* c, double seconds)
 }
 
 int spt_last_kernel(spt_ctx* c) { return c ? c->last_kernel : -1; }
+
+// Host-only (spt_internal.h): the multiplier and shift the pool kernel divides a jitter cell's id by the image width with.
+int spt_selftest_row_divisor(uint32_t w, uint32_t* mul, uint32_t* shift)
+{
+    if (!w || !mul || !shift) return 1;
+    spt::row_divisor(w, mul, shift);
+    return 0;
+}
 
 int spt_selftest_share(const spt_sphere* spheres, uint32_t n, int* pattern)
 {

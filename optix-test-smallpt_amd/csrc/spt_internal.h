@@ -26,7 +26,9 @@ int  spt_set_tuning(spt_ctx* ctx, uint32_t blocks_per_cu, uint32_t variant);
 int  spt_set_grid_pools(spt_ctx* ctx, int lane_owned, uint32_t slots, uint32_t ready, uint32_t drain, uint32_t min_batch, uint32_t walk_iters);
 /* Pool kernel: bit 13 = hand the task chunks out in their static order (no cost-ordered dispatch, spt_kernel.h KParams::chunk_order; the
  * grid kernel reads bits 15:13 as its workgroup size).  Bit 14 = the generic closest hit: no sharing pattern (csrc/spt_share.h) even
- * where the table matches one (A/B; the grid kernel reads it as part of bits 15:13). */
+ * where the table matches one (A/B; the grid kernel reads it as part of bits 15:13).  Bit 15 = the bounce loop's bookkeeping as it was
+ * before it was trimmed -- batch statistics counted per iteration in registers, the push's lane masks from an integer class, the image row
+ * by an integer division -- for the default pool size (A/B; the other sizes run the trimmed loop only; the grid kernel reads it as part of bits 15:13). */
 /* Pool kernel, cost-ordered dispatch: copies the chunk order that the last pool launch left for the next launch of the same view
  * (a permutation of 0 .. nchunks - 1, most expensive chunk first) to `order` (room for `cap` words).  *nchunks = 0 when that
  * launch recorded none (a few samples per cell, tuning bit 13, another kernel).  Synchronises with the device. */
@@ -84,6 +86,9 @@ int  spt_selftest_sphere_grid(const spt_sphere* spheres, uint32_t n, uint32_t ce
  * 0 = generic, 1 = box prefix, 2 = Cornell-9), the same function on the same padded table.  The pattern runs where the default pool size
  * does and tuning bit 14 is clear.  Returns 0, 1 = bad arguments. */
 int  spt_selftest_share(const spt_sphere* spheres, uint32_t n, int* pattern);
+/* Host-only: the round-up multiplier and shift with which the pool kernel computes a jitter cell's image row without a division
+ * (csrc/spt_kernel.h row_divisor): floor(x / (2 w)) = mulhi(x, *mul) >> *shift for every x < 2^31.  Returns 0, 1 = bad arguments. */
+int  spt_selftest_row_divisor(uint32_t w, uint32_t* mul, uint32_t* shift);
 
 /* spt_trace_spheres*: what the last query of this context ran through -- 0 = the exhaustive loop, 1 = the uniform grid, 2 = the sphere
  * hierarchy, -1 = no query yet -- and, in *fallback_rays (may be NULL), how many of its rays the grid or the hierarchy handed to the exhaustive

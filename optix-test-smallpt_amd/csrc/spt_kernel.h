@@ -48,7 +48,23 @@ struct KParams {
     const uint32_t* chunk_order;
     uint32_t* chunk_clock;
     uint32_t nchunks;
+    // pool kernel: the image row of a jitter cell without an integer division (row_divisor below)
+    uint32_t wdiv_mul, wdiv_shift;
 };
+
+// Round-up multiplier for the pool kernel's row index.  A jitter cell id is 4 p + cell (p = local pixel index, cell < 4) and stays below
+// 0xF0000000 (the API's bound on sample blocks per band), so x = id >> 1 = 2 p + (cell >> 1) < 2^31 and floor(x / (2 w)) = floor(p / w).
+// With D = 2 w, s = ceil(log2 D) - 1 (2^s < D <= 2^(s+1)) and mul = ceil(2^(32+s) / D) = (2^(32+s) + e) / D, 0 <= e < D <= 2^(s+1):
+// x mul / 2^(32+s) = x / D + x e / (D 2^(32+s)), and x e < 2^31 2^(s+1) = 2^(32+s) keeps the excess below 1 / D, so
+// floor(x / D) = mulhi(x, mul) >> s for every x < 2^31; mul <= 2^(32+s) / (2^s + 1) + 1 < 2^32 (D = 2^(s+1): mul = 2^31).
+inline void row_divisor(uint32_t w, uint32_t* mul, uint32_t* shift)
+{
+    const uint64_t D = 2ull * w;
+    uint32_t L = 1;
+    while ((1ull << L) < D) ++L;
+    *shift = L - 1u;
+    *mul = (uint32_t)(((1ull << (31u + L)) + D - 1ull) / D);
+}
 
 // Triangle-mesh scene (spt_mesh.hip): the reference's TriMesh instances flattened into device tables
 struct MParams {
@@ -146,7 +162,9 @@ extern "C" int spt_pool_max_spheres(void);
 extern "C" int spt_pool_default_slots(void);
 extern "C" int spt_pool_has_size(int pool);
 // share: sharing pattern of the wide closest hit (csrc/spt_share.h), chosen by spt::share_select on the padded table
-extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env = nullptr, int share = 0);
+// old_loop: the untrimmed bookkeeping of the bounce loop (tuning bit 15), compiled where spt_pool_has_old_loop says so
+extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env = nullptr, int share = 0, int old_loop = 0);
+extern "C" int spt_pool_has_old_loop(int pool);
 extern "C" int spt_pool_share_compiled(int pool, uint32_t n, int share);
 extern "C" hipError_t spt_k_selftest_range(int op, uint32_t first, uint32_t count, unsigned long long* d_mismatches, uint32_t* d_first_bad, hipStream_t stream);
 extern "C" hipError_t spt_k_accumulate(float* accum, const float* frame, size_t n, int clear, hipStream_t stream);

@@ -55,6 +55,12 @@ __device__ __forceinline__ uint32_t rank_in(unsigned long long m)
 {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
+__device__ __forceinline__ unsigned long long lanes_where(bool p) { return __builtin_amdgcn_ballot_w64(p); }   // the compare's own lane mask
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;                                                    // lane 0 holds the sum
+}
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint32_t umin2(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c)
@@ -76,8 +82,11 @@ enum { C_GEN = 0, C_DIFF = 1, C_REFR = 2 };
 // EP: empty, or EParams for the environment variant: E is staged in one LDS entry behind the material table and read on a miss only
 // (the bounce loop's constants come from the kernel-argument segment; E is not kept in scalar registers across it)
 // SH: sharing pattern of the wide closest hit (spt_share.h; kShareNone = the generic test)
-template <int P, int NG, int SH, typename... EP>
-__global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const EP... env)
+// OLD: the loop's bookkeeping as it was before it was trimmed (poolkernel_untrimmed, tuning bit 15, A/B): batch statistics counted per
+// iteration, the next class as an integer compared three times, the image row by an integer division.  Same lists, same order, same
+// arithmetic either way (tests/test_gpu_pool_loop.py).
+template <int P, int NG, int SH, bool OLD, typename... EP>
+__device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
 {
     constexpr bool ENV = kHasEnv<EP...>;
     static_assert(P % 16 == 0 && P <= 256, "pool size");
@@ -138,6 +147,12 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
     uint32_t lnG = 0, lnD = 0, lnR = 0;                          // lanes per class (32 bits per wave: scalar registers are scarce in this loop)
     uint32_t itTail = 0, itFull = 0;                             // batches after the task queue ran dry / full batches
     uint32_t lnTail = 0;
+    // The trimmed loop keeps the same statistics without a per-iteration cost in scalar registers (which the loop has none to spare: the
+    // compiler kept the ten counters above in vector registers and paid two selects and five additions with scalar operands per
+    // batch).  Lane l takes part in a batch iff l < b, so one per-lane counter per class, bumped by the class code's `valid`, holds all of
+    // them: lane 0 counts the class's batches, lane 63 its full ones, the wave sum its lanes; the tail is what was counted after the
+    // snapshot taken when the queue ran dry.
+    uint32_t cntG = 0, cntD = 0, cntR = 0, cntDry = 0;
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
     uint32_t it_total = 0;
     bool timed_out = false;
@@ -175,11 +190,13 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
             if (nR > m) { c = C_REFR; m = nR; }
             if (m == 0u) break;                                   // every list empty: all tasks of this wave are done
         }
-        if (c == C_GEN) { b = nG < 64u ? nG : 64u; nG -= b; lbase = nG; ++itG; lnG += b; }
-        else if (c == C_DIFF) { b = nD < 64u ? nD : 64u; nD -= b; lbase = (uint32_t)P + nD; ++itD; lnD += b; }
-        else { b = nR < 64u ? nR : 64u; lbase = 2u * (uint32_t)P - nR; nR -= b; ++itR; lnR += b; }   // REFR entries: LDR[P-nR .. P-1]
-        if (queue_empty) { ++itTail; lnTail += b; }
-        if (b == 64u) ++itFull;
+        if (c == C_GEN) { b = nG < 64u ? nG : 64u; nG -= b; lbase = nG; if constexpr (OLD) { ++itG; lnG += b; } }
+        else if (c == C_DIFF) { b = nD < 64u ? nD : 64u; nD -= b; lbase = (uint32_t)P + nD; if constexpr (OLD) { ++itD; lnD += b; } }
+        else { b = nR < 64u ? nR : 64u; lbase = 2u * (uint32_t)P - nR; nR -= b; if constexpr (OLD) { ++itR; lnR += b; } }   // REFR entries: LDR[P-nR .. P-1]
+        if constexpr (OLD) {
+            if (queue_empty) { ++itTail; lnTail += b; }
+            if (b == 64u) ++itFull;
+        }
         if ((++it_total & 255u) == 0u && K.watchdog_ticks != 0ull &&
             __builtin_amdgcn_s_memtime() - t_start > K.watchdog_ticks) { timed_out = true; break; }
 
@@ -195,6 +212,7 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
         PH_STAMP(0)
         if (c == C_GEN) {
             // ================= GEN: continue the slot's task (smallpt.cpp:304-340, :252 pop) =================
+            if constexpr (!OLD) cntG += valid ? 1u : 0u;
             const uint2 ts = gtask[slot];
             uint32_t task = ts.x, snext = ts.y;
             sp = __float_as_uint(A1[slot].w) >> 30;
@@ -224,7 +242,7 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
                     gen = true;
                 }
             }
-            const unsigned long long need_mask = __ballot(need_task);
+            const unsigned long long need_mask = OLD ? __ballot(need_task) : lanes_where(need_task);
             if (need_mask != 0ull) {
                 // cost-ordered dispatch (see chunk_order_kernel): completion times go to the chunk's clock word, fetch times below
                 // (pointers rebuilt from integers are generic to the compiler: said to be global, or it emits FLAT operations, which count
@@ -258,6 +276,7 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
                             queue_empty = true;
                             const unsigned long long t = __builtin_amdgcn_s_memtime();
                             asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(dry_lo), "=v"(dry_hi) : "s"((uint32_t)t), "s"((uint32_t)(t >> 32)));
+                            if constexpr (!OLD) cntDry = cntG + cntD + cntR;     // (every lane is active here: the branches above are wave-uniform)
                         } else {
                             const GWords ord = (GWords)(((unsigned long long)o_hi << 32) | o_lo);
                             if (ord) base_new = uni(ord[base_new >> 6]) << 6;        // the queue's k-th chunk of 64 tasks (declared wave-uniform: the list arithmetic stays scalar)
@@ -287,7 +306,9 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
                 // ---- camera ray of sample `snext` of the cell (smallpt.cpp:325-340 / :745-760) ----
                 const uint32_t cellid = task >> K.nb_log2;
                 const uint32_t pix_local = cellid >> 2, cell = cellid & 3u;
-                const uint32_t ry = pix_local / K.w;
+                // floor(pix_local / w) without the division: the host's round-up multiplier for 2 w (spt_kernel.h row_divisor) applied to
+                // 2 pix_local + (cell >> 1), which has the same quotient
+                const uint32_t ry = OLD ? pix_local / K.w : __umulhi(cellid >> 1, K.wdiv_mul) >> K.wdiv_shift;
                 const uint32_t px = pix_local - ry * K.w;
                 const uint32_t py = K.row_begin + (ry >> K.rb_log2) * K.rb_stride + (ry & K.rb_mask);   // band or interleaved row blocks
                 const uint32_t pixel_idx = py * K.w + px;                    // GLOBAL index (:298)
@@ -344,6 +365,7 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
             const f3 n = normalize<false>(mk(hx.x - gh.x, hx.y - gh.y, hx.z - gh.z));       // scene.cpp:124
             const f3 nl = dot(n, din) < 0 ? n : neg(n);                                     // :174 (D2)
             if (c == C_DIFF) {
+                if constexpr (!OLD) cntD += valid ? 1u : 0u;
                 const bool is_diff = valid && ((pk >> 28) & 3u) == 0u;   // idle lanes (pk = 0) must not drag a mirror-only batch through the diffuse code
                 o = hx + nl * 0.02f;                                                        // :172 (D3)
                 if (is_diff) {                                                              // DIFF :208-215
@@ -369,6 +391,7 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
                 has_ray = valid;
             } else {
                 // ---- glass, smallpt.cpp:225-263 ----
+                if constexpr (!OLD) cntR += valid ? 1u : 0u;
                 const float4 mfc = s_mat[3 * inst + (depth > 5u ? 2 : 1)];                  // f after the roulette (:192)
                 const f3 f = mk(mfc.x, mfc.y, mfc.z);
                 const f3 off = nl * 0.02f;                                                  // :172 (D3)
@@ -427,8 +450,9 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
         // to 3 * NG spheres with never-hit entries (r*r = -inf: det = -inf, NaN keys), so the loop is fully unrolled
         // without bounds tests; ascending index with strict '<' = lowest index wins ties.
         PH_STAMP(1)
-        nbounce += (unsigned long long)__popcll(__ballot(has_ray));
+        nbounce += (unsigned long long)__popcll(OLD ? __ballot(has_ray) : lanes_where(has_ray));
         uint32_t next = C_GEN;                                   // slots without a continuing path go back to GEN
+        bool to_diff = false, to_refr = false;                   // (trimmed loop: the same as two predicates, whose lane masks the branches below already hold)
         const bool queued = valid && !retired;
         uint32_t near_key = kInfKeyP, inst = 0;
         if (SPT_POOL_NARROW && 3 * NG <= 16 && b <= 4u) {
@@ -564,7 +588,8 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
                         A0[slot] = make_float4(hx.x, hx.y, hx.z, __uint_as_float(rbase));
                         A1[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(pack_path(depth, branchf, inst, refl, sp)));
                         A2[slot] = make_float4(w.x, w.y, w.z, __uint_as_float(k1));
-                        next = refl == 2u ? C_REFR : C_DIFF;
+                        if constexpr (OLD) next = refl == 2u ? C_REFR : C_DIFF;
+                        else { to_refr = refl == 2u; to_diff = !to_refr; }
                     }
                 }
             } else if constexpr (ENV) {                                                     // :168 miss: + w * E, the path's last event
@@ -574,7 +599,20 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
         }
         PH_STAMP(3)
         // ================= push every slot onto the list of its next class =================
-        {
+        if constexpr (!OLD) {
+            // a continuing path is a queued slot (has_ray implies valid and not retired), so the GEN mask is what the other two leave
+            const unsigned long long mq = lanes_where(queued), md = lanes_where(to_diff), mr = lanes_where(to_refr);
+            const unsigned long long mg = mq & ~(md | mr);
+            const bool to_gen = queued && !to_diff && !to_refr;
+            uint32_t pos = nG + rank_in(mg);
+            if (to_diff) pos = (uint32_t)P + nD + rank_in(md);
+            if (to_refr) pos = 2u * (uint32_t)P - 1u - nR - rank_in(mr);
+            if (queued) LG[pos] = (uint8_t)slot;
+            if (to_gen) A1[slot].w = __uint_as_float(sp << 30);
+            nG += (uint32_t)__popcll(mg);
+            nD += (uint32_t)__popcll(md);
+            nR += (uint32_t)__popcll(mr);
+        } else {
             const bool to_gen = queued && next == C_GEN;
             const unsigned long long mg = __ballot(to_gen);
             const unsigned long long md = __ballot(queued && next == C_DIFF);
@@ -595,6 +633,12 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
     // stats: one atomic per wave
     unsigned long long nk = nkill, nr = nrec;
     for (int off = 32; off > 0; off >>= 1) { nk += __shfl_down(nk, off); nr += __shfl_down(nr, off); }
+    if constexpr (!OLD) {
+        const uint32_t cnt = cntG + cntD + cntR, tail = queue_empty ? cnt - cntDry : 0u;
+        itG = uni(cntG); itD = uni(cntD); itR = uni(cntR); itTail = uni(tail);
+        itFull = (uint32_t)__builtin_amdgcn_readlane((int)cnt, 63);
+        lnG = wave_sum(cntG); lnD = wave_sum(cntD); lnR = wave_sum(cntR); lnTail = wave_sum(tail);      // (mod 2^32, like the counters they replace)
+    }
     if (lane == 0) {
         atomicAdd(&K.counters[0], nbounce);
         if (nk) atomicAdd(&K.counters[1], nk);
@@ -618,6 +662,12 @@ __global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const 
         atomicAdd(&K.counters[16], nr);                           // pending-child records written (64 B out, 64 B back in each)
     }
 }
+
+// the product kernel, and the untrimmed loop as a kernel of its own (the product kernels keep their names and their number)
+template <int P, int NG, int SH, typename... EP>
+__global__ __launch_bounds__(kPoolBlock) void poolkernel(const KParams K, const EP... env) { pool_body<P, NG, SH, false, EP...>(K, env...); }
+template <int P, int NG, int SH, typename... EP>
+__global__ __launch_bounds__(kPoolBlock) void poolkernel_untrimmed(const KParams K, const EP... env) { pool_body<P, NG, SH, true, EP...>(K, env...); }
 
 }  // namespace spt
 
@@ -710,50 +760,60 @@ extern "C" int spt_pool_max_spheres(void) { return spt::kMaxUnroll; }
 // 160 slots per wave with the 62-byte slot, 144 with the 70-byte slot: four workgroups (16 waves) per CU either way
 extern "C" int spt_pool_default_slots(void) { return spt::kSharePool; }
 
-template <int P, int NG, int SH>
+template <int P, int NG, int SH, bool OLD, typename... EP>
+static auto* pool_kernel_of()
+{
+    if constexpr (OLD) return &spt::poolkernel_untrimmed<P, NG, SH, EP...>;
+    else return &spt::poolkernel<P, NG, SH, EP...>;
+}
+
+template <int P, int NG, int SH, bool OLD>
 static hipError_t launch_pool(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env)
 {
     if (env) {
         const spt::EParams E{{env[0], env[1], env[2]}};
         lds += 16u;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG, SH, spt::EParams>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        auto* const kernel = pool_kernel_of<P, NG, SH, OLD, spt::EParams>();
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((spt::poolkernel<P, NG, SH, spt::EParams>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K, E);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K, E);
         return hipGetLastError();
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::poolkernel<P, NG, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    auto* const kernel = pool_kernel_of<P, NG, SH, OLD>();
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((spt::poolkernel<P, NG, SH>), dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(spt::kPoolBlock), lds, stream, *K);
     return hipGetLastError();
 }
 
 // Sharing patterns are compiled for the default pool size only (the other sizes are tuning A/B arms) and for the NG each pattern fits
 // (spt::share_compiled): the Cornell-9 pattern at NG = 3, the box prefix at NG >= 2.  The host chose `share` with spt::share_select.
-template <int P, int NG>
+// The untrimmed loop (tuning bit 15) is an A/B arm of the default pool size as well; the other sizes run the trimmed loop only.
+template <int P, int NG, bool OLD = false>
 static hipError_t launch_pool_share(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env, int share)
 {
     if constexpr (P == spt::kSharePool) {
         if constexpr (spt::share_compiled(spt::kShareCornell9, NG))
-            if (share == spt::kShareCornell9) return launch_pool<P, NG, spt::kShareCornell9>(K, blocks, lds, stream, env);
+            if (share == spt::kShareCornell9) return launch_pool<P, NG, spt::kShareCornell9, OLD>(K, blocks, lds, stream, env);
         if constexpr (spt::share_compiled(spt::kShareBox, NG))
-            if (share == spt::kShareBox) return launch_pool<P, NG, spt::kShareBox>(K, blocks, lds, stream, env);
+            if (share == spt::kShareBox) return launch_pool<P, NG, spt::kShareBox, OLD>(K, blocks, lds, stream, env);
     }
     if (share != spt::kShareNone) return hipErrorInvalidValue;
-    return launch_pool<P, NG, spt::kShareNone>(K, blocks, lds, stream, env);
+    return launch_pool<P, NG, spt::kShareNone, OLD>(K, blocks, lds, stream, env);
 }
 
-template <int P>
+template <int P, bool OLD = false>
 static hipError_t launch_pool_ng(const spt::KParams* K, uint32_t blocks, size_t lds, hipStream_t stream, const float* env, int share)
 {
     switch (K->n == 0 ? 1u : (K->n + 2u) / 3u) {
-    case 1: return launch_pool_share<P, 1>(K, blocks, lds, stream, env, share);
-    case 2: return launch_pool_share<P, 2>(K, blocks, lds, stream, env, share);
-    case 3: return launch_pool_share<P, 3>(K, blocks, lds, stream, env, share);
-    case 4: return launch_pool_share<P, 4>(K, blocks, lds, stream, env, share);
-    case 5: return launch_pool_share<P, 5>(K, blocks, lds, stream, env, share);
-    case 6: return launch_pool_share<P, 6>(K, blocks, lds, stream, env, share);
-    case 7: return launch_pool_share<P, 7>(K, blocks, lds, stream, env, share);
-    case 8: return launch_pool_share<P, 8>(K, blocks, lds, stream, env, share);
+    case 1: return launch_pool_share<P, 1, OLD>(K, blocks, lds, stream, env, share);
+    case 2: return launch_pool_share<P, 2, OLD>(K, blocks, lds, stream, env, share);
+    case 3: return launch_pool_share<P, 3, OLD>(K, blocks, lds, stream, env, share);
+    case 4: return launch_pool_share<P, 4, OLD>(K, blocks, lds, stream, env, share);
+    case 5: return launch_pool_share<P, 5, OLD>(K, blocks, lds, stream, env, share);
+    case 6: return launch_pool_share<P, 6, OLD>(K, blocks, lds, stream, env, share);
+    case 7: return launch_pool_share<P, 7, OLD>(K, blocks, lds, stream, env, share);
+    case 8: return launch_pool_share<P, 8, OLD>(K, blocks, lds, stream, env, share);
     default: return hipErrorInvalidValue;
     }
 }
@@ -774,9 +834,13 @@ extern "C" int spt_pool_share_compiled(int pool, uint32_t n, int share)
     return share == spt::kShareNone || (pool == spt::kSharePool && spt::share_compiled(share, ng));
 }
 
-extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env, int share)
+// whether this pool size carries the untrimmed loop of tuning bit 15
+extern "C" int spt_pool_has_old_loop(int pool) { return pool == spt::kSharePool; }
+
+extern "C" hipError_t spt_pool_launch(const spt::KParams* K, uint32_t blocks, int pool, hipStream_t stream, const float* env, int share, int old_loop)
 {
     const size_t lds = spt_pool_lds_bytes(K->n, pool);
+    if (old_loop) return pool == spt::kSharePool ? launch_pool_ng<spt::kSharePool, true>(K, blocks, lds, stream, env, share) : hipErrorInvalidValue;
     if (pool == 128) return launch_pool_ng<128>(K, blocks, lds, stream, env, share);
     if (pool == 160) return launch_pool_ng<160>(K, blocks, lds, stream, env, share);
     if (pool == 144) return launch_pool_ng<144>(K, blocks, lds, stream, env, share);
