@@ -390,8 +390,8 @@ int  spt_render_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uin
  *   progressive buffers); like the render entries it first waits for a pending launch.  It fails on an unknown aov, without a
  *   current scene, for w, h or samps of 0 and for a row band outside the image.
  *   Not covered: the reference's triangle-id view int2color(triId) (:182) -- a fract(sin(x) * 43758) hash that turns one ulp of sin
- *   into 1e-3 of colour, so it cannot be bit-exact --; several buffers per launch; the multi-GPU front; a progressive variant (callers
- *   accumulate the rows output with spt_accumulate_device). */
+ *   into 1e-3 of colour, so it cannot be bit-exact --; the multi-GPU front.  Several buffers of the same samples from one launch, and the
+ *   progressive loop over them: spt_render_aov_set* and spt_progressive_aov_* below. */
 enum { SPT_AOV_NORMAL = 0, SPT_AOV_ALBEDO = 1, SPT_AOV_UV = 2, SPT_AOV_DIST = 3 };
 /* Full w x h buffer to out_rgb (host, w*h*3 floats, row 0 = bottom).  Blocking. */
 int  spt_render_aov(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps_per_cell, uint64_t seed,
@@ -400,6 +400,40 @@ int  spt_render_aov(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h,
  * stream); returns without waiting, as spt_render_rows_device (keys use the global pixel index; call spt_sync() before reading stats). */
 int  spt_render_aov_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
                                 uint32_t samps_per_cell, uint64_t seed, uint32_t aov, uint32_t flags, void* d_out_rgb, void* hip_stream);
+
+/* Sets of first-hit feature buffers: what a denoiser takes -- normal, albedo, distance ... of the SAME samples -- from ONE trace per
+ * sample, plus the two buffers a single kind cannot give: the hit point, and the per-pixel hit count that normalises a silhouette pixel
+ * (a miss adds nothing, so the other buffers of a pixel that half-covers an object are sums over its hits only).
+ *   mask: one or more SPT_AOVSET_* bits (bit k = 1u << SPT_AOV_k for the four kinds above); the outputs are passed as an array of
+ *     popcount(mask) images in ascending bit order.
+ *   Samples, hit and routing: as spt_render_aov, for every scene kind (spheres, meshes, instances) and every accel mode.  Each sample is
+ *     traced ONCE and every selected buffer receives the value of that one Hit.
+ *   Values: NORMAL, ALBEDO, UV and DIST as in spt_render_aov; POSITION = hit.x of the Hit that spt_trace_spheres / spt_trace_rays returns
+ *     for the sample's ray (o + d * dist for spheres, the interpolated vertex position for meshes, the world-space x of
+ *     spt_set_instances' contract for instances); COVERAGE = 1.0f on each channel.
+ *   Accumulation, normalisation, misses: a miss adds nothing to any buffer, COVERAGE included; the D9 order and SPT_FLAG_NORMALISE apply
+ *     per buffer exactly as in spt_render_aov.  Each of the four old kinds of a set is bit-identical to spt_render_aov /
+ *     spt_render_aov_rows_device of that kind with the same arguments.  The un-normalised COVERAGE of a pixel is its hit count (exact in
+ *     float32 up to 2^24 samples): divide the other un-normalised buffers by it for the mean over the hits.
+ *   Stats: samples = rows * w * spp, bounces = samples (one query per sample, not one per buffer), max_depth_kills = 0.
+ *   A call changes no render state, like spt_render_aov.  It fails for mask == 0, for bits above SPT_AOVSET_ALL, for a NULL pointer among
+ *   the selected outputs, and for everything spt_render_aov rejects.
+ *   Not covered: the multi-GPU front; the triangle-id view. */
+#define SPT_AOVSET_NORMAL   1u    /* = 1u << SPT_AOV_NORMAL */
+#define SPT_AOVSET_ALBEDO   2u    /* = 1u << SPT_AOV_ALBEDO */
+#define SPT_AOVSET_UV       4u    /* = 1u << SPT_AOV_UV */
+#define SPT_AOVSET_DIST     8u    /* = 1u << SPT_AOV_DIST */
+#define SPT_AOVSET_POSITION 16u   /* hit.x of the Hit spt_trace_spheres / spt_trace_rays returns for the sample's ray */
+#define SPT_AOVSET_COVERAGE 32u   /* (1, 1, 1) per hit: the pixel's hit count (divide the other buffers by it) */
+#define SPT_AOVSET_ALL      63u
+/* Full w x h buffers to out_rgb[0 .. popcount(mask)) (host, w*h*3 floats each, row 0 = bottom).  Blocking. */
+int  spt_render_aov_set(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps_per_cell, uint64_t seed,
+                        uint32_t mask, uint32_t flags, float* const* out_rgb, spt_stats* stats);
+/* Rows [row_begin, row_begin+row_count) into d_out_rgb[0 .. popcount(mask)) -- a HOST array of DEVICE pointers, row_count*w*3 floats
+ * each --, enqueued on hip_stream (NULL = the context's stream); returns without waiting, as spt_render_aov_rows_device. */
+int  spt_render_aov_set_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                                    uint32_t samps_per_cell, uint64_t seed, uint32_t mask, uint32_t flags, void* const* d_out_rgb,
+                                    void* hip_stream);
 
 /* Progressive accumulation of the viewer's render thread (smallpt.cpp:924-937), device-resident:
  * d_accum[i] = clear ? d_frame[i] : d_accum[i] + d_frame[i] for n floats (both 16-byte aligned, on this device);
@@ -428,6 +462,24 @@ int  spt_progressive_begin(spt_ctx* ctx, uint32_t w, uint32_t h);
 int  spt_progressive_frame(spt_ctx* ctx, const spt_camera* cam, uint32_t samps_per_cell, uint64_t seed, int clear, spt_stats* stats);
 int  spt_progressive_snapshot(spt_ctx* ctx, float* out_rgb);
 int  spt_progressive_end(spt_ctx* ctx);
+/* The same loop over feature buffers -- the reference's viewer as shipped accumulates the first hit's NORMAL frame after frame
+ * (smallpt.cpp:179-183 inside :895-942):
+ *   spt_progressive_aov_begin(ctx, mask)   after spt_progressive_begin: one zeroed w*h*3 accumulation buffer (and a frame) per selected
+ *                            kind on the device; replaces an earlier selection;
+ *   spt_progressive_aov_frame              one spt_render_aov_set launch of the whole image (un-normalised sums) followed by
+ *                            `accum (clear ? = : +=) frame` per kind; blocking; stats as spt_render_aov_set.  It touches neither the
+ *                            radiance accumBuffer nor the render state (chunk-order records, spt_last_kernel).  A viewer that wants beauty
+ *                            and features of the same samples calls spt_progressive_frame and spt_progressive_aov_frame with the same
+ *                            camera, samples and seed;
+ *   spt_progressive_aov_snapshot(ctx, kind_bit, out)   copies the accumulation buffer of ONE selected kind (a single SPT_AOVSET_* bit) to
+ *                            host memory, in spt_progressive_snapshot's layout;
+ *   spt_progressive_end      frees these buffers too.
+ * After any sequence of frames the buffer of kind k holds, bit for bit, the running `clear ? = : +=` float32 sum of
+ * spt_render_aov_rows_device's un-normalised outputs of kind k for the same (camera, samples, seed, clear) sequence: what
+ * spt_accumulate_device computes.  The lanes below stay radiance-only. */
+int  spt_progressive_aov_begin(spt_ctx* ctx, uint32_t mask);
+int  spt_progressive_aov_frame(spt_ctx* ctx, const spt_camera* cam, uint32_t samps_per_cell, uint64_t seed, int clear, spt_stats* stats);
+int  spt_progressive_aov_snapshot(spt_ctx* ctx, uint32_t kind_bit, float* out_rgb);
 /* The same loop with SEVERAL FRAMES IN FLIGHT.  The reference overlaps its render thread with the GL thread (smallpt.cpp:895-962);
  * on the GPU the end of a 4-spp frame is a handful of long specular chains that leave most of the chip idle, so a host that
  * issues frame k+1 before frame k has drained keeps it busy.  A context renders one frame at a time (its scratch buffers belong

@@ -79,6 +79,10 @@ SYMBOLS = {
                                  C.c_uint32, _P, C.POINTER(SptStats)]),
     "spt_render_aov_rows_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                              C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    "spt_render_aov_set": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                     C.c_uint32, C.POINTER(_P), C.POINTER(SptStats)]),
+    "spt_render_aov_set_rows_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_P), _P]),
     "spt_interleaved_row_count": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "spt_render_interleaved_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),
@@ -86,6 +90,9 @@ SYMBOLS = {
     "spt_progressive_begin": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "spt_progressive_frame": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int, C.POINTER(SptStats)]),
     "spt_progressive_snapshot": (C.c_int, [_P, _P]),
+    "spt_progressive_aov_begin": (C.c_int, [_P, C.c_uint32]),
+    "spt_progressive_aov_frame": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int, C.POINTER(SptStats)]),
+    "spt_progressive_aov_snapshot": (C.c_int, [_P, C.c_uint32, _P]),
     "spt_progressive_attach": (C.c_int, [_P, _P]),
     "spt_progressive_frame_async": (C.c_int, [_P, _P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int]),
     "spt_progressive_wait": (C.c_int, [_P, C.POINTER(SptStats)]),

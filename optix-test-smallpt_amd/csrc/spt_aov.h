@@ -6,7 +6,10 @@
 //   * aov_camera_ray: the camera ray of one sample -- the expression tree of the render kernels' generators (spt_kernel.hip phase C1,
 //     spt_pool.hip, spt_mesh.hip meshkernel; smallpt.cpp:325-340 / :745-760), same keys (D7), so a buffer lines up sample for sample with
 //     the radiance render of the same seed;
-//   * aov_add: the value a hit adds (normal, albedo, uv, distance), in float32, samples in ascending order.
+//   * aov_add: the value a hit adds (normal, albedo, uv, distance), in float32, samples in ascending order;
+//   * f3 / AovSet: what a launch keeps of a sample's Hit -- the one kind of spt_render_aov, or every kind of a SPT_AOVSET_* mask
+//     (spt_render_aov_set: one trace per sample, one accumulator and one plane of cells per selected kind).  The kernels are written once
+//     over either accumulator (profiles/r06_aov_set.txt: what that did to the single-kind kernels' code).
 #ifndef SPT_AOV_H
 #define SPT_AOV_H
 #include "spt_kernel.h"
@@ -16,7 +19,7 @@
 
 namespace spt {
 
-enum : uint32_t { kAovNormal = 0, kAovAlbedo = 1, kAovUv = 2, kAovDist = 3 };
+enum : uint32_t { kAovNormal = 0, kAovAlbedo = 1, kAovUv = 2, kAovDist = 3, kAovPosition = 4, kAovCoverage = 5, kAovKinds = 6 };
 constexpr uint32_t kAovBlock = 256;                    // threads per workgroup of the AOV kernels other than the grid's
 
 // Task `task` of the launch (task id = ((local pixel * 4 + cell) << nb_log2) | block, as in the render kernels).
@@ -89,12 +92,57 @@ __device__ __forceinline__ f3 aov_add(f3 acc, uint32_t kind, f3 n, float4 colour
     return acc + x;
 }
 
+// The accumulator of a launch: f3 for the one kind of spt_render_aov (`kind` = SPT_AOV_*, aov_add above, cells[task]), AovSet for a set
+// (`kind` = a SPT_AOVSET_* mask: bit k selects kind k; spt_render_aov_set).  A set launch adds the value of EVERY kind per hit and consults
+// the mask only where it stores: the sample loop carries no test of the mask (the kernels have no scalar register to spare for one) and the
+// handful of additions is nothing beside a walk.  Channels that always hold the same number share a register -- uv.z stays +0, the three of
+// DIST and of COVERAGE are equal --, 13 VGPRs in all; each stored channel is the float32 sum, in sample order, that the single kind makes.
+// POSITION adds the Hit's x, COVERAGE 1 per hit.  Plane j of the launch (the j-th selected kind, ascending) is cells[j * ntasks .. (j + 1) * ntasks).
+struct AovSet { f3 n, albedo, x; float u, v, dist, cover; };
+
+template <class ACC> __device__ __forceinline__ ACC aov_zero();
+template <> __device__ __forceinline__ f3 aov_zero<f3>() { return mk(0, 0, 0); }
+template <> __device__ __forceinline__ AovSet aov_zero<AovSet>() { return AovSet{mk(0, 0, 0), mk(0, 0, 0), mk(0, 0, 0), 0.0f, 0.0f, 0.0f, 0.0f}; }
+
+// does a hit's value need the material colour?
+template <class ACC> __device__ __forceinline__ bool aov_albedo(uint32_t kind);
+template <> __device__ __forceinline__ bool aov_albedo<f3>(uint32_t kind) { return kind == kAovAlbedo; }
+template <> __device__ __forceinline__ bool aov_albedo<AovSet>(uint32_t) { return true; }
+// waves per SIMD a kernel over ACC asks the compiler for (0 = no request: the single-kind kernels fit four by themselves)
+template <class ACC> inline constexpr unsigned kAovWaves = std::is_same<ACC, AovSet>::value ? 4u : 0u;
+
+__device__ __forceinline__ f3 aov_add(f3 acc, uint32_t kind, f3 n, float4 colour, float u, float v, float dist, f3) { return aov_add(acc, kind, n, colour, u, v, dist); }
+__device__ __forceinline__ AovSet aov_add(AovSet a, uint32_t, f3 n, float4 colour, float u, float v, float dist, f3 x)
+{
+    a.n = a.n + n;
+    a.albedo = a.albedo + mk(colour.x, colour.y, colour.z);
+    a.u += u; a.v += v;
+    a.dist += dist;
+    a.x = a.x + x;
+    a.cover += 1.0f;
+    return a;
+}
+
+__device__ __forceinline__ void aov_store(float4* cells, uint32_t task, uint32_t, uint32_t, f3 acc) { cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f); }
+__device__ __forceinline__ void aov_store(float4* cells, uint32_t task, uint32_t ntasks, uint32_t mask, AovSet a)
+{
+    const float4 plane[kAovKinds] = {make_float4(a.n.x, a.n.y, a.n.z, 0.0f), make_float4(a.albedo.x, a.albedo.y, a.albedo.z, 0.0f), make_float4(a.u, a.v, 0.0f, 0.0f),
+                                     make_float4(a.dist, a.dist, a.dist, 0.0f), make_float4(a.x.x, a.x.y, a.x.z, 0.0f), make_float4(a.cover, a.cover, a.cover, 0.0f)};
+    asm volatile("" : "+s"(mask));     // the bits are tested here: hoisted out of a kernel's loops, the six tests would each hold a 64-bit scalar mask
+    size_t at = task;
+#pragma unroll
+    for (uint32_t k = 0; k < kAovKinds; ++k)
+        if ((mask >> k) & 1u) { cells[at] = plane[k]; at += ntasks; }
+}
+
 }  // namespace spt
 #endif
 
 // Launchers (spt_grid.hip, spt_mesh.hip).  K: camera, band, D9 layout, seed hashes, sphere table (geom / mat / n), cells; the task queue
-// and counters are not used.  Every launcher writes K.cells[0 .. K.ntasks) and nothing else.
+// and counters are not used.  kind: SPT_AOV_* (0 .. 3) writes K.cells[0 .. K.ntasks); spt_aov_set | mask (a SPT_AOVSET_* mask, not 0) writes
+// popcount(mask) planes of K.ntasks cells each.  Nothing else is written.
 namespace spt { struct MParams; struct GridParams; }
+constexpr uint32_t spt_aov_set = 0x80000000u;
 extern "C" hipError_t spt_aov_exhaustive_launch(const spt::KParams* K, uint32_t kind, int guard_all, hipStream_t stream);
 extern "C" hipError_t spt_aov_grid_launch(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs,
                                           const uint32_t* d_always, int where, uint32_t kind, uint32_t blocks, hipStream_t stream);

@@ -115,6 +115,8 @@ struct spt_ctx {
     float* d_accum = nullptr;      // spt_progressive_*: accumBuffer (smallpt.cpp:881-883) and the current frame, w*h*3 floats each
     float* d_frame = nullptr;
     uint32_t prog_w = 0, prog_h = 0;
+    uint32_t aov_mask = 0;         // spt_progressive_aov_*: the selected kinds; per kind an accumulation buffer and a frame, w*h*3 floats each
+    float* d_aov_accum[6] = {}; float* d_aov_frame[6] = {};
     hipEvent_t ev_acc = nullptr;   // owner of an accumBuffer: completion of the most recent accumulation (any lane's stream)
     bool acc_recorded = false;
     bool frame_in_flight = false;  // a spt_progressive_frame_async of this lane has not been waited for
@@ -227,6 +229,16 @@ int spt_create(int device_id, spt_ctx** out)
     return 0;
 }
 
+static void progressive_aov_free(spt_ctx* c)
+{
+    for (int k = 0; k < 6; ++k) {
+        if (c->d_aov_accum[k]) (void)hipFree(c->d_aov_accum[k]);
+        if (c->d_aov_frame[k]) (void)hipFree(c->d_aov_frame[k]);
+        c->d_aov_accum[k] = c->d_aov_frame[k] = nullptr;
+    }
+    c->aov_mask = 0;
+}
+
 void spt_destroy(spt_ctx* c)
 {
     if (!c) return;
@@ -240,6 +252,7 @@ void spt_destroy(spt_ctx* c)
     if (c->d_stack) (void)hipFree(c->d_stack);
     if (c->d_accum) (void)hipFree(c->d_accum);
     if (c->d_frame) (void)hipFree(c->d_frame);
+    progressive_aov_free(c);
     if (c->d_tris) (void)hipFree(c->d_tris);
     if (c->d_tri_index) (void)hipFree(c->d_tri_index);
     if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
@@ -1938,11 +1951,18 @@ int spt_render(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32
 // (spt_trace_spheres / spt_trace_rays), folded by spt_k_finalize.  Shares the render scratch (cells) and the launch events, so it waits for a
 // pending launch and the next launch waits for it; the render state (chunk order, SPT_ACCEL_AUTO's bounce share, spt_last_kernel, the
 // progressive buffers) is left alone.  A pending RENDER is completed first as spt_sync would complete it, so that its bookkeeping is kept.
+// set = false: aov is a SPT_AOV_* kind and d_out[0] its image.  set = true (spt_render_aov_set*): aov is a SPT_AOVSET_* mask and d_out holds
+// one image per selected kind in ascending bit order; the one launch writes a plane of cells per kind and spt_k_finalize folds each plane.
 static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
-                           uint32_t samps, uint64_t seed, uint32_t aov, uint32_t flags, void* d_out_rgb, void* hip_stream)
+                           uint32_t samps, uint64_t seed, bool set, uint32_t aov, uint32_t flags, void* const* d_out, void* hip_stream)
 {
-    if (!cam || !d_out_rgb) return c->fail("%s: NULL argument", who);
-    if (aov > SPT_AOV_DIST) return c->fail("%s: unknown aov %u (SPT_AOV_NORMAL, _ALBEDO, _UV or _DIST)", who, aov);
+    if (!cam || !d_out) return c->fail("%s: NULL argument", who);
+    uint32_t nplanes = 1;
+    if (set) {
+        if (aov == 0 || aov > SPT_AOVSET_ALL) return c->fail("%s: bad mask 0x%x (one or more of SPT_AOVSET_NORMAL .. SPT_AOVSET_COVERAGE)", who, aov);
+        nplanes = (uint32_t)__builtin_popcount(aov);
+    } else if (aov > SPT_AOV_DIST) return c->fail("%s: unknown aov %u (SPT_AOV_NORMAL, _ALBEDO, _UV or _DIST)", who, aov);
+    for (uint32_t j = 0; j < nplanes; ++j) if (!d_out[j]) return c->fail("%s: NULL argument", who);
     if (!c->d_geom && !c->mesh_scene) return c->fail("%s: no scene set (call spt_set_scene or spt_set_meshes)", who);
     if (w == 0 || h == 0 || samps == 0) return c->fail("%s: empty image or samps == 0", who);
     if (row_count == 0 || (uint64_t)row_begin + row_count > h) return c->fail("%s: row band [%u,+%u) outside image height %u", who, row_begin, row_count, h);
@@ -1960,12 +1980,13 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
         else SPT_HIP(c, hipEventSynchronize(c->ev_stop));
     }
     const size_t ntasks = (size_t)npix * 4 * nb;
-    if (ntasks > c->cells_cap) {
+    if (ntasks * nplanes > c->cells_cap) {
         if (c->d_cells) (void)hipFree(c->d_cells);
         c->d_cells = nullptr; c->cells_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cells), ntasks * sizeof(float4)));
-        c->cells_cap = ntasks;
+        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cells), ntasks * nplanes * sizeof(float4)));
+        c->cells_cap = ntasks * nplanes;
     }
+    if (set) aov |= spt_aov_set;
     spt::KParams P{};
     std::memcpy(P.cam_o, cam->origin, 12); std::memcpy(P.cam_d, cam->dir, 12);
     std::memcpy(P.cam_cx, cam->cx, 12); std::memcpy(P.cam_cy, cam->cy, 12);
@@ -2014,7 +2035,8 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
         SPT_HIP(c, spt_aov_inst_launch(&P, &M, &I, mesh_mode(c, false) != SPT_ACCEL_EXHAUSTIVE, aov, st));
     } else SPT_HIP(c, spt_aov_mesh_launch(&P, &M, aov, st));
     SPT_HIP(c, hipEventRecord(c->ev_mid, st));
-    SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, 1.0f / (float)(4u * samps), (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
+    for (uint32_t j = 0; j < nplanes; ++j)
+        SPT_HIP(c, spt_k_finalize(c->d_cells + j * ntasks, static_cast<float*>(d_out[j]), (uint32_t)npix, 1.0f / (float)(4u * samps), (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
     SPT_HIP(c, hipEventRecord(c->ev_stop, st));
     c->pending = true;
     c->last_aov = true;
@@ -2029,7 +2051,7 @@ int spt_render_aov_rows_device(spt_ctx* c, const spt_camera* cam, uint32_t w, ui
                                uint32_t samps, uint64_t seed, uint32_t aov, uint32_t flags, void* d_out_rgb, void* hip_stream)
 {
     if (!c) return 1;
-    return render_aov_impl(c, "spt_render_aov_rows_device", cam, w, h, row_begin, row_count, samps, seed, aov, flags, d_out_rgb, hip_stream);
+    return render_aov_impl(c, "spt_render_aov_rows_device", cam, w, h, row_begin, row_count, samps, seed, false, aov, flags, &d_out_rgb, hip_stream);
 }
 
 int spt_render_aov(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps, uint64_t seed, uint32_t aov, uint32_t flags,
@@ -2047,8 +2069,48 @@ int spt_render_aov(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, ui
         SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), nfl * sizeof(float)));
         c->out_cap = nfl;
     }
-    if (int rc = render_aov_impl(c, "spt_render_aov", cam, w, h, 0, h, samps, seed, aov, flags, c->d_out, nullptr)) return rc;
+    void* const d_out = c->d_out;
+    if (int rc = render_aov_impl(c, "spt_render_aov", cam, w, h, 0, h, samps, seed, false, aov, flags, &d_out, nullptr)) return rc;
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (int rc = spt_sync(c, nullptr)) return rc;
+    c->last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = c->last;
+    return 0;
+}
+
+// ---- several feature buffers of the same samples from one launch (SPT_AOVSET_*) ----
+int spt_render_aov_set_rows_device(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                                   uint32_t samps, uint64_t seed, uint32_t mask, uint32_t flags, void* const* d_out_rgb, void* hip_stream)
+{
+    if (!c) return 1;
+    return render_aov_impl(c, "spt_render_aov_set_rows_device", cam, w, h, row_begin, row_count, samps, seed, true, mask, flags, d_out_rgb, hip_stream);
+}
+
+int spt_render_aov_set(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps, uint64_t seed, uint32_t mask, uint32_t flags,
+                       float* const* out_rgb, spt_stats* stats)
+{
+    if (!c) return 1;
+    if (!out_rgb) return c->fail("spt_render_aov_set: out_rgb is NULL");
+    if (mask == 0 || mask > SPT_AOVSET_ALL) return c->fail("spt_render_aov_set: bad mask 0x%x (one or more of SPT_AOVSET_NORMAL .. SPT_AOVSET_COVERAGE)", mask);
+    const uint32_t nplanes = (uint32_t)__builtin_popcount(mask);
+    for (uint32_t j = 0; j < nplanes; ++j) if (!out_rgb[j]) return c->fail("spt_render_aov_set: out_rgb[%u] is NULL", j);
+    if (w == 0 || h == 0 || samps == 0) return c->fail("spt_render_aov_set: empty image or samps == 0");   // (before the staging buffer: none is allocated for it)
+    const auto t0 = std::chrono::steady_clock::now();
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t nfl = (size_t)w * h * 3, pitch = (nfl + 3) & ~(size_t)3;       // every plane of the staging buffer 16-byte aligned
+    if (pitch * nplanes > c->out_cap) {
+        if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+        if (c->d_out) (void)hipFree(c->d_out);
+        c->d_out = nullptr; c->out_cap = 0;
+        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), pitch * nplanes * sizeof(float)));
+        c->out_cap = pitch * nplanes;
+    }
+    void* d_out[6];
+    for (uint32_t j = 0; j < nplanes; ++j) d_out[j] = c->d_out + j * pitch;
+    if (int rc = render_aov_impl(c, "spt_render_aov_set", cam, w, h, 0, h, samps, seed, true, mask, flags, d_out, nullptr)) return rc;
+    for (uint32_t j = 0; j < nplanes; ++j)
+        SPT_HIP(c, hipMemcpyAsync(out_rgb[j], d_out[j], nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     if (int rc = spt_sync(c, nullptr)) return rc;
     c->last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -2081,6 +2143,7 @@ int spt_progressive_end(spt_ctx* c)
     if (c->d_accum) (void)hipFree(c->d_accum);
     if (c->d_frame) (void)hipFree(c->d_frame);
     c->d_accum = c->d_frame = nullptr;
+    progressive_aov_free(c);
     c->prog_w = c->prog_h = 0;
     c->acc_recorded = false;
     c->frame_in_flight = false;
@@ -2185,6 +2248,58 @@ int spt_progressive_snapshot(spt_ctx* c, float* out_rgb)
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_accum, (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the same loop over feature buffers: the reference's viewer as shipped accumulates the first hit's normal (smallpt.cpp:179-183 inside
+// :895-942).  One accumulation buffer and one frame per selected kind; the radiance accumBuffer and the render state are not touched. ----
+int spt_progressive_aov_begin(spt_ctx* c, uint32_t mask)
+{
+    if (!c) return 1;
+    if (!c->d_accum) return c->fail("spt_progressive_aov_begin: call spt_progressive_begin first");
+    if (c->attached_to) return c->fail("spt_progressive_aov_begin: lanes accumulate radiance only");
+    if (mask == 0 || mask > SPT_AOVSET_ALL) return c->fail("spt_progressive_aov_begin: bad mask 0x%x (one or more of SPT_AOVSET_NORMAL .. SPT_AOVSET_COVERAGE)", mask);
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    progressive_aov_free(c);
+    const size_t bytes = (size_t)c->prog_w * c->prog_h * 3 * sizeof(float);
+    for (uint32_t k = 0; k < 6; ++k) {
+        if (!((mask >> k) & 1u)) continue;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_aov_accum[k]), bytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_aov_frame[k]), bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_aov_accum[k], 0, bytes, c->stream);
+        if (e != hipSuccess) { progressive_aov_free(c); return c->fail("spt_progressive_aov_begin: %s", hipGetErrorString(e)); }
+    }
+    c->aov_mask = mask;
+    return 0;
+}
+
+int spt_progressive_aov_frame(spt_ctx* c, const spt_camera* cam, uint32_t samps, uint64_t seed, int clear, spt_stats* stats)
+{
+    if (!c) return 1;
+    if (!c->aov_mask) return c->fail("spt_progressive_aov_frame: call spt_progressive_aov_begin first");
+    if (c->frame_in_flight) return c->fail("spt_progressive_aov_frame: a radiance frame of this context has not been waited for");
+    void* frames[6];
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < 6; ++k) if ((c->aov_mask >> k) & 1u) frames[n++] = c->d_aov_frame[k];
+    if (int rc = render_aov_impl(c, "spt_progressive_aov_frame", cam, c->prog_w, c->prog_h, 0, c->prog_h, samps, seed, true, c->aov_mask, 0u, frames, nullptr)) return rc;
+    for (uint32_t k = 0; k < 6; ++k)
+        if ((c->aov_mask >> k) & 1u)
+            SPT_HIP(c, spt_k_accumulate(c->d_aov_accum[k], c->d_aov_frame[k], (size_t)c->prog_w * c->prog_h * 3, clear, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return spt_sync(c, stats);
+}
+
+int spt_progressive_aov_snapshot(spt_ctx* c, uint32_t kind_bit, float* out_rgb)
+{
+    if (!c) return 1;
+    if (!out_rgb) return c->fail("spt_progressive_aov_snapshot: out_rgb is NULL");
+    if (kind_bit == 0 || (kind_bit & (kind_bit - 1u)) || !(kind_bit & c->aov_mask))
+        return c->fail("spt_progressive_aov_snapshot: 0x%x is not one kind of the mask 0x%x given to spt_progressive_aov_begin", kind_bit, c->aov_mask);
+    SPT_HIP(c, hipSetDevice(c->device));
+    const int k = __builtin_ctz(kind_bit);
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_aov_accum[k], (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }

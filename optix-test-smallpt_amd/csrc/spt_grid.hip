@@ -975,12 +975,13 @@ __device__ __forceinline__ uint32_t aov_task_at(const KParams& K, uint32_t q, ui
     return task < K.ntasks ? task : 0xFFFFFFFFu;
 }
 
-// value of a sphere hit (Sphere::makeHit, scene.cpp:118-127: n = normalize(x - centre), uv = 0) added to acc
-__device__ __forceinline__ f3 aov_sphere_add(const KParams& K, uint32_t kind, f3 acc, uint32_t i, float t, const float4 g, f3 o, f3 d)
+// value of a sphere hit (Sphere::makeHit, scene.cpp:118-127: x = o + d t, n = normalize(x - centre), uv = 0) added to the launch's selection
+template <class ACC>
+__device__ __forceinline__ ACC aov_sphere_add(const KParams& K, uint32_t kind, ACC acc, uint32_t i, float t, const float4 g, f3 o, f3 d)
 {
     const QueryHit h = query_hit(true, i, t, g, o, d);
-    const float4 colour = kind == kAovAlbedo ? K.mat[3 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-    return aov_add(acc, kind, mk(h.f[6], h.f[7], h.f[8]), colour, 0.0f, 0.0f, t);
+    const float4 colour = aov_albedo<ACC>(kind) ? K.mat[3 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+    return aov_add(acc, kind, mk(h.f[6], h.f[7], h.f[8]), colour, 0.0f, 0.0f, t, mk(h.f[3], h.f[4], h.f[5]));
 }
 
 template <bool GUARD>
@@ -992,6 +993,8 @@ __device__ __forceinline__ void aov_sphere_loop(const float4* s_geom, uint32_t n
     }
 }
 
+// ACC: f3 (kind = SPT_AOV_*) or AovSet (kind = a SPT_AOVSET_* mask), spt_aov.h
+template <class ACC>
 __global__ __launch_bounds__(kAovBlock) void aov_exhaustive(const KParams K, uint32_t kind, int guard_all)
 {
     extern __shared__ float4 s_aov_geom[];
@@ -1002,7 +1005,7 @@ __global__ __launch_bounds__(kAovBlock) void aov_exhaustive(const KParams K, uin
     const bool valid = task != 0xFFFFFFFFu;
     AovTask a{};
     if (valid) a = aov_task(K, task);
-    f3 acc = mk(0, 0, 0);
+    ACC acc = aov_zero<ACC>();
     for (uint32_t s = a.s_begin; __ballot(valid && s < a.s_end) != 0ull; ++s) {     // wave-uniform
         const bool active = valid && s < a.s_end;
         f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
@@ -1016,14 +1019,14 @@ __global__ __launch_bounds__(kAovBlock) void aov_exhaustive(const KParams K, uin
         if (active && near_key != kGInfKey)                                         // a miss adds nothing (smallpt.cpp:168)
             acc = aov_sphere_add(K, kind, acc, near_i, __uint_as_float(near_key + kGEpsBias), s_aov_geom[near_i], o, d);
     }
-    if (valid) K.cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    if (valid) aov_store(K.cells, task, K.ntasks, kind, acc);
 }
 
 // Through the grid: persistent workgroups of kGridBlock threads share one LDS copy of the tables (WHERE as in gridkernel), a wave takes 64
 // queue positions at a time.  Per sample, as query_grid does for a caller's ray: query_ray_route, the always-list, then the walk -- an
 // iteration TESTS the next sphere of the lane's cell or STEPS to the next cell, whichever more lanes want.  A ray the route refuses (a far
 // or pushed camera origin) or whose walk ends beyond t_ok runs the exhaustive loop in its lane over the global table (guarded square root).
-template <int WHERE>
+template <int WHERE, class ACC>
 __global__ __launch_bounds__(kGridBlock) void aov_grid(const KParams K, const GridParams G, const uint32_t* __restrict__ g_cells,
                                                        const uint16_t* __restrict__ g_refs, const uint32_t* __restrict__ g_always, uint32_t kind)
 {
@@ -1055,7 +1058,7 @@ __global__ __launch_bounds__(kGridBlock) void aov_grid(const KParams K, const Gr
         const bool valid = task != 0xFFFFFFFFu;
         AovTask a{};
         if (valid) a = aov_task(K, task);
-        f3 acc = mk(0, 0, 0);
+        ACC acc = aov_zero<ACC>();
         for (uint32_t s = a.s_begin; __ballot(valid && s < a.s_end) != 0ull; ++s) {
             const bool active = valid && s < a.s_end;
             f3 o = mk(0, 0, 0), d = mk(0, 0, 1);
@@ -1124,7 +1127,11 @@ __global__ __launch_bounds__(kGridBlock) void aov_grid(const KParams K, const Gr
             if (active && near_key != kGInfKey)
                 acc = aov_sphere_add(K, kind, acc, near_i, __uint_as_float(near_key + kGEpsBias), geom_at(near_i), o, d);
         }
-        if (valid) K.cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+        if constexpr (std::is_same<ACC, AovSet>::value) {         // a set: the cells pointer, too, comes from the argument segment here
+            KArg* kc = (KArg*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kc));
+            if (valid) aov_store(kc->cells, task, kc->ntasks, kind, acc);
+        } else if (valid) aov_store(K.cells, task, K.ntasks, kind, acc);
     }
 }
 
@@ -1217,9 +1224,15 @@ extern "C" hipError_t spt_aov_exhaustive_launch(const spt::KParams* K, uint32_t 
     const size_t lds = (size_t)(K->n ? K->n : 1u) * sizeof(float4);
     const uint32_t qend = spt::deal_tiles_end(K->w, K->row_count, 4u << K->nb_log2);
     const uint32_t blocks = (uint32_t)(((uint64_t)qend + spt::kAovBlock - 1) / spt::kAovBlock);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_exhaustive), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (kind & spt_aov_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_exhaustive<spt::AovSet>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(spt::aov_exhaustive<spt::AovSet>, dim3(blocks), dim3(spt::kAovBlock), lds, stream, *K, kind & ~spt_aov_set, guard_all);
+        return hipGetLastError();
+    }
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_exhaustive<spt::f3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(spt::aov_exhaustive, dim3(blocks), dim3(spt::kAovBlock), lds, stream, *K, kind, guard_all);
+    hipLaunchKernelGGL(spt::aov_exhaustive<spt::f3>, dim3(blocks), dim3(spt::kAovBlock), lds, stream, *K, kind, guard_all);
     return hipGetLastError();
 }
 
@@ -1227,9 +1240,15 @@ template <int WHERE>
 static hipError_t launch_aov_grid(const spt::KParams* K, const spt::GridParams* G, const uint32_t* d_cells, const uint16_t* d_refs, const uint32_t* d_always,
                                   uint32_t kind, uint32_t blocks, size_t lds, hipStream_t stream)
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_grid<WHERE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (kind & spt_aov_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_grid<WHERE, spt::AovSet>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((spt::aov_grid<WHERE, spt::AovSet>), dim3(blocks), dim3(spt::kGridBlock), lds, stream, *K, *G, d_cells, d_refs, d_always, kind & ~spt_aov_set);
+        return hipGetLastError();
+    }
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spt::aov_grid<WHERE, spt::f3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((spt::aov_grid<WHERE>), dim3(blocks), dim3(spt::kGridBlock), lds, stream, *K, *G, d_cells, d_refs, d_always, kind);
+    hipLaunchKernelGGL((spt::aov_grid<WHERE, spt::f3>), dim3(blocks), dim3(spt::kGridBlock), lds, stream, *K, *G, d_cells, d_refs, d_always, kind);
     return hipGetLastError();
 }
 

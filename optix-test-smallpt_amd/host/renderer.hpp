@@ -57,6 +57,21 @@ public:
         return out;
     }
 
+    // Several feature buffers of the same samples from ONE launch (spt_render_aov_set): mask = SPT_AOVSET_* bits (the four kinds above,
+    // POSITION = the hit point, COVERAGE = 1 per hit); one image per selected kind, in ascending bit order.
+    std::vector<std::vector<float3>> renderAovSet(const spt_camera& camera, size_t imageWidth, size_t imageHeight, size_t sampleCountPerJitterCell,
+                                                  size_t seed, uint32_t mask, bool normalise = false)
+    {
+        std::vector<std::vector<float3>> out;
+        std::vector<float*> ptrs;
+        for (uint32_t k = 0; k < 6; ++k)
+            if ((mask >> k) & 1u) out.emplace_back(imageWidth * imageHeight);
+        for (auto& image : out) ptrs.push_back(reinterpret_cast<float*>(image.data()));
+        check(spt_render_aov_set(ctx_, &camera, (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)sampleCountPerJitterCell, (uint64_t)seed,
+                                 mask, normalise ? SPT_FLAG_NORMALISE : 0u, ptrs.data(), &stats_));
+        return out;
+    }
+
     // accumBuffer of the viewer loop in HBM (spt_progressive_*, smallpt.cpp:881-883,922-937,955-959)
     void progressiveBegin(size_t w, size_t h) { check(spt_progressive_begin(ctx_, (uint32_t)w, (uint32_t)h)); }
     void progressiveFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool clear)

@@ -6,8 +6,11 @@
 //   smallpt_mi355x [spp] [--scene file.json | shipped-meshes] [--size WxH] [--seed N] [--out image.ppm] [--device D]
 //                  [--dump-scene out.json] [--parse-only]
 //                  [--accel grid|bvh|bvh-fast|exhaustive]             closest hit of sphere tables above 24 (default grid) / mesh scenes (default bvh)
-//                  [--aov normal|albedo|uv|dist]                  first-hit feature buffer instead of radiance (spt_render_aov); with
+//                  [--aov normal|albedo|uv|dist|position|coverage] first-hit feature buffer instead of radiance (spt_render_aov; position and
+//                                                              coverage through spt_render_aov_set with that one kind); with
 //                                                              --single-triangle --aov normal: the reference program's own image (smallpt.cpp:179-183)
+//                  [--aov kind,kind,...]                          several buffers of the same samples from one launch (spt_render_aov_set):
+//                                                              --out img.ppm writes img.<kind>.ppm per kind
 //                  [--devices 0,1,...] [--self-exchange]      row bands over several GPUs + RCCL exchange (MultiRenderer)
 //                  [--env r,g,b] [--print-environment]         radiance of escaped paths (overrides the scene file's "environment"); print it
 //                                                              as loaded and overridden, then exit (host only)
@@ -16,6 +19,7 @@
 //                  [--dump-raw accum.bin]                      main()'s progressive loop (smallpt.cpp:840-1005) without the
 //                                                              window: N frames, then the request(s), then M frames; writes the
 //                                                              normalised image like the exit path (:995-1004)
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -33,6 +37,8 @@
 
 using namespace spt_host;
 
+static const char* const kAovNames[6] = {"normal", "albedo", "uv", "dist", "position", "coverage"};   // bit k of SPT_AOVSET_*
+
 int main(int argc, char* argv[])
 {
     int spp = 4, w = 256, h = 256, device = 0;       // smallpt.cpp:274-276 defaults
@@ -43,6 +49,8 @@ int main(int argc, char* argv[])
     std::string scene_path, out_path = "image.ppm", dump_path;
     bool single_triangle = false;
     int aov = -1;                                  // --aov: SPT_AOV_* (-1: radiance)
+    uint32_t aov_mask = 0;                         // --aov with a comma list, or position / coverage alone: SPT_AOVSET_* bits (spt_render_aov_set)
+    bool aov_list = false;                         // a comma list: one file per kind (a kind alone is written to --out itself)
     bool parse_only = false, viewer = false, threaded = false, self_exchange = false;
     int frames = 1, frames_after = 0;
     std::vector<int> devices;
@@ -74,7 +82,21 @@ int main(int argc, char* argv[])
         else if (a == "--pipeline") { pipeline = std::atoi(next()); if (pipeline < 1 || pipeline > 8) { std::fprintf(stderr, "--pipeline 1..8\n"); return 2; } }
         else if (a == "--bench-frames") bench_frames = std::atoi(next());
         else if (a == "--watchdog") watchdog = std::atof(next());
-        else if (a == "--aov") { const std::string m = next(); if (m == "normal") aov = SPT_AOV_NORMAL; else if (m == "albedo") aov = SPT_AOV_ALBEDO; else if (m == "uv") aov = SPT_AOV_UV; else if (m == "dist") aov = SPT_AOV_DIST; else { std::fprintf(stderr, "--aov normal|albedo|uv|dist\n"); return 2; } }
+        else if (a == "--aov") {
+            const std::string m = next();                         // one kind, or a comma list (a set: one launch, one file per kind)
+            aov_list = m.find(',') != std::string::npos;
+            aov_mask = 0;
+            for (size_t b = 0; b <= m.size();) {
+                const size_t e = std::min(m.find(',', b), m.size());
+                int k = -1;
+                for (int j = 0; j < 6; ++j) if (m.compare(b, e - b, kAovNames[j]) == 0) k = j;
+                if (k < 0 || ((aov_mask >> k) & 1u)) { std::fprintf(stderr, "--aov normal|albedo|uv|dist|position|coverage, or a comma list of those (each once, no empty entry)\n"); return 2; }
+                aov_mask |= 1u << k;
+                aov = k;
+                b = e + 1;
+            }
+            if (!aov_list && aov < 4) aov_mask = 0;               // one of the four old kinds alone: spt_render_aov, as before
+        }
         else if (a == "--single-triangle") single_triangle = true;   // SingleTriangleScene of main(), smallpt.cpp:818-832
         else if (a == "--viewer") viewer = true;
         else if (a == "--threaded") threaded = true;
@@ -208,14 +230,29 @@ int main(int argc, char* argv[])
         Renderer renderer(device);
         upload(renderer);
         renderer.setOneShot(true);                               // cpuRender renders its view once
-        std::vector<float3> c = aov >= 0 ? renderer.renderAov(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, (uint32_t)aov, /*normalise=*/true)
+        std::vector<std::vector<float3>> set;
+        if (aov_mask) set = renderer.renderAovSet(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, aov_mask, /*normalise=*/true);
+        std::vector<float3> c = aov_mask ? std::vector<float3>() : aov >= 0 ? renderer.renderAov(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, (uint32_t)aov, /*normalise=*/true)
                                          : renderer.render(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, /*normalise=*/true);
         const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
         const spt_stats& st = renderer.stats();
         std::fprintf(stderr, "Rendering (%d spp) 100.00%%\nElapsed time: %lld ms\n", samps * 4, (long long)ms);   // :368,373
         std::fprintf(stderr, "kernel %.3f ms, %.1f Msamples/s, %.3f bounces/sample, grid %u x %u\n", st.kernel_ms,
                      st.samples / (st.kernel_ms * 1e3), (double)st.bounces / (double)st.samples, st.grid_blocks, st.block_threads);
-        if (spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(c.data()), (uint32_t)w, (uint32_t)h)) {  // :375-376
+        if (aov_mask && !aov_list) c.swap(set[0]);               // position or coverage alone: --out itself, like the four old kinds
+        if (aov_mask && aov_list) {                              // img.ppm -> img.normal.ppm, img.albedo.ppm, ...
+            const size_t dot = out_path.rfind('.');
+            const bool ext = dot != std::string::npos && out_path.find('/', dot) == std::string::npos;
+            size_t j = 0;
+            for (int k = 0; k < 6; ++k) {
+                if (!((aov_mask >> k) & 1u)) continue;
+                const std::string path = (ext ? out_path.substr(0, dot) : out_path) + "." + kAovNames[k] + (ext ? out_path.substr(dot) : std::string());
+                if (spt_write_ppm(path.c_str(), reinterpret_cast<const float*>(set[j++].data()), (uint32_t)w, (uint32_t)h)) {
+                    std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                    return 1;
+                }
+            }
+        } else if (spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(c.data()), (uint32_t)w, (uint32_t)h)) {  // :375-376
             std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
             return 1;
         }

@@ -128,6 +128,29 @@ def _occluded_device(r, who, name, rays_t, tmax_t, out_t, stream):
 AOV_KINDS = {"normal": 0, "albedo": 1, "uv": 2, "dist": 3}
 
 
+# spt_render_aov_set kinds: bit k of the mask (SPT_AOVSET_* = 1 << k); the four above, the hit point and the hit count
+AOV_SET_KINDS = dict(AOV_KINDS, position=4, coverage=5)
+
+
+def _aov_set(kinds):
+    """(mask, the selected names in ascending bit order) of an iterable of AOV_SET_KINDS names."""
+    if isinstance(kinds, str):
+        kinds = (kinds,)
+    try:
+        names = list(kinds)
+    except TypeError:
+        raise ValueError(f"kinds must be an iterable of names out of {', '.join(AOV_SET_KINDS)}") from None
+    for k in names:
+        if not isinstance(k, str) or k not in AOV_SET_KINDS:
+            raise ValueError(f"unknown aov {k!r}: one of {', '.join(AOV_SET_KINDS)}")
+    if not names:
+        raise ValueError("kinds is empty")
+    if len(set(names)) != len(names):
+        raise ValueError("kinds names a buffer twice")
+    names.sort(key=AOV_SET_KINDS.get)
+    return sum(1 << AOV_SET_KINDS[k] for k in names), names
+
+
 def _aov_kind(aov):
     if not isinstance(aov, str) or aov not in AOV_KINDS:
         raise ValueError(f"unknown aov {aov!r}: one of {', '.join(AOV_KINDS)}")
@@ -513,6 +536,38 @@ class Renderer:
             FLAG_NORMALISE if normalise else 0, C.c_void_p(out_tensor.data_ptr()),
             C.c_void_p(stream) if stream else None))
 
+    def render_aov_set(self, w, h, samps_per_cell, kinds=("normal", "albedo", "dist"), seed=0, normalise=False, camera=None):
+        """Several first-hit feature buffers of the SAME samples from one launch (spt_render_aov_set): any of 'normal', 'albedo', 'uv',
+        'dist' (as ``render_aov``), 'position' (the hit point) and 'coverage' (1 per hit: un-normalised, the pixel's hit count).
+        Returns ({kind: (h, w, 3) float32}, stats)."""
+        mask, names = _aov_set(kinds)
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        outs = {k: np.empty((h, w, 3), dtype=np.float32) for k in names}
+        ptrs = (C.c_void_p * len(names))(*[outs[k].ctypes.data for k in names])
+        st = SptStats()
+        self._check(self._lib.spt_render_aov_set(self._h, C.byref(cam), w, h, samps_per_cell, seed, mask,
+                                                 FLAG_NORMALISE if normalise else 0, ptrs, C.byref(st)))
+        return outs, _stats_dict(st)
+
+    def render_aov_set_rows_device(self, out_tensors, w, h, row_begin, row_count, samps_per_cell, seed=0, normalise=False,
+                                   camera=None, stream=None):
+        """Enqueues rows [row_begin, row_begin+row_count) of ``render_aov_set`` into ``out_tensors`` = {kind: tensor} (each as
+        ``render_aov_rows_device`` takes it).  Asynchronous: call ``sync()`` for completion + statistics."""
+        if not isinstance(out_tensors, dict):
+            raise ValueError("out_tensors must be a dict {kind: tensor}")
+        mask, names = _aov_set(out_tensors.keys())
+        for k in names:
+            t = out_tensors[k]
+            if t.numel() != row_count * w * 3 or not t.is_contiguous():
+                raise ValueError(f"out_tensors[{k!r}] must be contiguous with row_count*w*3 float32 elements")
+            if str(t.dtype) != "torch.float32" or t.device.type != "cuda":
+                raise ValueError(f"out_tensors[{k!r}] must be a float32 tensor on the GPU")
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        ptrs = (C.c_void_p * len(names))(*[out_tensors[k].data_ptr() for k in names])
+        self._check(self._lib.spt_render_aov_set_rows_device(
+            self._h, C.byref(cam), w, h, row_begin, row_count, samps_per_cell, seed, mask,
+            FLAG_NORMALISE if normalise else 0, ptrs, C.c_void_p(stream) if stream else None))
+
     def set_watchdog(self, seconds):
         """Pool kernel: a launch whose waves run longer than this fails in sync() instead of hanging (0 = off)."""
         self._check(self._lib.spt_set_watchdog(self._h, float(seconds)))
@@ -717,6 +772,8 @@ class ProgressiveRenderer:
         self.frame = self._lanes[0]["frame"]
         self._issued = 0
         self._last_acc = None    # event after the most recent accumulation kernel
+        self._last_seed = None
+        self._aov_names = None   # aov_begin: the selected feature buffers (accumulated behind the C-ABI, spt_progressive_aov_*)
 
     def update_camera(self, camera):
         self.camera = camera
@@ -733,6 +790,7 @@ class ProgressiveRenderer:
             self.r.replay_state_on(r)
             lane["version"] = self.r._state_version
         seed = self.frames       # :922 renders with the running sampleCount, also on the clearing frame
+        self._last_seed = seed
         if self.pipeline > 1 and lane["done"] is not None:
             stream.wait_event(lane["done"])               # the lane's frame buffer was read by its last accumulation
         r.render_rows_device(lane["frame"], self.w, self.h, 0, self.h, self.samps, seed=seed, normalise=False,
@@ -757,8 +815,46 @@ class ProgressiveRenderer:
             lane["stream"].synchronize()
             lane["r"].sync()
 
+    def aov_begin(self, kinds=("normal",)):
+        """Feature buffers beside the radiance loop -- the reference's viewer as shipped accumulates the first hit's normal --: one
+        device-resident accumulation buffer per kind of ``kinds`` (names as ``Renderer.render_aov_set``), zeroed."""
+        mask, names = _aov_set(kinds)
+        r = self.r
+        if self._aov_names is None:
+            # spt_progressive_aov_begin takes the image size from spt_progressive_begin, whose own radiance accumBuffer and frame (2 x w*h*3
+            # floats on the device) stay unused here: this class accumulates radiance in its torch tensor.  Freed by close().
+            r._check(r._lib.spt_progressive_begin(r._h, self.w, self.h))
+        r._check(r._lib.spt_progressive_aov_begin(r._h, mask))
+        self._aov_names = names
+
+    def aov_frame(self, seed=None, clear=False):
+        """One fused launch of the selected buffers (un-normalised sums) for the current camera, added to (``clear``: replacing) their
+        accumulation buffers; blocking.  seed None = the seed of the radiance frame ``step()`` issued last, so that beauty and features
+        are those of the same samples.  Returns the stats."""
+        if self._aov_names is None:
+            raise SptError("aov_frame: call aov_begin first")
+        if seed is None:
+            seed = 0 if self._last_seed is None else self._last_seed
+        self.flush()
+        st = SptStats()
+        r = self.r
+        r._check(r._lib.spt_progressive_aov_frame(r._h, C.byref(self.camera), self.samps, seed, 1 if clear else 0, C.byref(st)))
+        return _stats_dict(st)
+
+    def aov_snapshot(self, kind):
+        """The accumulation buffer of one selected kind: (h, w, 3) float32."""
+        if self._aov_names is None or kind not in self._aov_names:
+            raise ValueError(f"aov_snapshot: {kind!r} is not one of the kinds given to aov_begin")
+        out = np.empty((self.h, self.w, 3), dtype=np.float32)
+        r = self.r
+        r._check(r._lib.spt_progressive_aov_snapshot(r._h, 1 << AOV_SET_KINDS[kind], out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def close(self):
         self.flush()
+        if self._aov_names is not None:
+            self.r._check(self.r._lib.spt_progressive_end(self.r._h))
+            self._aov_names = None
         for lane in self._lanes[1:]:
             lane["r"].close()
 
