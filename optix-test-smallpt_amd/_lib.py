@@ -116,6 +116,8 @@ INTERNAL_SYMBOLS = {
     "spt_selftest_range": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "spt_set_watchdog": (C.c_int, [_P, C.c_double]),
     "spt_last_kernel": (C.c_int, [_P]),
+    "spt_grid_placement": (C.c_int, [_P]),
+    "spt_selftest_grid_placement": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32 * 8), C.c_char_p, C.c_uint32]),
     "spt_last_query_path": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "spt_selftest_query_route": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P]),
     "spt_chunk_order_snapshot": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),

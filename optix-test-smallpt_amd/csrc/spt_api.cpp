@@ -334,6 +334,19 @@ static int table_share(const float4* geom, uint32_t n)
     return spt::share_select(c, ng);
 }
 
+// The un-guarded square root (sqrt_rsq) in the closest-hit loop is exact for det = 0 or 2^-96 <= det < inf.  That holds
+// whenever r*r >= 2^-60 and no coordinate can overflow b*b / dot(op,op); other scenes get the guarded build.
+static bool table_needs_guard(const spt_sphere* s, uint32_t n)
+{
+    bool needs_guard = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float big = std::fmax(std::fmax(std::fabs(s[i].center[0]), std::fabs(s[i].center[1])),
+                                    std::fmax(std::fabs(s[i].center[2]), std::fabs(s[i].radius)));
+        if (!(s[i].radius * s[i].radius >= 0x1p-60f) || !(big <= 1e15f)) needs_guard = true;
+    }
+    return needs_guard;
+}
+
 int spt_set_scene(spt_ctx* c, const spt_sphere* s, uint32_t n)
 {
     if (!c) return 1;
@@ -350,14 +363,7 @@ static int set_scene_impl(spt_ctx* c, const spt_sphere* s, uint32_t n)
     if (n && !s) return c->fail("spt_set_scene: spheres is NULL");
     for (uint32_t i = 0; i < n; ++i)
         if (s[i].refl < SPT_DIFF || s[i].refl > SPT_REFR) return c->fail("spt_set_scene: sphere %u has refl=%d", i, s[i].refl);
-    // The un-guarded square root (sqrt_rsq) in the closest-hit loop is exact for det = 0 or 2^-96 <= det < inf.  That holds
-    // whenever r*r >= 2^-60 and no coordinate can overflow b*b / dot(op,op); other scenes get the guarded build.
-    bool needs_guard = false;
-    for (uint32_t i = 0; i < n; ++i) {
-        const float big = std::fmax(std::fmax(std::fabs(s[i].center[0]), std::fabs(s[i].center[1])),
-                                    std::fmax(std::fabs(s[i].center[2]), std::fabs(s[i].radius)));
-        if (!(s[i].radius * s[i].radius >= 0x1p-60f) || !(big <= 1e15f)) needs_guard = true;
-    }
+    const bool needs_guard = table_needs_guard(s, n);
     // The exhaustive kernels stage the whole table in LDS (SPT_MAX_SPHERES); a larger table exists only behind a structure -- the
     // grid while its tables fit one CU's LDS, the hierarchy (records in global memory) beyond -- whose error bounds exclude the
     // degenerate scenes of the guarded build.
@@ -421,53 +427,75 @@ static int set_scene_impl(spt_ctx* c, const spt_sphere* s, uint32_t n)
 // LDS the grid kernel may spend on cell headers + references + the always-list, beside the 16-byte sphere records (one workgroup per CU)
 static size_t grid_table_budget(uint32_t n) { return (size_t)150 * 1024 - (size_t)(n ? n : 1u) * 16u; }
 
-// Uniform grid over the current sphere table (spt_grid.h); the caller holds the C-boundary try block.  Tables the pool kernel
-// takes, scenes that need the range-guarded square root and tables that do not fit the LDS keep the other kernels (grid_why says which).
-static int build_sphere_grid_tables(spt_ctx* c)
+// Which table placement of the grid kernels a sphere table gets (spt_grid.hip WHERE: 0 = sphere records, cell headers and references in
+// LDS, 1 = everything in global memory, 2 = the records in global memory and the grid tables in LDS), or -1 with the reason in `why`: tables the
+// pool kernel takes, scenes that need the range-guarded square root and tables beyond the grid keep the other kernels.  Host only -- no device
+// call; spt_set_scene and spt_selftest_grid_placement both decide through this function.  dsel = cells per sphere (0: the default 4),
+// force = spt_set_grid_pools' lane_owned - 1 (1: every table in global memory, 2: the sphere records only), pool_max = spt_pool_max_spheres().
+struct GridChoice {
+    int placement = -1;
+    spt::SphereGrid g;               // the grid of that placement (placement >= 0)
+    std::string why;
+};
+static void choose_grid_placement(const float4* geom, const float* radius, uint32_t n, uint32_t dsel, int force, bool needs_guard, uint32_t pool_max, GridChoice& out)
 {
-    c->grid_ready = false;
-    if (c->n <= (uint32_t)spt_pool_max_spheres()) { c->grid_why = "table small enough for the unrolled closest hit"; return 0; }
-    if (c->needs_guard) { c->grid_why = "scene needs the range-guarded square root"; return 0; }
+    out.placement = -1;
+    out.g = spt::SphereGrid();
+    if (n <= pool_max) { out.why = "table small enough for the unrolled closest hit"; return; }
+    if (needs_guard) { out.why = "scene needs the range-guarded square root"; return; }
     // Tables that fit one CU's LDS are staged there (both grid kernels).  Larger ones -- sphere records or grid beyond the LDS -- keep the
     // grid with their tables in global memory (spt_grid.hip GLOBAL_TABLES, round 4) up to kGridGlobalMax spheres: every lookup of the walk
     // is then a 64-lane gather through the texture path instead of an LDS read, which the walk's ~40 dependent lookups per ray pay for
     // (16 384 random spheres: 404 Msamples/s against 230 through the hierarchy; at 24 576 the two are level, at 32 768 the hierarchy's
     // log N wins 326 : 236, profiles/r04_big_tables.txt), so beyond that the hierarchy keeps the scene as in round 3.
     constexpr uint32_t kGridGlobalMax = 24576;
-    spt::SphereGrid g;
-    const uint32_t dsel = (c->variant >> 24) & 0xFFu;
-    const bool records_fit = (size_t)c->n * 16u + 8192u <= (size_t)150 * 1024;
-    c->grid_global = 0;
-    if (records_fit && c->grid_force_global == 0) spt::build_sphere_grid(c->h_geom.data(), c->h_radius.data(), c->n, dsel ? (double)dsel : 4.0, grid_table_budget(c->n), g);
+    spt::SphereGrid& g = out.g;
+    const bool records_fit = (size_t)n * 16u + 8192u <= (size_t)150 * 1024;
+    int where = 0;
+    if (records_fit && force == 0) spt::build_sphere_grid(geom, radius, n, dsel ? (double)dsel : 4.0, grid_table_budget(n), g);
     // (an LDS grid that had to shrink below a quarter of a cell per sphere to fit -- from about 6 500 random spheres on -- tests too many
     // spheres per cell: 8 000 spheres, 4 x 4 x 7 cells: 336 Msamples/s from LDS against 596 from global memory at the full resolution;
     // 6 000 spheres, 0.36 cells per sphere: 888 against 666; profiles/r04_big_tables.txt)
-    if (g.usable && c->n <= kGridGlobalMax) {
-        const double interior = (double)g.P.dim[0] * g.P.dim[1] * g.P.dim[2], in_grid_n = (double)c->n - (double)g.always.size();
+    if (g.usable && n <= kGridGlobalMax) {
+        const double interior = (double)g.P.dim[0] * g.P.dim[1] * g.P.dim[2], in_grid_n = (double)n - (double)g.always.size();
         if (interior < 0.25 * in_grid_n) g = spt::SphereGrid();
     }
     if (!g.usable) {
         const std::string lds_why = g.why;
-        if (c->n > 0xFFFFu) { c->grid_why = "more spheres than the grid's 16-bit references address"; return 0; }
+        if (n > 0xFFFFu) { out.why = "more spheres than the grid's 16-bit references address"; return; }
         // the sphere records in global memory and the grid in LDS (two of the walk's three lookups per sphere stay LDS reads), if a grid of
         // at least a quarter of a cell per sphere fits there; else everything in global memory at the full resolution, up to kGridGlobalMax
         g = spt::SphereGrid();
-        if (c->grid_force_global != 1) spt::build_sphere_grid(c->h_geom.data(), c->h_radius.data(), c->n, dsel ? (double)dsel : 4.0, (size_t)150 * 1024, g);
-        c->grid_global = 2;
+        if (force != 1) spt::build_sphere_grid(geom, radius, n, dsel ? (double)dsel : 4.0, (size_t)150 * 1024, g);
+        where = 2;
         const double interior = g.usable ? (double)g.P.dim[0] * g.P.dim[1] * g.P.dim[2] : 0.0;
-        if (!g.usable || interior < 0.25 * ((double)c->n - (double)g.always.size())) {
-            if (c->n > kGridGlobalMax) { c->grid_why = records_fit ? lds_why : "sphere records alone exceed the LDS, and the table is beyond the size up to which the global-memory grid beats the hierarchy"; return 0; }
+        if (!g.usable || interior < 0.25 * ((double)n - (double)g.always.size())) {
+            if (n > kGridGlobalMax) { out.why = records_fit ? lds_why : "sphere records alone exceed the LDS, and the table is beyond the size up to which the global-memory grid beats the hierarchy"; return; }
             g = spt::SphereGrid();
-            spt::build_sphere_grid(c->h_geom.data(), c->h_radius.data(), c->n, dsel ? (double)dsel : 4.0, (size_t)256 << 20, g);
-            c->grid_global = 1;
+            spt::build_sphere_grid(geom, radius, n, dsel ? (double)dsel : 4.0, (size_t)256 << 20, g);
+            where = 1;
         }
     }
-    if (!g.usable) { c->grid_why = g.why; return 0; }
+    if (!g.usable) { out.why = g.why; return; }
     // A cell that lists a third of the table means nearly everything shares a cell (the extent is set by a few large spheres that
     // are not large enough for the always-tested list): the walk would test the whole table per lane with LDS gathers, slower than
     // the exhaustive kernel's broadcast loop (measured 2.5x on such a table), which then keeps the scene.
-    const size_t in_grid = (size_t)c->n - g.always.size();
-    if (in_grid > 96 && (size_t)g.max_cell * 3 > in_grid) { c->grid_why = "a single cell lists more than a third of the spheres"; return 0; }
+    const size_t in_grid = (size_t)n - g.always.size();
+    if (in_grid > 96 && (size_t)g.max_cell * 3 > in_grid) { out.why = "a single cell lists more than a third of the spheres"; return; }
+    out.why.clear();
+    out.placement = where;
+}
+
+// Uniform grid over the current sphere table (spt_grid.h); the caller holds the C-boundary try block.  A table that
+// choose_grid_placement refuses keeps the other kernels (grid_why says why).
+static int build_sphere_grid_tables(spt_ctx* c)
+{
+    c->grid_ready = false;
+    GridChoice choice;
+    choose_grid_placement(c->h_geom.data(), c->h_radius.data(), c->n, (c->variant >> 24) & 0xFFu, c->grid_force_global, c->needs_guard, (uint32_t)spt_pool_max_spheres(), choice);
+    if (choice.placement < 0) { c->grid_why = choice.why; return 0; }
+    c->grid_global = choice.placement;
+    const spt::SphereGrid& g = choice.g;
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
     auto upload = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
@@ -573,6 +601,32 @@ int spt_selftest_sphere_grid(const spt_sphere* s, uint32_t n, uint32_t cells_per
         }
         if (why && why_len) std::snprintf(why, why_len, "%s", reason.c_str());
         return ok ? 0 : 2;
+    } catch (const std::exception& e) {
+        if (why && why_len) std::snprintf(why, why_len, "%s", e.what());
+        return 1;
+    }
+}
+
+// Host-only: the table placement spt_set_scene would give this table (choose_grid_placement, the function it runs; no device call).
+// out8 = {dim x, dim y, dim z, references, always-tested spheres, table bytes, most references in one cell, 0} of the chosen grid.
+int spt_selftest_grid_placement(const spt_sphere* s, uint32_t n, uint32_t cells_per_sphere, int force, int* placement, uint32_t* out8, char* why, uint32_t why_len)
+{
+    if ((!s && n) || !placement || force < 0 || force > 2 || cells_per_sphere > 0xFFu) return 1;
+    try {
+        std::vector<float4> geom(n);
+        std::vector<float> radius(n);
+        for (uint32_t i = 0; i < n; ++i) { geom[i] = make_float4(s[i].center[0], s[i].center[1], s[i].center[2], s[i].radius * s[i].radius); radius[i] = s[i].radius; }
+        GridChoice choice;
+        choose_grid_placement(geom.data(), radius.data(), n, cells_per_sphere, force, table_needs_guard(s, n), (uint32_t)spt_pool_max_spheres(), choice);
+        *placement = choice.placement;
+        if (out8) {
+            const spt::SphereGrid& g = choice.g;
+            const bool on = choice.placement >= 0;
+            out8[0] = on ? (uint32_t)g.P.dim[0] : 0u; out8[1] = on ? (uint32_t)g.P.dim[1] : 0u; out8[2] = on ? (uint32_t)g.P.dim[2] : 0u; out8[3] = on ? g.P.nrefs : 0u;
+            out8[4] = on ? (uint32_t)g.always.size() : 0u; out8[5] = on ? (uint32_t)g.lds_bytes() : 0u; out8[6] = on ? g.max_cell : 0u; out8[7] = 0u;
+        }
+        if (why && why_len) std::snprintf(why, why_len, "%s", choice.why.c_str());
+        return 0;
     } catch (const std::exception& e) {
         if (why && why_len) std::snprintf(why, why_len, "%s", e.what());
         return 1;
@@ -2339,6 +2393,8 @@ int spt_set_watchdog(spt_ctx* c, double seconds)
 }
 
 int spt_last_kernel(spt_ctx* c) { return c ? c->last_kernel : -1; }
+
+int spt_grid_placement(spt_ctx* c) { return c && !c->mesh_scene && c->grid_ready ? c->grid_global : -1; }
 
 // Host-only (spt_internal.h): the multiplier and shift the pool kernel divides a jitter cell's id by the image width with.
 int spt_selftest_row_divisor(uint32_t w, uint32_t* mul, uint32_t* shift)

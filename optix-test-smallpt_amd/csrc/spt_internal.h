@@ -49,6 +49,11 @@ int  spt_set_watchdog(spt_ctx* ctx, double seconds);
  * After a pool launch spt_diag returns out24[0..2] = batches per class (GEN, DIFF, REFR), [3..5] = lanes per class, [23] = the sharing
  * pattern its closest hit ran (csrc/spt_share.h: 0 = generic, 1 = box prefix, 2 = Cornell-9). */
 int  spt_last_kernel(spt_ctx* ctx);
+/* Where the grid kernels of the current sphere scene read their tables (spt_grid.hip WHERE): 0 = sphere records, cell headers and references
+ * staged in LDS, 1 = everything from global memory, 2 = the records from global memory and the grid tables staged in LDS; -1 = the current
+ * scene has no grid (a mesh scene, or a table the grid refuses).  Chosen by spt_set_scene; spt_set_grid_pools' lane_owned = 2 / 3 forces
+ * 1 / asks for 2 at the next spt_set_scene (A/B and tests; 3 ends at 1 where the LDS grid would be too coarse). */
+int  spt_grid_placement(spt_ctx* ctx);
 
 /* Numerics self-test of the kernel's exact-math helpers (host arrays in/out, n elements):
  * op 0 sqrt_fix, 2 sqrt_exact, 3 rcp_exact, 10 sqrt_rsq, 4 (float)((double)x / w) by the FMA sequence,
@@ -81,6 +86,12 @@ int  spt_selftest_sphere_bvh(const spt_sphere* spheres, uint32_t n, uint32_t* ou
  * meets, that references are ascending and in range and that the ray test admits every origin inside the box.
  * out8 = {dim x, dim y, dim z, references, always-tested spheres, table bytes, usable, most references in one cell}; 0 = valid, 2 = not usable / invalid, 1 = builder error. */
 int  spt_selftest_sphere_grid(const spt_sphere* spheres, uint32_t n, uint32_t cells_per_sphere, uint32_t* out8, char* why, uint32_t why_len);
+/* Host-only: the placement (spt_grid_placement) spt_set_scene would choose for this table -- the same function, no device call -- at
+ * `cells_per_sphere` (tuning bits 31:24; 0 = the default) under force = 0 (none), 1 (everything in global memory) or 2 (the sphere records
+ * only): spt_set_grid_pools' lane_owned - 1.  *placement = 0 / 1 / 2, or -1 with the reason the grid refuses the table in `why`;
+ * out8 (may be NULL) = {dim x, dim y, dim z, references, always-tested spheres, table bytes, most references in one cell, 0} of the chosen
+ * grid (zeros when refused).  Returns 0, 1 = bad arguments / builder error (message in `why`). */
+int  spt_selftest_grid_placement(const spt_sphere* spheres, uint32_t n, uint32_t cells_per_sphere, int force, int* placement, uint32_t* out8, char* why, uint32_t why_len);
 
 /* Host-only: the sharing pattern of the pool kernel's closest hit that spt_set_scene would choose for this table (csrc/spt_share.h;
  * 0 = generic, 1 = box prefix, 2 = Cornell-9), the same function on the same padded table.  The pattern runs where the default pool size

@@ -581,6 +581,11 @@ class Renderer:
         over an instanced scene, spt_set_instances) for the last launch."""
         return {0: "mega", 1: "pool", 2: "mesh", 3: "sbvh", 4: "grid", 5: "gpool", 6: "mesh_bvh", 7: "mesh_bvh_fast", 8: "mesh_inst"}[self._lib.spt_last_kernel(self._h)]
 
+    def grid_placement(self):
+        """Where the grid kernels of the current sphere scene read their tables (spt_grid_placement): 0 = everything staged in LDS,
+        1 = everything from global memory, 2 = the sphere records from global memory and the grid tables in LDS; -1 = no grid."""
+        return int(self._lib.spt_grid_placement(self._h))
+
     def render_interleaved_device(self, out_tensor, w, h, block_rows, world, rank, samps_per_cell, seed=0,
                                   normalise=False, camera=None, stream=None):
         """Like render_rows_device for the rows of rank `rank` when the image is dealt out to `world` ranks round-robin in

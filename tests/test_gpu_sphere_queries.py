@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from test_sphere_accel import NATURAL_PLACEMENT
+
 pytestmark = pytest.mark.gpu
 
 ACCEL_NAMES = {0: "exhaustive", 1: "bvh", 2: "grid"}
@@ -161,6 +163,8 @@ def test_large_tables_grid_bvh_exhaustive_agree_with_oracle(pkg, nspheres):
         with pkg.Renderer(0) as r:
             r.set_sphere_accel(accel)
             r.set_scene(spheres)
+            if accel == 2:                                  # all in LDS / records in global memory (tests/test_sphere_accel.py pins the choice on the CPU)
+                assert r.grid_placement() == (0 if nspheres == 1024 else NATURAL_PLACEMENT["random 16384"])
             out[accel] = r.trace_spheres(rays)
             paths[accel] = r.last_query_path()[0]
             r.trace_spheres(inbox)

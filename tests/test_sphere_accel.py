@@ -25,6 +25,25 @@ def _selftest_grid(pkg, spheres, density=0):
     return rc, list(out), why.value.decode()
 
 
+def grid_placement_of(pkg, spheres, force=0, density=0):
+    """spt_selftest_grid_placement: (placement or -1, out8, refusal reason) of the decision function spt_set_scene runs; force as
+    spt_set_grid_pools' lane_owned - 1."""
+    lib = pkg.load_library()
+    placement, out, why = C.c_int(-9), (C.c_uint32 * 8)(), C.create_string_buffer(256)
+    rc = lib.spt_selftest_grid_placement(spheres.ctypes.data_as(C.c_void_p), len(spheres), density, force, C.byref(placement), C.byref(out), why, 256)
+    assert rc == 0, (rc, why.value)
+    return placement.value, list(out), why.value.decode()
+
+
+def identical_50(pkg):
+    """Fifty copies of one emitting sphere: every cell of the grid lists all of them."""
+    return pkg.make_spheres([(1.0, (50, 40, 80), (1, 1, 1), (.5, .5, .5), 0)] * 50)
+
+
+# Natural (unforced) placements the GPU tests rely on; test_grid_placement_selection pins them without a GPU.
+NATURAL_PLACEMENT = {"random 4096": 0, "random 12000": 2, "random 16384": 2}
+
+
 def _cluster_scene(pkg, n, seed, huge=True):
     """n spheres: small ones of very different sizes, overlapping, some concentric / coincident, all three materials, a few
     emitters; optionally closed in by the Cornell walls and light (radii 1e5 / 600: the always-tested list)."""
@@ -81,6 +100,72 @@ def test_sphere_grid_structure(pkg):
     assert rc == 1 and "non-finite" in why
 
 
+def test_grid_placement_selection(pkg):
+    """Which table placement (spt_grid.hip WHERE: 0 = all in LDS, 1 = all in global memory, 2 = records in global memory and the grid in
+    LDS) spt_set_scene gives a table, through spt_selftest_grid_placement -- the function spt_set_scene itself runs, without a device.
+
+    How the literals were obtained: the decision code was moved out of build_sphere_grid_tables unchanged, the hook was run on every
+    table below and the observed placements were written down; each was then checked by hand against the rule of
+    choose_grid_placement (csrc/spt_api.cpp) that applies to it, named in the comment beside it.  12000 / 16384 / 30000 agree with
+    what the GPU tests expect of last_kernel ("grid", "grid", "sbvh").  Findings: placement 1 IS reachable without the switch -- from
+    about 17 000 random spheres up to 24 576 the 150 KB grid has less than a quarter of a cell per sphere -- and a forced "records only"
+    request (force 2) on the identical-50 table stays at placement 2: its 6 x 6 x 6 cells are more than a quarter of a cell per sphere,
+    although every cell lists all fifty."""
+    R = pkg.random_spheres
+    tiny = np.concatenate([R(100), pkg.make_spheres([(2.0 ** -31, (50, 40, 80), (0, 0, 0), (.5, .5, .5), 0)])])
+    unforced = [
+        ("cluster 24", _cluster_scene(pkg, 24, 5), -1, "small enough"),          # n <= the pool kernel's 24
+        ("cluster 25", _cluster_scene(pkg, 25, 5), 0, None),                      # the first table above it: everything fits the LDS
+        ("random 1024", R(1024), 0, None),
+        ("random 4096", R(4096, 7), 0, None),
+        ("cluster 4096", _cluster_scene(pkg, 4096, 9), -1, "a single cell lists more than a third"),
+        ("radius 2^-31", tiny, -1, "range-guarded square root"),
+        ("random 6000", R(6000), 0, None),           # 12 x 10 x 18 = 2160 cells >= 5993 / 4: the LDS grid is kept
+        ("random 8000", R(8000), 2, None),           # records fit, but the grid beside them drops below 1/4 cell per sphere; alone it has 21 x 17 x 32
+        ("random 9088", R(9088), 2, None),           # 9088 * 16 + 8192 = 150 KB exactly: records_fit, 8 KB of grid is too coarse
+        ("random 9089", R(9089), 2, None),           # records_fit fails: straight to the 150 KB grid
+        ("random 12000", R(12000), 2, None),
+        ("random 12000 seed 11", R(12000, 11), 2, None),
+        ("random 16384", R(16384), 2, None),         # 15 x 12 x 23 = 4140 cells >= 16377 / 4 = 4094.25: just
+        ("random 16384 without walls", R(16384)[7:].copy(), 2, None),
+        ("random 17000", R(17000), 1, None),         # the same 4140 cells < 16993 / 4: everything in global memory at the full resolution
+        ("random 24576", R(24576), 1, None),         # kGridGlobalMax itself
+        ("random 24577", R(24577), -1, "beyond the size up to which the global-memory grid beats the hierarchy"),
+        ("random 30000", R(30000), -1, "sphere records alone exceed the LDS"),
+        ("random 70000", R(70000), -1, "16-bit references"),
+    ]
+    for name, sc, want, reason in unforced:
+        got, out, why = grid_placement_of(pkg, sc)
+        assert got == want, (name, got, why)
+        if want < 0:
+            assert reason in why and out == [0] * 8, (name, why, out)
+        else:
+            assert why == "" and min(out[:3]) >= 1, (name, why, out)
+        if name in NATURAL_PLACEMENT:
+            assert NATURAL_PLACEMENT[name] == want, name
+    # the rules behind the literals above, on the numbers the hook reports
+    _, (dx, dy, dz, *_), _ = grid_placement_of(pkg, R(16384))
+    assert dx * dy * dz >= 0.25 * (16384 - 7)
+    _, (dx, dy, dz, _, always, nbytes, _, _), _ = grid_placement_of(pkg, R(6000))
+    assert dx * dy * dz >= 0.25 * (6000 - always) and nbytes + 6000 * 16 <= 150 * 1024
+    assert 9088 * 16 + 8192 == 150 * 1024
+    # the switch (spt_set_grid_pools lane_owned = 2 / 3 -> force 1 / 2) on the tables of tests/test_gpu_grid_placements.py: every
+    # placement is reachable on every one of them, with the dims of the unforced grid (so the walks are the same walks)
+    forced = [("cluster 100", _cluster_scene(pkg, 100, 6), 7), ("open 257", _cluster_scene(pkg, 257, 8, huge=False), 0),
+              ("config 5", R(1024, 1024), 7), ("identical 50", identical_50(pkg), 0)]
+    for name, sc, always in forced:
+        p0, out0, _ = grid_placement_of(pkg, sc)
+        assert p0 == 0 and out0[4] == always, (name, p0, out0)
+        for force, want in ((1, 1), (2, 2)):
+            got, out, why = grid_placement_of(pkg, sc, force)
+            assert got == want and out == out0 and why == "", (name, force, got, out, why)
+    assert grid_placement_of(pkg, identical_50(pkg))[1][6] == 50          # every cell lists all fifty
+    # bad arguments
+    lib = pkg.load_library()
+    assert lib.spt_selftest_grid_placement(None, 0, 0, 3, C.byref(C.c_int()), None, None, 0) == 1
+    assert lib.spt_selftest_grid_placement(None, 0, 0, 0, None, None, None, 0) == 1
+
+
 def test_sphere_grid_walk_equals_exhaustive_on_cpu(tmp_path):
     """The traversal arithmetic the kernel uses (csrc/spt_grid.h) + the builder against the exhaustive loop, on the CPU: random,
     grazing, axis-parallel, on-cell-face, almost-zero-component, drifted-length and far-origin rays over six kinds of tables;
@@ -102,7 +187,7 @@ def test_sphere_grid_images_equal_oracle(pkg, renderer, oracle, lane_owned):
     or lanes that own their path (spt_grid.hip) --; image and bounce count equal the oracle's exhaustive loop."""
     scenes = [("cluster 25", _cluster_scene(pkg, 25, 5)), ("cluster 100", _cluster_scene(pkg, 100, 6)), ("cluster 600", _cluster_scene(pkg, 600, 7)),
               ("open 257", _cluster_scene(pkg, 257, 8, huge=False)), ("config 5", pkg.random_spheres(1024, 1024)), ("random 4096", pkg.random_spheres(4096, 7)),
-              ("identical 50", pkg.make_spheres([(1.0, (50, 40, 80), (1, 1, 1), (.5, .5, .5), 0)] * 50)),
+              ("identical 50", identical_50(pkg)),
               # some of these 4096 are concentric with the wall spheres (centres 1e5 away): the extent is 1e5 long, nearly everything
               # shares a cell, the grid declines (spt_api.cpp build_sphere_grid_tables) and from 1024 spheres on the hierarchy takes over
               ("cluster 4096", _cluster_scene(pkg, 4096, 9)),
@@ -119,6 +204,8 @@ def test_sphere_grid_images_equal_oracle(pkg, renderer, oracle, lane_owned):
             renderer.set_scene(sc)
             img, st = renderer.render(w, h, samps, seed=seed)
             assert renderer.last_kernel() == expect.get(name, name_of), name
+            if name in NATURAL_PLACEMENT:
+                assert renderer.grid_placement() == NATURAL_PLACEMENT[name], name
             ref, rst = oracle.render(sc, w, h, samps, seed=seed)
             assert np.array_equal(img, ref), (name, int((img != ref).any(axis=-1).sum()))
             assert st["bounces"] == rst["bounces"] and st["max_depth_kills"] == rst["max_depth_kills"], name
