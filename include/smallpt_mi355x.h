@@ -167,7 +167,9 @@ int  spt_set_meshes(spt_ctx* ctx, const spt_mesh* meshes, uint32_t nmesh, const 
  *     their normal is noise for every ray) that finds the needles whose supporting line the ray's line crosses, wherever along
  *     it.  Rounds 2 and 3 documented those rays as exceptions (18 of 668 000 test rays); tests/test_meshes.py now requires 0
  *     differences on 700 000 random and adversarial rays, the CPU harness tests/sanitize/tribvh_main.cpp runs the same walk
- *     functions against the exhaustive loop.  A render launch lists the triangles in whose plane the camera's origin lies once
+ *     functions against the exhaustive loop; tests/test_gpu_line_tree.py forces the tree form of the lines at a few hundred thin
+ *     triangles (and reaches it unforced with 16 500 slivers) and requires the exhaustive loop's bytes from every mesh kernel --
+ *     closest hit, occlusion, interval, instanced, render and feature-buffer launches.  A render launch lists the triangles in whose plane the camera's origin lies once
  *     (the lines of all its rays of depth 0 pass through that point) and those rays test the list instead of walking the plane
  *     tree.  Cost, shipped scene (8192 triangles), 1280 x 720 x 4 spp: 1.4 ms per pinhole frame, 1.5 ms with the smallpt camera,
  *     against 25-29 ms through the exhaustive loop; spt_trace_rays_device 0.41 Grays/s against 0.125.  A ray that starts hundreds of scene sizes away degrades

@@ -117,6 +117,9 @@ INTERNAL_SYMBOLS = {
     "spt_set_watchdog": (C.c_int, [_P, C.c_double]),
     "spt_last_kernel": (C.c_int, [_P]),
     "spt_grid_placement": (C.c_int, [_P]),
+    "spt_set_line_form": (C.c_int, [_P, C.c_int]),
+    "spt_mesh_line_form": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "spt_selftest_bvh_lines": (C.c_int, [C.POINTER(SptMesh), C.c_uint32, C.c_int, C.POINTER(C.c_uint32 * 4), C.c_char_p, C.c_uint32]),
     "spt_selftest_grid_placement": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32 * 8), C.c_char_p, C.c_uint32]),
     "spt_last_query_path": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "spt_selftest_query_route": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P]),

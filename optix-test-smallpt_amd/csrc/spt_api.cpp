@@ -56,6 +56,8 @@ struct InstScene {
     uint64_t tri_sum = 0;            // sum over instances of the model's triangles (SPT_ACCEL_AUTO)
     bool specular = false;
     bool accel_built = false;        // every model's hierarchy is in its descriptor
+    std::vector<uint32_t> thin;      // per model, once built: its thin triangles (spt_mesh_line_form)
+    std::vector<uint8_t> line_tree;  // ... and whether they are a cone tree (1) or a table (0)
 };
 
 struct spt_ctx {
@@ -109,6 +111,8 @@ struct spt_ctx {
     uint32_t* d_cam_planes = nullptr; uint32_t ncam = 0, cam_cap = 0; float cam_key[4] = {0, 0, 0, 0}; bool cam_valid = false;   // spt_bvh.h camera_planes of the last pinhole origin
     float4* d_bvh_cones = nullptr; float4* d_plane_nodes = nullptr; float4* d_line_nodes = nullptr; bool have_planes = false, have_lines = false;   // spt_tribvh.h
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0;
+    uint32_t bvh_thin = 0;           // thin triangles of the structures above (spt_mesh_line_form)
+    int line_form = 0;               // spt_set_line_form: build_bvh's `form` for the structures built from now on (0 = by count)
     uint32_t ntris = 0, ninst = 0;
     bool inst_scene = false;         // the current mesh scene is instanced (spt_set_instances): ntris = min(tri_sum, 2^32 - 1), ninst = instances
     InstScene inst;
@@ -831,7 +835,7 @@ static int set_meshes_impl(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, c
 static int build_accel(spt_ctx* c)
 {
     spt::Bvh bvh;
-    spt::build_bvh(c->h_tris.data(), c->ntris, bvh);
+    spt::build_bvh(c->h_tris.data(), c->ntris, bvh, c->line_form);
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
     auto upload = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
@@ -848,6 +852,7 @@ static int build_accel(spt_ctx* c)
     if (c->have_planes) SPT_HIP(c, upload(c->d_plane_nodes, bvh.planes.data(), bvh.planes.size() * sizeof(float4)));
     if (c->have_lines) SPT_HIP(c, upload(c->d_line_nodes, bvh.lines.data(), bvh.lines.size() * sizeof(float4)));
     c->bvh_flat = bvh.flat && bvh.thin_count; c->nline_slots = (uint32_t)bvh.flat_lines.size(); c->cam_valid = false;
+    c->bvh_thin = bvh.thin_count;
     if (c->bvh_flat) {
         SPT_HIP(c, upload(c->d_flat_lines, bvh.flat_lines.data(), bvh.flat_lines.size() * sizeof(float4)));
         SPT_HIP(c, upload(c->d_flat_line_index, bvh.flat_line_index.data(), bvh.flat_line_index.size() * sizeof(uint32_t)));
@@ -885,11 +890,13 @@ static int build_inst_accel(spt_ctx* c, InstScene& s, const char* who)
 {
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+    s.thin.resize(s.models.size(), 0u);
+    s.line_tree.resize(s.models.size(), 0);
     for (size_t m = 0; m < s.models.size(); ++m) {
         if (s.models[m].bvh_nodes) continue;
         spt::MParams M = s.models[m];                                  // (stored only once complete)
         spt::Bvh bvh;
-        spt::build_bvh(s.tris[m].data(), M.ntris, bvh);
+        spt::build_bvh(s.tris[m].data(), M.ntris, bvh, c->line_form);
         hipError_t e = inst_upload(s, M.bvh_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float4));
         if (e == hipSuccess) e = inst_upload(s, M.bvh_tris, bvh.tris.data(), bvh.tris.size() * sizeof(float4));
         if (e == hipSuccess) e = inst_upload(s, M.bvh_index, bvh.index.data(), bvh.index.size() * sizeof(uint32_t));
@@ -903,6 +910,7 @@ static int build_inst_accel(spt_ctx* c, InstScene& s, const char* who)
         }
         if (e != hipSuccess) return c->fail("%s: %s", who, hipGetErrorString(e));
         s.models[m] = M;
+        s.thin[m] = bvh.thin_count; s.line_tree[m] = bvh.thin_count && !bvh.flat ? 1 : 0;
     }
     SPT_HIP(c, hipMemcpy(s.d_models, s.models.data(), s.models.size() * sizeof(spt::MParams), hipMemcpyHostToDevice));
     s.accel_built = true;
@@ -1042,9 +1050,9 @@ int spt_set_mesh_accel(spt_ctx* c, int accel)
     }
 }
 
-// Host-only self-test of the builder (no device call): builds the hierarchy over the meshes' triangles and validates it.
-// out4 = {nodes, leaves, depth, triangles}.
-int spt_selftest_bvh(const spt_mesh* meshes, uint32_t nmesh, uint32_t* out4, char* why, uint32_t why_len)
+// Host-only self-tests of the builder (no device call): build the structures over the meshes' triangles with the thin triangles kept as
+// `form` says (build_bvh) and validate them.  0 = valid, 2 = invalid, 1 = error; the reason goes to `why`.
+static int selftest_bvh_build(const spt_mesh* meshes, uint32_t nmesh, int form, spt::Bvh& bvh, char* why, uint32_t why_len)
 {
     try {
         std::vector<float4> recs;
@@ -1062,17 +1070,37 @@ int spt_selftest_bvh(const spt_mesh* meshes, uint32_t nmesh, uint32_t* out4, cha
             }
         }
         const uint32_t ntris = (uint32_t)(recs.size() / 3);
-        spt::Bvh bvh;
-        spt::build_bvh(recs.data(), ntris, bvh);
+        spt::build_bvh(recs.data(), ntris, bvh, form);
         std::string reason;
         const bool ok = spt::validate_bvh(recs.data(), ntris, bvh, reason);
-        if (out4) { out4[0] = (uint32_t)(bvh.nodes.size() / 4); out4[1] = bvh.leaves; out4[2] = bvh.depth; out4[3] = bvh.regular_count; }
         if (why && why_len) std::snprintf(why, why_len, "%s", reason.c_str());
         return ok ? 0 : 2;
     } catch (const std::exception& e) {
         if (why && why_len) std::snprintf(why, why_len, "%s", e.what());
         return 1;
     }
+}
+
+// out4 = {nodes, leaves, depth, triangles}.
+int spt_selftest_bvh(const spt_mesh* meshes, uint32_t nmesh, uint32_t* out4, char* why, uint32_t why_len)
+{
+    spt::Bvh bvh;
+    const int rc = selftest_bvh_build(meshes, nmesh, 0, bvh, why, why_len);
+    if (rc != 1 && out4) { out4[0] = (uint32_t)(bvh.nodes.size() / 4); out4[1] = bvh.leaves; out4[2] = bvh.depth; out4[3] = bvh.regular_count; }
+    return rc;
+}
+
+// out4 = {thin triangles, table (1) or tree (0), float4 of the line tree, slots of the line table}.
+int spt_selftest_bvh_lines(const spt_mesh* meshes, uint32_t nmesh, int form, uint32_t* out4, char* why, uint32_t why_len)
+{
+    if (form < 0 || form > 2 || (!meshes && nmesh)) {
+        if (why && why_len) std::snprintf(why, why_len, "spt_selftest_bvh_lines: form = %d, must be 0 (by count), 1 (table) or 2 (tree)%s", form, !meshes && nmesh ? "; NULL meshes" : "");
+        return 1;
+    }
+    spt::Bvh bvh;
+    const int rc = selftest_bvh_build(meshes, nmesh, form, bvh, why, why_len);
+    if (rc != 1 && out4) { out4[0] = bvh.thin_count; out4[1] = bvh.flat ? 1u : 0u; out4[2] = (uint32_t)bvh.lines.size(); out4[3] = (uint32_t)bvh.flat_lines.size(); }
+    return rc;
 }
 
 // Which closest-hit mode a launch (render = true) or a ray query of the current mesh scene takes.  SPT_ACCEL_AUTO picks between the two EXACT
@@ -2395,6 +2423,29 @@ int spt_set_watchdog(spt_ctx* c, double seconds)
 int spt_last_kernel(spt_ctx* c) { return c ? c->last_kernel : -1; }
 
 int spt_grid_placement(spt_ctx* c) { return c && !c->mesh_scene && c->grid_ready ? c->grid_global : -1; }
+
+int spt_set_line_form(spt_ctx* c, int form)
+{
+    if (!c) return 1;
+    if (form < 0 || form > 2) return c->fail("spt_set_line_form: form = %d, must be 0 (by count), 1 (table) or 2 (tree)", form);
+    c->line_form = form;                                          // read by the next build_accel / build_inst_accel
+    return 0;
+}
+
+int spt_mesh_line_form(spt_ctx* c, uint32_t* thin_count)
+{
+    uint64_t thin = 0;
+    bool tree = false;
+    if (c && c->mesh_scene && c->bvh_ready) {
+        if (c->inst_scene) {
+            for (size_t m = 0; m < c->inst.thin.size(); ++m) { thin += c->inst.thin[m]; tree = tree || c->inst.line_tree[m]; }
+        } else {
+            thin = c->bvh_thin; tree = thin && !c->bvh_flat;
+        }
+    }
+    if (thin_count) *thin_count = thin > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)thin;
+    return thin == 0 ? 0 : (tree ? 2 : 1);
+}
 
 // Host-only (spt_internal.h): the multiplier and shift the pool kernel divides a jitter cell's id by the image width with.
 int spt_selftest_row_divisor(uint32_t w, uint32_t* mul, uint32_t* shift)

@@ -54,6 +54,16 @@ int  spt_last_kernel(spt_ctx* ctx);
  * scene has no grid (a mesh scene, or a table the grid refuses).  Chosen by spt_set_scene; spt_set_grid_pools' lane_owned = 2 / 3 forces
  * 1 / asks for 2 at the next spt_set_scene (A/B and tests; 3 ends at 1 where the LDS grid would be too coarse). */
 int  spt_grid_placement(spt_ctx* ctx);
+/* How the structures of a mesh scene (SPT_ACCEL_BVH / BVH_FAST / AUTO) keep the thin triangles' lines (csrc/spt_tribvh.h (3)): form 0 = by
+ * their number (the default: a table that every ray scans up to kTriFlatLines = 16 384 thin triangles, a cone tree that every ray walks
+ * beyond), 1 = always the table, 2 = always the tree.  Applies to the structures built AFTER the call (spt_set_meshes, spt_set_instances,
+ * or spt_set_mesh_accel where it builds), per model of an instanced scene; any other value fails with a message.  Tests force the tree at
+ * small sizes with it.  Results never depend on it: either form lists every thin triangle a ray's line can be reported by. */
+int  spt_set_line_form(spt_ctx* ctx, int form);
+/* What the built structures of the current mesh scene hold: 0 = no thin triangle (or nothing built: a sphere scene, SPT_ACCEL_EXHAUSTIVE
+ * before any other mode), 1 = the line table, 2 = the line tree; *thin_count (may be NULL) = the thin triangles in it.  An instanced scene
+ * reports the sum over its models, and 2 if any model holds a tree. */
+int  spt_mesh_line_form(spt_ctx* ctx, uint32_t* thin_count);
 
 /* Numerics self-test of the kernel's exact-math helpers (host arrays in/out, n elements):
  * op 0 sqrt_fix, 2 sqrt_exact, 3 rcp_exact, 10 sqrt_rsq, 4 (float)((double)x / w) by the FMA sequence,
@@ -79,6 +89,9 @@ int  spt_selftest_range(spt_ctx* ctx, int op, uint32_t first, uint32_t count, ui
  * triangles with an edge of length zero are the rest)};
  * returns 0 = valid, 2 = invalid (reason in `why`), 1 = builder error. */
 int  spt_selftest_bvh(const spt_mesh* meshes, uint32_t nmesh, uint32_t* out4, char* why, uint32_t why_len);
+/* The same build and validation with the thin triangles kept as `form` says (spt_set_line_form: 0 / 1 / 2; anything else returns 1);
+ * out4 = {thin triangles, 1 = table / 0 = tree, float4 of the line tree, slots of the line table (group headers included)}. */
+int  spt_selftest_bvh_lines(const spt_mesh* meshes, uint32_t nmesh, int form, uint32_t* out4, char* why, uint32_t why_len);
 /* The same for the sphere hierarchy of spt_set_sphere_accel; out4 = {nodes, leaves, depth, always-tested spheres}. */
 int  spt_selftest_sphere_bvh(const spt_sphere* spheres, uint32_t n, uint32_t* out4, char* why, uint32_t why_len);
 /* Host-only self-test of the SPT_ACCEL_GRID builder (csrc/spt_grid.cpp): builds the uniform grid over the table at

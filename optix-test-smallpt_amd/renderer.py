@@ -286,6 +286,8 @@ class Renderer:
             other.set_mesh_accel(st["mesh_accel"])
         if st.get("environment") is not None:
             other.set_environment(st["environment"])
+        if st.get("line_form") is not None:
+            other.set_line_form(st["line_form"])
         if st["scene"] is not None:
             if st["scene"][0] == "spheres":
                 other.set_scene(st["scene"][1])
@@ -585,6 +587,18 @@ class Renderer:
         """Where the grid kernels of the current sphere scene read their tables (spt_grid_placement): 0 = everything staged in LDS,
         1 = everything from global memory, 2 = the sphere records from global memory and the grid tables in LDS; -1 = no grid."""
         return int(self._lib.spt_grid_placement(self._h))
+
+    def set_line_form(self, form=0):
+        """How the structures of mesh scenes built from now on keep their thin triangles (csrc/spt_internal.h spt_set_line_form): 0 = by
+        their number (the default), 1 = the table, 2 = the cone tree.  Results never depend on it."""
+        self._check(self._lib.spt_set_line_form(self._h, int(form)))
+        self._state["line_form"] = int(form)
+        self._state_version += 1
+
+    def mesh_line_form(self):
+        """(form, thin triangles) of the current mesh scene's built structures (spt_mesh_line_form): form 0 = none, 1 = table, 2 = tree."""
+        n = C.c_uint32(0)
+        return int(self._lib.spt_mesh_line_form(self._h, C.byref(n))), int(n.value)
 
     def render_interleaved_device(self, out_tensor, w, h, block_rows, world, rank, samps_per_cell, seed=0,
                                   normalise=False, camera=None, stream=None):
