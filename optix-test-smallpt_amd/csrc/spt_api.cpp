@@ -40,6 +40,9 @@ inline uint32_t mix32(uint32_t x)
     return x;
 }
 
+inline bool is_mesh_kernel(int k) { return k == kMesh || k == kMeshBvh || k == kMeshBvhFast || k == kMeshInst; }   // (triangles: not kSphereBvh)
+inline bool is_grid_kernel(int k) { return k == kGrid || k == kGridPools; }
+
 }  // namespace
 
 // An instanced mesh scene (spt_set_instances): per model its host triangle records and its device descriptor (the MParams of a
@@ -76,17 +79,16 @@ struct spt_ctx {
     int last_share = 0;            // ... the one the last pool launch ran
     float* d_stack = nullptr;      // pool kernel: global-memory stack of pending transmitted children
     size_t stack_cap = 0;          // in floats
-    bool last_was_pool = false;
-    int last_kernel = 0;           // 0 megakernel, 1 pool kernel, 2 mesh kernel (triangles; 6 / 7: through the exact / the plain hierarchy), 3 mesh kernel over a sphere hierarchy, 4 grid kernel (lanes own paths), 5 grid kernel with path pools, 8 mesh kernel over instances
+    int last_kernel = kMega;       // RenderKernel of the last render launch (spt_last_kernel)
     // triangle-mesh scene (spt_set_meshes); mesh_scene selects it for spt_render*
     bool mesh_scene = false;
     bool mesh_specular = false;            // a mesh material is SPEC or REFR: long mirror / glass chains are possible (task dealing of the hierarchy kernel)
     float4* d_tris = nullptr; uint4* d_tri_index = nullptr; float4* d_verts = nullptr; uint32_t* d_inst_first = nullptr; float4* d_mesh_mats = nullptr;
     float* d_trace_rays = nullptr; float* d_trace_hits = nullptr; uint64_t trace_cap = 0;   // spt_trace_rays staging (rays)
-    float* d_range_rays = nullptr; uint64_t range_cap = 0;   // spt_trace_*_range staging (32-byte rays; the hits go to d_trace_hits)
+    float* d_range_rays = nullptr; size_t range_cap = 0;     // spt_trace_*_range staging (32-byte rays, cap in floats; the hits go to d_trace_hits)
     // spt_trace_spheres*: the rays a walk hands to the exhaustive loop (one launch's worth), {count of the launch, pad, total of the query}, the
     // query's completion (a query waits for its predecessor: they share these), what the last query ran through (-1: none yet)
-    uint32_t* d_qlist = nullptr; uint64_t qlist_cap = 0; uint32_t* d_qcount = nullptr;
+    uint32_t* d_qlist = nullptr; size_t qlist_cap = 0; uint32_t* d_qcount = nullptr;
     hipEvent_t ev_query = nullptr; bool query_pending = false; int query_path = -1;
     std::vector<float4> h_geom;      // host copy of the sphere table {centre, r*r} and the radii: its hierarchy is built on demand
     std::vector<float> h_radius;
@@ -108,7 +110,7 @@ struct spt_ctx {
     bool bvh_ready = false;          // the hierarchy below belongs to the current mesh scene
     float4* d_bvh_nodes = nullptr; float4* d_bvh_tris = nullptr; uint32_t* d_bvh_index = nullptr;
     float4* d_flat_lines = nullptr; uint32_t* d_flat_line_index = nullptr; uint32_t nline_slots = 0; bool bvh_flat = false;     // thin triangles as a table (spt_tribvh.h (3))
-    uint32_t* d_cam_planes = nullptr; uint32_t ncam = 0, cam_cap = 0; float cam_key[4] = {0, 0, 0, 0}; bool cam_valid = false;   // spt_bvh.h camera_planes of the last pinhole origin
+    uint32_t* d_cam_planes = nullptr; uint32_t ncam = 0; size_t cam_cap = 0; float cam_key[4] = {0, 0, 0, 0}; bool cam_valid = false;   // spt_bvh.h camera_planes of the last pinhole origin
     float4* d_bvh_cones = nullptr; float4* d_plane_nodes = nullptr; float4* d_line_nodes = nullptr; bool have_planes = false, have_lines = false;   // spt_tribvh.h
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0;
     uint32_t bvh_thin = 0;           // thin triangles of the structures above (spt_mesh_line_form)
@@ -178,6 +180,19 @@ struct spt_ctx {
         hipError_t e__ = (call);                                                                 \
         if (e__ != hipSuccess) return (ctx)->fail("%s failed: %s", #call, hipGetErrorString(e__)); \
     } while (0)
+
+// Grows a device scratch buffer to room for `need` elements (nothing to do when it has it): frees, allocates `alloc` elements (by default
+// `need`) and sets the capacity only once the allocation stands.  The contents are not kept.
+template <typename T>
+static hipError_t grow(T*& ptr, size_t& cap, size_t need, size_t alloc = 0)
+{
+    if (need <= cap) return hipSuccess;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr; cap = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), (alloc ? alloc : need) * sizeof(T));
+    if (e == hipSuccess) cap = need;
+    return e;
+}
 
 extern "C" {
 
@@ -310,7 +325,7 @@ int spt_set_grid_pools(spt_ctx* c, int lane_owned, uint32_t slots, uint32_t read
 int spt_set_tuning(spt_ctx* c, uint32_t blocks_per_cu, uint32_t variant)
 {
     if (!c) return 1;
-    const uint32_t psel = (variant >> 11) & 3u;                   // pool slots per wave: 1 -> 96 and 2 -> 192 exist in -DSPT_POOL_SIZES builds only
+    const uint32_t psel = (variant >> kTunePoolSizeShift) & kTunePoolSizeMask;   // pool slots per wave: 1 -> 96 and 2 -> 192 exist in -DSPT_POOL_SIZES builds only
     const int pool = psel == 1 ? 96 : (psel == 2 ? 192 : (psel == 3 ? 128 : spt_pool_default_slots()));
     if (!spt_pool_has_size(pool)) return c->fail("spt_set_tuning: this build carries no pool kernel with %d slots per wave (bits 12:11 = %u)", pool, psel);
     c->blocks_per_cu = blocks_per_cu;
@@ -496,7 +511,7 @@ static int build_sphere_grid_tables(spt_ctx* c)
 {
     c->grid_ready = false;
     GridChoice choice;
-    choose_grid_placement(c->h_geom.data(), c->h_radius.data(), c->n, (c->variant >> 24) & 0xFFu, c->grid_force_global, c->needs_guard, (uint32_t)spt_pool_max_spheres(), choice);
+    choose_grid_placement(c->h_geom.data(), c->h_radius.data(), c->n, (c->variant >> kTuneGridCellsShift) & kTuneGridCellsMask, c->grid_force_global, c->needs_guard, (uint32_t)spt_pool_max_spheres(), choice);
     if (choice.placement < 0) { c->grid_why = choice.why; return 0; }
     c->grid_global = choice.placement;
     const spt::SphereGrid& g = choice.g;
@@ -1134,6 +1149,23 @@ static spt::MParams mesh_params(const spt_ctx* c, int mode)
     return M;
 }
 
+// The hierarchy over the current sphere table (build_sphere_accel) as the mesh kernels and the queries take it.
+static spt::MParams sphere_bvh_params(const spt_ctx* c)
+{
+    spt::MParams M{};
+    M.bvh_nodes = c->d_sbvh_nodes; M.bvh_tris = c->d_sbvh_geom; M.bvh_index = c->d_sbvh_index;
+    M.always = c->d_sbvh_always; M.nalways = c->sbvh_nalways; M.sphere_mode = 1u;
+    return M;
+}
+
+// Workgroups of a query or feature-buffer launch through the current grid: 1024 threads each, 160 KB of LDS per CU.
+static uint32_t grid_query_blocks(const spt_ctx* c)
+{
+    const size_t lds = c->grid_global == 1 ? 0 : (c->grid_global == 2 ? spt_grid_lds_bytes_tables(&c->grid) : spt_grid_lds_bytes(&c->grid));
+    const uint32_t per_cu = lds == 0 ? 2u : (lds * 2 <= (size_t)160 * 1024 ? 2u : 1u);
+    return (uint32_t)(c->cu_count > 0 ? c->cu_count : 1) * per_cu;
+}
+
 // Instanced scenes: the closest-hit query (range = 0: 6 floats per ray; 1: 8) through each model's exact hierarchy unless the mode is
 // SPT_ACCEL_EXHAUSTIVE (SPT_ACCEL_BVH_FAST included: the models carry no plain-hierarchy form).
 static int inst_trace_enqueue(spt_ctx* c, int range, const float* d_rays, uint64_t n, float* d_hits, hipStream_t st)
@@ -1227,29 +1259,18 @@ static int sphere_query_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, flo
     if (!c->ev_query) SPT_HIP(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
     if (!c->d_qcount) SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_qcount), 16));
     const uint64_t slice_cap = n < spt::kQuerySlice ? n : spt::kQuerySlice;
-    if (path != spt::kQueryExhaustive && slice_cap > c->qlist_cap) {
-        if (c->d_qlist) (void)hipFree(c->d_qlist);           // (hipFree waits for the device: no launch still reads the old list)
-        c->d_qlist = nullptr; c->qlist_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_qlist), slice_cap * sizeof(uint32_t)));
-        c->qlist_cap = slice_cap;
-    }
+    if (path != spt::kQueryExhaustive) SPT_HIP(c, grow(c->d_qlist, c->qlist_cap, slice_cap));   // (hipFree waits for the device: no launch still reads the old list)
     if (c->query_pending) SPT_HIP(c, hipStreamWaitEvent(st, c->ev_query, 0));   // the previous query (any stream) has released the list
     SPT_HIP(c, hipMemsetAsync(c->d_qcount, 0, 16, st));
     const int guard_all = c->needs_guard ? 1 : 0;
     const uint32_t list_blocks = (uint32_t)(c->cu_count > 0 ? c->cu_count : 1) * 8u;
-    uint32_t grid_blocks = 0;
+    const uint32_t grid_blocks = path == spt::kQueryGrid ? grid_query_blocks(c) : 0u;
     int where = c->grid_global;
-    if (path == spt::kQueryGrid) {
-        const size_t lds = where == 1 ? 0 : (where == 2 ? spt_grid_lds_bytes_tables(&c->grid) : spt_grid_lds_bytes(&c->grid));
-        const uint32_t per_cu = lds == 0 ? 2u : (lds * 2 <= (size_t)160 * 1024 ? 2u : 1u);   // 1024-thread workgroups, 160 KB of LDS per CU
-        grid_blocks = (uint32_t)(c->cu_count > 0 ? c->cu_count : 1) * per_cu;
-    }
     spt::KParams K{};
     spt::MParams M{};
     if (path == spt::kQueryBvh) {
         K.geom = c->d_geom; K.n = c->n;
-        M.bvh_nodes = c->d_sbvh_nodes; M.bvh_tris = c->d_sbvh_geom; M.bvh_index = c->d_sbvh_index;
-        M.always = c->d_sbvh_always; M.nalways = c->sbvh_nalways; M.sphere_mode = 1u;
+        M = sphere_bvh_params(c);
     }
     for (uint64_t first = 0; first < n; first += spt::kQuerySlice) {
         const uint32_t m = (uint32_t)(n - first < spt::kQuerySlice ? n - first : spt::kQuerySlice);
@@ -1431,12 +1452,7 @@ static hipError_t ensure_range_staging(spt_ctx* c, uint64_t n)
 {
     static_assert(sizeof(spt_ray_range) == 32, "OptixRay layout (RTP_BUFFER_FORMAT_RAY_ORIGIN_TMIN_DIRECTION_TMAX)");
     hipError_t e = ensure_trace_staging(c, n);
-    if (e == hipSuccess && n > c->range_cap) {
-        if (c->d_range_rays) (void)hipFree(c->d_range_rays);
-        c->d_range_rays = nullptr; c->range_cap = 0;
-        e = hipMalloc(reinterpret_cast<void**>(&c->d_range_rays), n * sizeof(spt_ray_range));
-        if (e == hipSuccess) c->range_cap = n;
-    }
+    if (e == hipSuccess) e = grow(c->d_range_rays, c->range_cap, (size_t)n * (sizeof(spt_ray_range) / sizeof(float)));
     return e;
 }
 
@@ -1601,6 +1617,33 @@ int spt_render_interleaved_device(spt_ctx* c, const spt_camera* cam, uint32_t w,
     return render_rows_impl(c, cam, w, h, rank * block_rows, rows, lb, world * block_rows, block_rows - 1u, samps, seed, flags, d_out_rgb, hip_stream);
 }
 
+// D9: a jitter cell's samples are accumulated in nb = 1, 2, 4 or 8 blocks (>= 16 samples each); one task = one block
+static uint32_t sample_blocks_log2(uint32_t samps) { return samps >= 128u ? 3u : (samps >= 64u ? 2u : (samps >= 32u ? 1u : 0u)); }
+
+// What a render and a feature-buffer launch share of KParams: camera, image, a contiguous row band, sample blocks, seed, the sphere table
+// (none in a mesh scene) and the cells.  The caller has validated the arguments and grown the cells.
+static void fill_kparams(const spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                         uint32_t samps, uint64_t seed, spt::KParams& P)
+{
+    std::memcpy(P.cam_o, cam->origin, 12); std::memcpy(P.cam_d, cam->dir, 12);
+    std::memcpy(P.cam_cx, cam->cx, 12); std::memcpy(P.cam_cy, cam->cy, 12);
+    P.cam_push = cam->push;
+    P.sampler = cam->sampler;
+    P.inv_wf = 1.f / (float)w; P.inv_hf = 1.f / (float)h;   // pixelSize, smallpt.cpp:746
+    P.w = w; P.h = h; P.row_begin = row_begin; P.row_count = row_count;
+    P.rb_log2 = 0u; P.rb_stride = 1u; P.rb_mask = 0u;
+    P.inv_w = 1.0 / (double)w; P.inv_h = 1.0 / (double)h;
+    P.nb_log2 = sample_blocks_log2(samps);
+    const uint32_t nb = 1u << P.nb_log2;
+    P.samps = samps; P.ntasks = (uint32_t)((uint64_t)row_count * w * 4 * nb);
+    P.sb = (samps + nb - 1u) / nb;
+    P.s0 = mix32((uint32_t)seed + 0x243F6A88u);
+    P.s1 = mix32((uint32_t)(seed >> 32) ^ P.s0 ^ 0x85A308D3u);
+    P.n = c->mesh_scene ? 0u : c->n; P.n_pad = P.n ? P.n : 1u;
+    P.geom = c->mesh_scene ? nullptr : c->d_geom; P.mat = c->mesh_scene ? nullptr : c->d_mat;
+    P.cells = c->d_cells;
+}
+
 // The regular triangles in whose plane the camera's origin lies (spt_bvh.h camera_planes), for the depth-0 rays of a launch through the
 // exact hierarchy; cached per camera origin and push extent.  Fills M.cam_planes / ncam / cam_cull.
 static int camera_plane_list(spt_ctx* c, const spt_camera* cam, hipStream_t st, spt::MParams& M)
@@ -1615,12 +1658,7 @@ static int camera_plane_list(spt_ctx* c, const spt_camera* cam, hipStream_t st, 
     if (!c->cam_valid || std::memcmp(c->cam_key, key, sizeof c->cam_key) != 0) {
         std::vector<uint32_t> list;
         spt::camera_planes(c->h_tris.data(), c->ntris, cam->origin, extra, list);
-        if (list.size() > c->cam_cap) {
-            if (c->d_cam_planes) (void)hipFree(c->d_cam_planes);
-            c->d_cam_planes = nullptr; c->cam_cap = 0;
-            SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cam_planes), list.size() * sizeof(uint32_t)));
-            c->cam_cap = (uint32_t)list.size();
-        }
+        SPT_HIP(c, grow(c->d_cam_planes, c->cam_cap, list.size()));
         if (!list.empty()) SPT_HIP(c, hipMemcpyAsync(c->d_cam_planes, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         if (!list.empty()) SPT_HIP(c, hipStreamSynchronize(st));           // (the list is a local)
         c->ncam = (uint32_t)list.size();
@@ -1629,6 +1667,264 @@ static int camera_plane_list(spt_ctx* c, const spt_camera* cam, hipStream_t st, 
     }
     M.cam_planes = c->d_cam_planes; M.ncam = c->ncam; M.cam_cull = 1u;
     return 0;
+}
+
+// ---- the render launch path: choose_route decides which kernel runs, one launch_* per kernel family prepares and launches it between
+// begin_launch and finish_launch, and render_rows_impl validates, fills the shared parameters and dispatches ----
+
+// The wave-private path pools of spt_gpool.hip for the current grid, if the tables leave the LDS for them: R begun walks of 64 bytes + two byte
+// lists per wave beside the grid tables.  spt_set_grid_pools (internal) keeps the lane-owned kernel or changes the pool geometry;
+// SPT_GPOOL="S,R,drain,min_batch[,walk_iters]" overrides it per process (tools).  Fills Q except its slots.
+static bool grid_pools_fit(const spt_ctx* c, uint32_t threads, spt::QParams& Q)
+{
+    if (c->grid_lane_owned || c->grid_global) return false;
+    static const char* env = std::getenv("SPT_GPOOL");
+    uint32_t S = c->gq[0], Rwant = c->gq[1], drain = c->gq[2], minb = c->gq[3], witers = c->gq[4];
+    if (env) { unsigned a = 0, b2 = 0, d2 = 0, m2 = 0, w2 = 0; const int got = std::sscanf(env, "%u,%u,%u,%u,%u", &a, &b2, &d2, &m2, &w2); if (got >= 4) { S = a; Rwant = b2; drain = d2; minb = m2; } if (got == 5) witers = w2; }
+    const uint32_t waves = threads / 64u;
+    const size_t fixed = spt_gpool_lds_bytes(&c->grid, waves, S, 0);
+    const size_t room = fixed < (size_t)160 * 1024 ? (size_t)160 * 1024 - fixed : 0;
+    uint32_t R = (uint32_t)(room / ((size_t)waves * 64u)) & ~3u;
+    if (R > Rwant) R = Rwant & ~3u;
+    Q.S = S; Q.R = R; Q.drain = drain; Q.min_batch = minb; Q.walk_iters = witers ? witers : 1u;
+    return R >= 48u && c->n <= 0xC000u && c->grid.nrefs < 0x7FFEu;
+}
+
+// grid kernels: one 1024-thread workgroup per CU shares the LDS tables (tuning: variant bits 15:13 = threads / 128 - 1 ... 0 = 1024; blocks_per_cu)
+static uint32_t grid_render_threads(const spt_ctx* c)
+{
+    const uint32_t tsel = (c->variant >> kTuneGridThreadsShift) & kTuneGridThreadsMask;
+    return tsel ? 128u * (tsel + 1u) : (uint32_t)spt_grid_block_threads();
+}
+static uint32_t grid_render_blocks(const spt_ctx* c) { return (uint32_t)c->cu_count * (c->blocks_per_cu ? c->blocks_per_cu : 1u); }
+
+// Which kernel renders the current scene for a camera whose largest |origin coordinate| or |push| is cam_big.  The order of the tests matters: a
+// grid scene whose launch conditions this call does not meet falls through to the hierarchy or the exhaustive kernels, and only a table that
+// none of them takes (above SPT_MAX_SPHERES, no hierarchy) is refused.  mode = the closest-hit mode of a mesh scene's launch (mesh_mode);
+// Q = the pool geometry of kGridPools.
+static RenderKernel choose_route(const spt_ctx* c, float cam_big, int& mode, spt::QParams& Q)
+{
+    mode = SPT_ACCEL_EXHAUSTIVE;
+    // the grid and the pool kernel run without the range guard of the square root (coordinates within 1e15); tuning bit 10 forces the megakernel where either would run
+    const bool fast_kernels = cam_big <= 1e15f && !(c->variant & kTuneForceMega);
+    // large sphere table through its uniform grid (spt_grid.hip / spt_gpool.hip): the default above the pool kernel's limit
+    if (!c->mesh_scene && c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready && fast_kernels)
+        return grid_pools_fit(c, grid_render_threads(c), Q) ? kGridPools : kGrid;
+    // a sphere table too large for the pool kernel through its hierarchy (spt_mesh.hip)
+    const bool sphere_bvh = !c->mesh_scene && c->sbvh_ready && c->n > (uint32_t)spt_pool_max_spheres() &&
+                            (c->sphere_accel == SPT_ACCEL_BVH || (c->sphere_accel == SPT_ACCEL_GRID && !c->grid_ready && c->n >= kSphereBvhFrom && !c->needs_guard));
+    if (!c->mesh_scene && !sphere_bvh && c->n > SPT_MAX_SPHERES) return kRefused;    // (a grid table whose launch conditions this call does not meet)
+    if (sphere_bvh) return kSphereBvh;
+    if (c->mesh_scene) {
+        mode = mesh_mode(c, true);
+        return c->inst_scene ? kMeshInst : (mode == SPT_ACCEL_BVH ? kMeshBvh : (mode == SPT_ACCEL_BVH_FAST ? kMeshBvhFast : kMesh));
+    }
+    // material-sorted pool kernel (spt_pool.hip): small tables, regular scenes; it has no instrumented build
+    if (c->pool_ok && fast_kernels && !(c->variant & kTuneStats)) return kPool;
+    return kMega;
+}
+
+static int begin_launch(spt_ctx* c, hipStream_t st)
+{
+    SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
+    SPT_HIP(c, hipEventRecord(c->ev_start, st));
+    return 0;
+}
+
+// Folds the launch's cells into the image and records what ran.  A launch that fails before this point leaves last_kernel as it was.
+static int finish_launch(spt_ctx* c, hipStream_t st, const spt::KParams& P, RenderKernel kernel, uint32_t blocks, uint32_t threads, uint32_t flags, float* d_out)
+{
+    const uint32_t npix = P.row_count * P.w;
+    const float scale = 1.0f / (float)(4u * P.samps);   // smallpt.cpp:360 operator/=(float3, float)
+    SPT_HIP(c, hipEventRecord(c->ev_mid, st));
+    SPT_HIP(c, spt_k_finalize(c->d_cells, d_out, npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, 1u << P.nb_log2, st));
+    SPT_HIP(c, hipEventRecord(c->ev_stop, st));
+    c->pending = true;
+    c->last_kernel = kernel;
+    c->last = spt_stats{};
+    c->last.samples = (uint64_t)npix * 4ull * P.samps;
+    c->last.grid_blocks = blocks;
+    c->last.block_threads = threads;
+    return 0;
+}
+
+static int launch_grid(spt_ctx* c, spt::KParams& P, hipStream_t st, const float* radiance, uint32_t flags, float* d_out)
+{
+    const uint32_t threads = grid_render_threads(c), blocks = grid_render_blocks(c);
+    SPT_HIP(c, grow(c->d_stack, c->stack_cap, spt_grid_stack_floats(blocks, threads)));
+    P.stack = c->d_stack;
+    P.watchdog_ticks = c->watchdog_ticks;
+    const uint32_t lsel = (c->variant >> kTuneGridLeaveShift) & kTuneGridLeaveMask;
+    if (begin_launch(c, st)) return 1;
+    SPT_HIP(c, spt_grid_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, blocks, threads, lsel ? lsel - 1u : 16u, (c->variant & kTuneStats) ? 1 : 0,
+                               c->grid_global, st, radiance));
+    return finish_launch(c, st, P, kGrid, blocks, threads, flags, d_out);
+}
+
+// round 4: wave-private path pools with register-resident walkers (spt_gpool.hip); Q from grid_pools_fit
+static int launch_gpool(spt_ctx* c, spt::KParams& P, spt::QParams& Q, hipStream_t st, const float* radiance, uint32_t flags, float* d_out)
+{
+    const uint32_t threads = grid_render_threads(c), blocks = grid_render_blocks(c), waves = threads / 64u;
+    // one allocation: the children stack followed by the slots
+    const size_t stack_floats = spt_gpool_stack_floats(blocks, waves, Q.S);
+    SPT_HIP(c, grow(c->d_stack, c->stack_cap, stack_floats + spt_gpool_slot_floats(blocks, waves, Q.S)));
+    P.stack = c->d_stack;
+    P.watchdog_ticks = c->watchdog_ticks;
+    Q.slots = reinterpret_cast<float4*>(c->d_stack + stack_floats);
+    if (begin_launch(c, st)) return 1;
+    SPT_HIP(c, spt_gpool_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, &Q, blocks, threads, (c->variant & kTuneStats) ? 1 : 0, st, radiance));
+    return finish_launch(c, st, P, kGridPools, blocks, threads, flags, d_out);
+}
+
+// triangle-mesh scene, instanced or not, or a sphere table through its hierarchy (spt_mesh.hip); kernel and mode from choose_route
+static int launch_mesh(spt_ctx* c, spt::KParams& P, RenderKernel kernel, int mode, const spt_camera* cam, hipStream_t st, const float* radiance, uint32_t flags, float* d_out)
+{
+    // (a short launch -- the viewer's frames -- takes three workgroups per CU instead of four: 661 -> 672 frames/s on the shipped scene
+    // through the hierarchy at 1280x720 x 4 spp, 949 -> 1033 with two frames in flight, which then share the CUs; tools/ab_mesh_viewer_blocks.py)
+    if (c->mesh_scene) c->last_mesh_mode = mode;
+    const bool through_hierarchy = kernel == kSphereBvh || mode != SPT_ACCEL_EXHAUSTIVE;   // (the exhaustive tile loop keeps four)
+    const uint64_t samples = (uint64_t)P.row_count * P.w * 4ull * P.samps;
+    const uint32_t mesh_per_cu = c->blocks_per_cu ? c->blocks_per_cu : (through_hierarchy && samples < (4ull << 20) ? 3u : 4u);
+    uint64_t blocks = (uint64_t)c->cu_count * mesh_per_cu;
+    const uint64_t needed = ((uint64_t)P.ntasks + 255) / 256;
+    if (blocks > needed) blocks = needed;
+    if (blocks < 1) blocks = 1;
+    SPT_HIP(c, grow(c->d_stack, c->stack_cap, spt_mesh_stack_floats((uint32_t)blocks)));
+    P.stack = c->d_stack;
+    spt::MParams M{};
+    if (kernel == kSphereBvh) {
+        M = sphere_bvh_params(c);
+    } else if (c->inst_scene) {                              // (no camera-plane list: depth-0 rays walk each model's plane tree)
+        M = inst_render_params(c);
+    } else {
+        M = mesh_params(c, mode);
+        if (M.plane_nodes && camera_plane_list(c, cam, st, M)) return 1;
+    }
+    if (begin_launch(c, st)) return 1;
+    if (c->inst_scene) {
+        const spt::IParams I = inst_params(c);
+        SPT_HIP(c, spt_inst_launch(&P, &M, &I, mode != SPT_ACCEL_EXHAUSTIVE, (uint32_t)blocks, st, radiance));
+    } else {
+        SPT_HIP(c, spt_mesh_launch(&P, &M, (uint32_t)blocks, st, radiance));
+    }
+    return finish_launch(c, st, P, kernel, (uint32_t)blocks, 256, flags, d_out);
+}
+
+// material-sorted pool kernel (spt_pool.hip)
+static int launch_pool(spt_ctx* c, spt::KParams& P, const spt_camera* cam, uint64_t seed, hipStream_t st, const float* radiance, uint32_t flags, float* d_out)
+{
+    const uint64_t samples = (uint64_t)P.row_count * P.w * 4ull * P.samps;
+    const uint32_t psel = (c->variant >> kTunePoolSizeShift) & kTunePoolSizeMask;
+    const int pool = psel == 1 ? 96 : (psel == 2 ? 192 : (psel == 3 ? 128 : spt_pool_default_slots()));   // default: four workgroups per CU
+    const size_t lds = spt_pool_lds_bytes(P.n, pool) + (radiance ? 16u : 0u);   // (+ E behind the material table)
+    uint32_t per_cu = c->blocks_per_cu;
+    if (per_cu == 0) {
+        const uint32_t by_lds = (uint32_t)((160u * 1024u) / lds);
+        per_cu = by_lds < 1 ? 1 : (by_lds > 8 ? 8 : by_lds);
+        // A short launch (the viewer's frames: 3.7 M samples = 900 per wave of a full grid) is over before the slot pools of four
+        // workgroups per CU ever run full: with half the waves the batches are fuller, and the other half of every CU's LDS is free
+        // for the next frame's kernel when several frames are in flight.  Measured at 1280x720 x 4 spp, frames/s with 4 / 2 / 1
+        // workgroups per CU (profiles/r03_small_launch_ab.txt): one frame at a time 427 / 450 / 411, two in flight 675 / 773 / 730,
+        // four 935 / 1155 / 1152, eight 1197 / 1575 / 1756; from 8 spp on (1024x768) a single launch is faster with four again.
+        // So: launches below 4 Mi samples take two, one when six or more frames are in flight (the lanes of
+        // spt_progressive_frame_async know their number).  SPT_SMALL_LAUNCH_BLOCKS overrides (experiments).
+        static const uint32_t forced = [] { const char* e = std::getenv("SPT_SMALL_LAUNCH_BLOCKS"); return e ? (uint32_t)std::atoi(e) : 0u; }();
+        const uint32_t small_blocks = forced ? forced : (c->frames_in_flight_hint >= 6u ? 1u : 2u);
+        if (samples < (4ull << 20) && per_cu > small_blocks) per_cu = small_blocks;
+    }
+    uint64_t blocks = (uint64_t)c->cu_count * per_cu;
+    const uint64_t needed = ((uint64_t)P.ntasks + 255) / 256;
+    if (blocks > needed) blocks = needed;
+    if (blocks < 1) blocks = 1;
+    // one allocation: the children stack followed by the {task, next sample} words of every slot
+    const size_t stack_floats = spt_pool_stack_floats((uint32_t)blocks, pool);
+    SPT_HIP(c, grow(c->d_stack, c->stack_cap, stack_floats + spt_pool_state_bytes((uint32_t)blocks, pool) / sizeof(float)));
+    P.stack = c->d_stack;
+    P.slot_state = reinterpret_cast<uint2*>(c->d_stack + stack_floats);
+    P.watchdog_ticks = c->watchdog_ticks;
+    // Cost-ordered dispatch: the queue hands out chunks of 64 tasks; every launch records how long each chunk kept its wave busy, and a
+    // launch of the SAME view with the SAME seed (a repeated render) starts the expensive chunks first.  Round 3 applied the order to
+    // any seed of the view ("a pixel's cost is a property of what it looks at"); measured with the seed stepped every launch that is
+    // wrong at the granularity of a chunk -- 80.4-80.7 ms against 79.3-79.7 in the static order, also when only the most expensive
+    // 1/64 of the chunks is moved to the front (profiles/r04_cost_order_seeds.txt): a chunk's time is mostly the luck of its 2048
+    // samples and of when its wave ran it -- so the seed is part of the key now, and a new seed runs in the static order like a first
+    // launch.  Recording is not free either -- the clock stores and the three ordering kernels behind the frame cost 0.6 ms of an 80 ms
+    // launch (profiles/r04_cost_order_regions.txt) --, so a launch records only when it repeats its predecessor (same view, same seed)
+    // or an order for it exists: a progressive loop never pays, a repeated render runs twice in the static order and is ordered from
+    // its third launch on.  Results do not depend on the dispatch order.  kTuneStaticOrder switches it off for this kernel (A/B),
+    // SPT_FLAG_ONE_SHOT for one launch.
+    const uint32_t nchunks = (uint32_t)(((uint64_t)P.ntasks + 63) / 64);
+    std::vector<unsigned char> key(sizeof(spt_camera) + 10 * sizeof(uint32_t) + 2 * sizeof(uint64_t) + sizeof c->env);
+    {
+        unsigned char* k = key.data();
+        std::memcpy(k, cam, sizeof(spt_camera)); k += sizeof(spt_camera);
+        const uint32_t words[10] = {P.w, P.h, P.row_begin, P.row_count, P.rb_log2, P.rb_stride, P.rb_mask, P.samps, c->variant, (uint32_t)blocks};
+        std::memcpy(k, words, sizeof words); k += sizeof words;
+        std::memcpy(k, &c->scene_gen, sizeof(uint64_t)); k += sizeof(uint64_t);
+        std::memcpy(k, &seed, sizeof(uint64_t)); k += sizeof(uint64_t);
+        std::memcpy(k, c->env, sizeof c->env);
+    }
+    if (c->order_pending) { SPT_HIP(c, hipStreamWaitEvent(st, c->ev_order, 0)); c->order_pending = false; }
+    // (not for the viewer's frames of a few samples per cell: a chunk's time is then the luck of 64 single paths, and the order kernel
+    // between two frames costs the frames in flight more than it gains)
+    // (... and not beyond 4 Mi chunks -- 48 MB of tables; a single band of config 4's size is 1 Mi --: the tail the order removes is a
+    // fixed few milliseconds, nothing of a launch that long)
+    const bool have_order = c->order_valid && key == c->order_key;
+    const bool repeats = key == c->last_pool_key;
+    if (!(c->variant & kTuneStaticOrder) && !(flags & SPT_FLAG_ONE_SHOT) && P.samps >= 16u && nchunks <= (4u << 20) && (have_order || repeats)) {
+        // order[cap] | clock[2 * cap] | 512 words of the sorting kernels; new tables hold no order
+        if (nchunks > c->chunk_cap) c->order_valid = false;
+        SPT_HIP(c, grow(c->d_chunk_tables, c->chunk_cap, nchunks, (size_t)nchunks * 3 + 512));
+        uint32_t* const d_order = c->d_chunk_tables;
+        uint32_t* const d_clock = c->d_chunk_tables + c->chunk_cap;
+        P.chunk_order = (have_order && c->order_valid) ? d_order : nullptr;     // (order_valid: the tables may just have been re-allocated)
+        P.chunk_clock = d_clock;
+        P.nchunks = nchunks;
+        SPT_HIP(c, hipMemsetAsync(d_clock + nchunks, 0, (size_t)nchunks * sizeof(uint32_t), st));
+    }
+    if (begin_launch(c, st)) return 1;
+    // sharing pattern of the closest hit (spt_share.h): compiled for the default pool size; kTuneGenericHit forces the generic test
+    const int share = !(c->variant & kTuneGenericHit) && spt_pool_share_compiled(pool, P.n, c->share) ? c->share : spt::kShareNone;
+    // kTuneOldLoop: the bounce loop's bookkeeping as it was before it was trimmed (A/B, default pool size)
+    SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st, radiance, share, (c->variant & kTuneOldLoop) && spt_pool_has_old_loop(pool) ? 1 : 0));
+    c->last_share = share;
+    if (finish_launch(c, st, P, kPool, (uint32_t)blocks, 256, flags, d_out)) return 1;
+    if (P.chunk_clock) {                                         // (after ev_stop: not part of the frame's device time, overlaps the caller's next step)
+        SPT_HIP(c, spt_pool_chunk_order(P.chunk_clock, nchunks, P.ntasks, c->d_chunk_tables, c->d_chunk_tables + 3 * c->chunk_cap, st));
+        SPT_HIP(c, hipEventRecord(c->ev_order, st));
+        c->order_pending = true;
+        c->order_key = key;
+        c->order_valid = true;
+        c->last_nchunks = nchunks;
+    } else {
+        c->last_nchunks = 0;
+    }
+    c->last_pool_key.swap(key);
+    return 0;
+}
+
+// megakernel (spt_kernel.hip): every sphere table up to SPT_MAX_SPHERES, the guarded build for degenerate scenes and far cameras
+static int launch_mega(spt_ctx* c, spt::KParams& P, float cam_big, hipStream_t st, const float* radiance, uint32_t flags, float* d_out)
+{
+    // launch geometry: a persistent grid that fills the chip; the task queue makes any size correct
+    const int mat_lds = (c->n <= 256) ? 1 : 0;
+    const int big_block = (c->variant & kTuneBigBlock) ? 512 : 256;   // A/B on the box: 256 is faster once the LDS reads are prefetched
+    const size_t lds = spt_k_lds_bytes(P.n_pad, mat_lds, big_block);
+    const int threads = spt_k_block_threads_for(mat_lds, big_block);
+    uint32_t per_cu = c->blocks_per_cu;
+    if (per_cu == 0) {
+        const uint32_t by_lds = (uint32_t)((160u * 1024u) / lds);
+        per_cu = by_lds < 1 ? 1 : (by_lds > 8 ? 8 : by_lds);
+    }
+    uint64_t blocks = (uint64_t)c->cu_count * per_cu;
+    const uint64_t needed = ((uint64_t)P.ntasks + threads - 1) / threads;
+    if (blocks > needed) blocks = needed;
+    if (blocks < 1) blocks = 1;
+    SPT_HIP(c, grow(c->d_stack, c->stack_cap, spt_k_stack_floats((uint32_t)blocks, threads)));
+    P.stack = c->d_stack;
+    if (begin_launch(c, st)) return 1;
+    SPT_HIP(c, spt_k_launch(&P, (uint32_t)blocks, mat_lds, (c->needs_guard || !(cam_big <= 1e15f)) ? 1 : 0, (c->variant & kTuneStats) ? 1 : 0, 1, big_block, st, radiance));
+    return finish_launch(c, st, P, kMega, (uint32_t)blocks, (uint32_t)threads, flags, d_out);
 }
 
 static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
@@ -1640,331 +1936,44 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
     if ((uint64_t)w * h > 0xFFFFFFFFull) return c->fail("spt_render_rows_device: w*h exceeds 2^32-1 pixels");
     if ((uint64_t)samps * 4 > 0xFFFFFFFFull) return c->fail("spt_render_rows_device: spp overflows 32 bits");
     const uint64_t npix = (uint64_t)row_count * w;
-    // D9: a jitter cell's samples are accumulated in nb = 1, 2, 4 or 8 blocks (>= 16 samples each); one task = one block
-    const uint32_t nb_log2 = samps >= 128u ? 3u : (samps >= 64u ? 2u : (samps >= 32u ? 1u : 0u));
-    const uint32_t nb = 1u << nb_log2;
+    const uint32_t nb = 1u << sample_blocks_log2(samps);
     if (npix * 4 * nb > 0xF0000000ull) return c->fail("spt_render_rows_device: band has more than 15*2^26 sample blocks (%u per pixel); split it", 4u * nb);
     if (!c->d_geom && !c->mesh_scene) return c->fail("spt_render_rows_device: no scene set (call spt_set_scene)");
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
     c->last_aov = false;
-
-    const size_t ntasks = (size_t)npix * 4 * nb;
-    if (ntasks > c->cells_cap) {
-        if (c->d_cells) (void)hipFree(c->d_cells);
-        c->d_cells = nullptr; c->cells_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cells), ntasks * sizeof(float4)));
-        c->cells_cap = ntasks;
-    }
+    SPT_HIP(c, grow(c->d_cells, c->cells_cap, (size_t)npix * 4 * nb));
+    if (cam->sampler > SPT_SAMPLER_PINHOLE) return c->fail("spt_render_rows_device: unknown camera sampler %u", cam->sampler);
 
     spt::KParams P{};
-    std::memcpy(P.cam_o, cam->origin, 12); std::memcpy(P.cam_d, cam->dir, 12);
-    std::memcpy(P.cam_cx, cam->cx, 12); std::memcpy(P.cam_cy, cam->cy, 12);
-    P.cam_push = cam->push;
-    if (cam->sampler > SPT_SAMPLER_PINHOLE) return c->fail("spt_render_rows_device: unknown camera sampler %u", cam->sampler);
-    P.sampler = cam->sampler;
-    P.inv_wf = 1.f / (float)w; P.inv_hf = 1.f / (float)h;   // pixelSize, smallpt.cpp:746
-    P.w = w; P.h = h; P.row_begin = row_begin; P.row_count = row_count;
+    fill_kparams(c, cam, w, h, row_begin, row_count, samps, seed, P);
     P.rb_log2 = rb_log2; P.rb_stride = rb_stride; P.rb_mask = rb_mask;
-    P.inv_w = 1.0 / (double)w; P.inv_h = 1.0 / (double)h;
     spt::row_divisor(w, &P.wdiv_mul, &P.wdiv_shift);    // (valid below 2^32 / 2 cell ids: the bound on sample blocks above)
-    P.samps = samps; P.ntasks = (uint32_t)ntasks;
-    P.nb_log2 = nb_log2; P.sb = (samps + nb - 1u) / nb;
-    P.park_threshold = (c->variant & 0xFFu) ? (c->variant & 0xFFu) : 8u;
-    P.s0 = mix32((uint32_t)seed + 0x243F6A88u);
-    P.s1 = mix32((uint32_t)(seed >> 32) ^ P.s0 ^ 0x85A308D3u);
-    P.n = c->n; P.n_pad = c->n ? c->n : 1;
-    P.geom = c->d_geom; P.mat = c->d_mat;
-    P.cells = c->d_cells; P.queue = c->d_queue; P.counters = c->d_counters;
+    P.park_threshold = (c->variant & kTuneParkMask) ? (c->variant & kTuneParkMask) : 8u;
+    P.queue = c->d_queue; P.counters = c->d_counters;
 
     const float cam_big = std::fmax(std::fmax(std::fabs(cam->origin[0]), std::fabs(cam->origin[1])),
                                     std::fmax(std::fabs(cam->origin[2]), std::fabs(cam->push)));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    const float scale = 1.0f / (float)(4u * samps);   // smallpt.cpp:360 operator/=(float3, float)
+    float* const d_out = static_cast<float*>(d_out_rgb);
     // environment radiance (spt_set_environment): the kernels' environment variants, product builds only; E = 0 runs the kernels without the term
     const float* const radiance = env_on(c) ? c->env : nullptr;
-    if (radiance && (c->variant & 0x100u)) return c->fail("spt_render_rows_device: the instrumented kernels (tuning bit 8) have no environment variant; set the environment to 0");
+    if (radiance && (c->variant & kTuneStats)) return c->fail("spt_render_rows_device: the instrumented kernels (tuning bit 8) have no environment variant; set the environment to 0");
 
-    // ---- large sphere table through its uniform grid (spt_grid.hip): the default above the pool kernel's limit ----
-    if (!c->mesh_scene && c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready && cam_big <= 1e15f && !(c->variant & 0x400u)) {
-        // one 1024-thread workgroup per CU shares the LDS tables (tuning: variant bits 15:13 = threads / 128 - 1 ... 0 = 1024; blocks_per_cu)
-        const uint32_t tsel = (c->variant >> 13) & 7u;
-        const uint32_t threads = tsel ? 128u * (tsel + 1u) : (uint32_t)spt_grid_block_threads();
-        const uint32_t blocks = (uint32_t)c->cu_count * (c->blocks_per_cu ? c->blocks_per_cu : 1u);
-        const size_t need_stack = spt_grid_stack_floats(blocks, threads);
-        if (need_stack > c->stack_cap) {
-            if (c->d_stack) (void)hipFree(c->d_stack);
-            c->d_stack = nullptr; c->stack_cap = 0;
-            SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_stack), need_stack * sizeof(float)));
-            c->stack_cap = need_stack;
-        }
-        P.stack = c->d_stack;
-        P.watchdog_ticks = c->watchdog_ticks;
-        const uint32_t lsel = (c->variant >> 16) & 0xFFu;
-        // ---- round 4: wave-private path pools with register-resident walkers (spt_gpool.hip) whenever the tables leave the LDS for
-        // them: R begun walks of 64 bytes + two byte lists per wave beside the grid tables.  spt_set_grid_pools (internal) keeps the
-        // lane-owned kernel or changes the pool geometry; SPT_GPOOL="S,R,drain,min_batch[,walk_iters]" overrides it per process (tools). ----
-        if (!c->grid_lane_owned && !c->grid_global) {
-            static const char* env = std::getenv("SPT_GPOOL");
-            uint32_t S = c->gq[0], Rwant = c->gq[1], drain = c->gq[2], minb = c->gq[3], witers = c->gq[4];
-            if (env) { unsigned a = 0, b2 = 0, d2 = 0, m2 = 0, w2 = 0; const int got = std::sscanf(env, "%u,%u,%u,%u,%u", &a, &b2, &d2, &m2, &w2); if (got >= 4) { S = a; Rwant = b2; drain = d2; minb = m2; } if (got == 5) witers = w2; }
-            const uint32_t waves = threads / 64u;
-            const size_t fixed = spt_gpool_lds_bytes(&c->grid, waves, S, 0);
-            const size_t room = fixed < (size_t)160 * 1024 ? (size_t)160 * 1024 - fixed : 0;
-            uint32_t R = (uint32_t)(room / ((size_t)waves * 64u)) & ~3u;
-            if (R > Rwant) R = Rwant & ~3u;
-            if (R >= 48u && c->n <= 0xC000u && c->grid.nrefs < 0x7FFEu) {
-                const size_t stack_floats = spt_gpool_stack_floats(blocks, waves, S);
-                const size_t need = stack_floats + spt_gpool_slot_floats(blocks, waves, S);
-                if (need > c->stack_cap) {
-                    if (c->d_stack) (void)hipFree(c->d_stack);
-                    c->d_stack = nullptr; c->stack_cap = 0;
-                    SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_stack), need * sizeof(float)));
-                    c->stack_cap = need;
-                }
-                P.stack = c->d_stack;
-                spt::QParams Q{};
-                Q.slots = reinterpret_cast<float4*>(c->d_stack + stack_floats);
-                Q.S = S; Q.R = R; Q.drain = drain; Q.min_batch = minb; Q.walk_iters = witers ? witers : 1u;
-                SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
-                SPT_HIP(c, hipEventRecord(c->ev_start, st));
-                SPT_HIP(c, spt_gpool_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, &Q, blocks, threads, (c->variant & 0x100u) ? 1 : 0, st, radiance));
-                SPT_HIP(c, hipEventRecord(c->ev_mid, st));
-                SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
-                SPT_HIP(c, hipEventRecord(c->ev_stop, st));
-                c->pending = true;
-                c->last_was_pool = false;
-                c->last_kernel = 5;
-                c->last = spt_stats{};
-                c->last.samples = npix * 4ull * samps;
-                c->last.grid_blocks = blocks;
-                c->last.block_threads = threads;
-                return 0;
-            }
-        }
-        SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
-        SPT_HIP(c, hipEventRecord(c->ev_start, st));
-        SPT_HIP(c, spt_grid_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, blocks, threads, lsel ? lsel - 1u : 16u, (c->variant & 0x100u) ? 1 : 0,
-                                   c->grid_global, st, radiance));
-        SPT_HIP(c, hipEventRecord(c->ev_mid, st));
-        SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
-        SPT_HIP(c, hipEventRecord(c->ev_stop, st));
-        c->pending = true;
-        c->last_was_pool = false;
-        c->last_kernel = 4;
-        c->last = spt_stats{};
-        c->last.samples = npix * 4ull * samps;
-        c->last.grid_blocks = blocks;
-        c->last.block_threads = threads;
-        return 0;
-    }
-
-    // ---- triangle-mesh scene (spt_mesh.hip), or a sphere table too large for the pool kernel through its hierarchy ----
-    const bool sphere_bvh = !c->mesh_scene && c->sbvh_ready && c->n > (uint32_t)spt_pool_max_spheres() &&
-                            (c->sphere_accel == SPT_ACCEL_BVH || (c->sphere_accel == SPT_ACCEL_GRID && !c->grid_ready && c->n >= kSphereBvhFrom && !c->needs_guard));
-    if (!c->mesh_scene && !sphere_bvh && c->n > SPT_MAX_SPHERES)    // (a grid table whose launch conditions this call does not meet)
+    int mode = SPT_ACCEL_EXHAUSTIVE;
+    spt::QParams Q{};
+    const RenderKernel kernel = choose_route(c, cam_big, mode, Q);
+    switch (kernel) {
+    case kRefused:
         return c->fail("spt_render_rows_device: %u spheres > SPT_MAX_SPHERES (%u) render through the grid only with camera coordinates within 1e15 and without the exhaustive-kernel tuning bit; use SPT_ACCEL_BVH", c->n, SPT_MAX_SPHERES);
-    if (c->mesh_scene || sphere_bvh) {
-        // (a short launch -- the viewer's frames -- takes three workgroups per CU instead of four: 661 -> 672 frames/s on the shipped scene
-        // through the hierarchy at 1280x720 x 4 spp, 949 -> 1033 with two frames in flight, which then share the CUs; tools/ab_mesh_viewer_blocks.py)
-        const int mode = c->mesh_scene ? mesh_mode(c, true) : SPT_ACCEL_EXHAUSTIVE;
-        if (c->mesh_scene) c->last_mesh_mode = mode;
-        const bool through_hierarchy = sphere_bvh || (c->mesh_scene && mode != SPT_ACCEL_EXHAUSTIVE);   // (the exhaustive tile loop keeps four)
-        const uint32_t mesh_per_cu = c->blocks_per_cu ? c->blocks_per_cu : (through_hierarchy && npix * 4ull * samps < (4ull << 20) ? 3u : 4u);
-        uint64_t blocks = (uint64_t)c->cu_count * mesh_per_cu;
-        const uint64_t needed = (ntasks + 255) / 256;
-        if (blocks > needed) blocks = needed;
-        if (blocks < 1) blocks = 1;
-        const size_t need_stack = spt_mesh_stack_floats((uint32_t)blocks);
-        if (need_stack > c->stack_cap) {
-            if (c->d_stack) (void)hipFree(c->d_stack);
-            c->d_stack = nullptr; c->stack_cap = 0;
-            SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_stack), need_stack * sizeof(float)));
-            c->stack_cap = need_stack;
-        }
-        P.stack = c->d_stack;
-        spt::MParams M{};
-        if (sphere_bvh) {
-            M.bvh_nodes = c->d_sbvh_nodes; M.bvh_tris = c->d_sbvh_geom; M.bvh_index = c->d_sbvh_index;
-            M.always = c->d_sbvh_always; M.nalways = c->sbvh_nalways; M.sphere_mode = 1u;
-        } else if (c->inst_scene) {                              // (no camera-plane list: depth-0 rays walk each model's plane tree)
-            P.n = 0; P.n_pad = 1; P.geom = nullptr; P.mat = nullptr;
-            M = inst_render_params(c);
-        } else {
-            P.n = 0; P.n_pad = 1; P.geom = nullptr; P.mat = nullptr;
-            M = mesh_params(c, mode);
-            if (M.plane_nodes && camera_plane_list(c, cam, st, M)) return 1;
-        }
-        SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
-        SPT_HIP(c, hipEventRecord(c->ev_start, st));
-        if (c->inst_scene) {
-            const spt::IParams I = inst_params(c);
-            SPT_HIP(c, spt_inst_launch(&P, &M, &I, mode != SPT_ACCEL_EXHAUSTIVE, (uint32_t)blocks, st, radiance));
-        } else {
-            SPT_HIP(c, spt_mesh_launch(&P, &M, (uint32_t)blocks, st, radiance));
-        }
-        SPT_HIP(c, hipEventRecord(c->ev_mid, st));
-        SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
-        SPT_HIP(c, hipEventRecord(c->ev_stop, st));
-        c->pending = true;
-        c->last_was_pool = false;
-        c->last_kernel = sphere_bvh ? 3 : c->inst_scene ? 8 : (mode == SPT_ACCEL_BVH ? 6 : (mode == SPT_ACCEL_BVH_FAST ? 7 : 2));
-        c->last = spt_stats{};
-        c->last.samples = npix * 4ull * samps;
-        c->last.grid_blocks = (uint32_t)blocks;
-        c->last.block_threads = 256;
-        return 0;
+    case kGrid: return launch_grid(c, P, st, radiance, flags, d_out);
+    case kGridPools: return launch_gpool(c, P, Q, st, radiance, flags, d_out);
+    case kSphereBvh: case kMesh: case kMeshBvh: case kMeshBvhFast: case kMeshInst:
+        return launch_mesh(c, P, kernel, mode, cam, st, radiance, flags, d_out);
+    case kPool: return launch_pool(c, P, cam, seed, st, radiance, flags, d_out);
+    case kMega: return launch_mega(c, P, cam_big, st, radiance, flags, d_out);
     }
-
-    // ---- material-sorted pool kernel (spt_pool.hip): small tables, regular scenes; variant bit 10 forces the megakernel ----
-    if (c->pool_ok && cam_big <= 1e15f && !(c->variant & 0x500u)) {
-        const uint32_t psel = (c->variant >> 11) & 3u;
-        const int pool = psel == 1 ? 96 : (psel == 2 ? 192 : (psel == 3 ? 128 : spt_pool_default_slots()));   // default: four workgroups per CU
-        const size_t lds = spt_pool_lds_bytes(P.n, pool) + (radiance ? 16u : 0u);   // (+ E behind the material table)
-        uint32_t per_cu = c->blocks_per_cu;
-        if (per_cu == 0) {
-            const uint32_t by_lds = (uint32_t)((160u * 1024u) / lds);
-            per_cu = by_lds < 1 ? 1 : (by_lds > 8 ? 8 : by_lds);
-            // A short launch (the viewer's frames: 3.7 M samples = 900 per wave of a full grid) is over before the slot pools of four
-            // workgroups per CU ever run full: with half the waves the batches are fuller, and the other half of every CU's LDS is free
-            // for the next frame's kernel when several frames are in flight.  Measured at 1280x720 x 4 spp, frames/s with 4 / 2 / 1
-            // workgroups per CU (profiles/r03_small_launch_ab.txt): one frame at a time 427 / 450 / 411, two in flight 675 / 773 / 730,
-            // four 935 / 1155 / 1152, eight 1197 / 1575 / 1756; from 8 spp on (1024x768) a single launch is faster with four again.
-            // So: launches below 4 Mi samples take two, one when six or more frames are in flight (the lanes of
-            // spt_progressive_frame_async know their number).  SPT_SMALL_LAUNCH_BLOCKS overrides (experiments).
-            static const uint32_t forced = [] { const char* e = std::getenv("SPT_SMALL_LAUNCH_BLOCKS"); return e ? (uint32_t)std::atoi(e) : 0u; }();
-            const uint32_t small_blocks = forced ? forced : (c->frames_in_flight_hint >= 6u ? 1u : 2u);
-            if (npix * 4ull * samps < (4ull << 20) && per_cu > small_blocks) per_cu = small_blocks;
-        }
-        uint64_t blocks = (uint64_t)c->cu_count * per_cu;
-        const uint64_t needed = (ntasks + 255) / 256;
-        if (blocks > needed) blocks = needed;
-        if (blocks < 1) blocks = 1;
-        // one allocation: the children stack followed by the {task, next sample} words of every slot
-        const size_t stack_floats = spt_pool_stack_floats((uint32_t)blocks, pool);
-        const size_t need_stack = stack_floats + spt_pool_state_bytes((uint32_t)blocks, pool) / sizeof(float);
-        if (need_stack > c->stack_cap) {
-            if (c->d_stack) (void)hipFree(c->d_stack);
-            c->d_stack = nullptr; c->stack_cap = 0;
-            SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_stack), need_stack * sizeof(float)));
-            c->stack_cap = need_stack;
-        }
-        P.stack = c->d_stack;
-        P.slot_state = reinterpret_cast<uint2*>(c->d_stack + stack_floats);
-        P.watchdog_ticks = c->watchdog_ticks;
-        // Cost-ordered dispatch: the queue hands out chunks of 64 tasks; every launch records how long each chunk kept its wave busy, and a
-        // launch of the SAME view with the SAME seed (a repeated render) starts the expensive chunks first.  Round 3 applied the order to
-        // any seed of the view ("a pixel's cost is a property of what it looks at"); measured with the seed stepped every launch that is
-        // wrong at the granularity of a chunk -- 80.4-80.7 ms against 79.3-79.7 in the static order, also when only the most expensive
-        // 1/64 of the chunks is moved to the front (profiles/r04_cost_order_seeds.txt): a chunk's time is mostly the luck of its 2048
-        // samples and of when its wave ran it -- so the seed is part of the key now, and a new seed runs in the static order like a first
-        // launch.  Recording is not free either -- the clock stores and the three ordering kernels behind the frame cost 0.6 ms of an 80 ms
-        // launch (profiles/r04_cost_order_regions.txt) --, so a launch records only when it repeats its predecessor (same view, same seed)
-        // or an order for it exists: a progressive loop never pays, a repeated render runs twice in the static order and is ordered from
-        // its third launch on.  Results do not depend on the dispatch order.  Tuning bit 13 switches it off for this kernel (A/B),
-        // SPT_FLAG_ONE_SHOT for one launch.
-        const uint32_t nchunks = (uint32_t)((ntasks + 63) / 64);
-        std::vector<unsigned char> key(sizeof(spt_camera) + 10 * sizeof(uint32_t) + 2 * sizeof(uint64_t) + sizeof c->env);
-        {
-            unsigned char* k = key.data();
-            std::memcpy(k, cam, sizeof(spt_camera)); k += sizeof(spt_camera);
-            const uint32_t words[10] = {w, h, row_begin, row_count, rb_log2, rb_stride, rb_mask, samps, c->variant, (uint32_t)blocks};
-            std::memcpy(k, words, sizeof words); k += sizeof words;
-            std::memcpy(k, &c->scene_gen, sizeof(uint64_t)); k += sizeof(uint64_t);
-            std::memcpy(k, &seed, sizeof(uint64_t)); k += sizeof(uint64_t);
-            std::memcpy(k, c->env, sizeof c->env);
-        }
-        if (c->order_pending) { SPT_HIP(c, hipStreamWaitEvent(st, c->ev_order, 0)); c->order_pending = false; }
-        // (not for the viewer's frames of a few samples per cell: a chunk's time is then the luck of 64 single paths, and the order kernel
-        // between two frames costs the frames in flight more than it gains; bit 13 means something else to the grid kernel only)
-        // (... and not beyond 4 Mi chunks -- 48 MB of tables; a single band of config 4's size is 1 Mi --: the tail the order removes is a
-        // fixed few milliseconds, nothing of a launch that long)
-        const bool have_order = c->order_valid && key == c->order_key;
-        const bool repeats = key == c->last_pool_key;
-        if (!(c->variant & 0x2000u) && !(flags & SPT_FLAG_ONE_SHOT) && samps >= 16u && nchunks <= (4u << 20) && (have_order || repeats)) {
-            if (nchunks > c->chunk_cap) {
-                if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
-                c->d_chunk_tables = nullptr; c->chunk_cap = 0; c->order_valid = false;
-                SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_chunk_tables), ((size_t)nchunks * 3 + 512) * sizeof(uint32_t)));
-                c->chunk_cap = nchunks;
-            }
-            uint32_t* const d_order = c->d_chunk_tables;
-            uint32_t* const d_clock = c->d_chunk_tables + c->chunk_cap;
-            P.chunk_order = (have_order && c->order_valid) ? d_order : nullptr;     // (order_valid: the tables may just have been re-allocated)
-            P.chunk_clock = d_clock;
-            P.nchunks = nchunks;
-            SPT_HIP(c, hipMemsetAsync(d_clock + nchunks, 0, (size_t)nchunks * sizeof(uint32_t), st));
-        }
-        SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
-        SPT_HIP(c, hipEventRecord(c->ev_start, st));
-        // sharing pattern of the closest hit (spt_share.h): compiled for the default pool size; tuning bit 14 forces the generic test
-        const int share = !(c->variant & 0x4000u) && spt_pool_share_compiled(pool, P.n, c->share) ? c->share : spt::kShareNone;
-        // tuning bit 15: the bounce loop's bookkeeping as it was before it was trimmed (A/B, default pool size)
-        SPT_HIP(c, spt_pool_launch(&P, (uint32_t)blocks, pool, st, radiance, share, (c->variant & 0x8000u) && spt_pool_has_old_loop(pool) ? 1 : 0));
-        c->last_share = share;
-        SPT_HIP(c, hipEventRecord(c->ev_mid, st));
-        SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
-        SPT_HIP(c, hipEventRecord(c->ev_stop, st));
-        if (P.chunk_clock) {                                         // (after ev_stop: not part of the frame's device time, overlaps the caller's next step)
-            SPT_HIP(c, spt_pool_chunk_order(P.chunk_clock, nchunks, (uint32_t)ntasks, c->d_chunk_tables, c->d_chunk_tables + 3 * c->chunk_cap, st));
-            SPT_HIP(c, hipEventRecord(c->ev_order, st));
-            c->order_pending = true;
-            c->order_key = key;
-            c->order_valid = true;
-            c->last_nchunks = nchunks;
-        } else {
-            c->last_nchunks = 0;
-        }
-        c->last_pool_key.swap(key);
-        c->pending = true;
-        c->last_was_pool = true;
-        c->last_kernel = 1;
-        c->last = spt_stats{};
-        c->last.samples = npix * 4ull * samps;
-        c->last.grid_blocks = (uint32_t)blocks;
-        c->last.block_threads = 256;
-        return 0;
-    }
-    c->last_was_pool = false;
-    c->last_kernel = 0;
-
-    // launch geometry: a persistent grid that fills the chip; the task queue makes any size correct
-    const int mat_lds = (c->n <= 256) ? 1 : 0;
-    const int big_block = (c->variant & 0x200u) ? 512 : 256;   // A/B on the box: 256 is faster once the LDS reads are prefetched
-    const size_t lds = spt_k_lds_bytes(P.n_pad, mat_lds, big_block);
-    const int threads = spt_k_block_threads_for(mat_lds, big_block);
-    uint32_t per_cu = c->blocks_per_cu;
-    if (per_cu == 0) {
-        const uint32_t by_lds = (uint32_t)((160u * 1024u) / lds);
-        per_cu = by_lds < 1 ? 1 : (by_lds > 8 ? 8 : by_lds);
-    }
-    uint64_t blocks = (uint64_t)c->cu_count * per_cu;
-    const uint64_t needed = (ntasks + threads - 1) / threads;
-    if (blocks > needed) blocks = needed;
-    if (blocks < 1) blocks = 1;
-
-    {
-        const size_t need_stack = spt_k_stack_floats((uint32_t)blocks, threads);
-        if (need_stack > c->stack_cap) {
-            if (c->d_stack) (void)hipFree(c->d_stack);
-            c->d_stack = nullptr; c->stack_cap = 0;
-            SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_stack), need_stack * sizeof(float)));
-            c->stack_cap = need_stack;
-        }
-        P.stack = c->d_stack;
-    }
-    SPT_HIP(c, hipMemsetAsync(c->d_queue, 0, 256, st));
-    SPT_HIP(c, hipEventRecord(c->ev_start, st));
-    SPT_HIP(c, spt_k_launch(&P, (uint32_t)blocks, mat_lds, (c->needs_guard || !(cam_big <= 1e15f)) ? 1 : 0, (c->variant & 0x100u) ? 1 : 0, 1, big_block, st, radiance));
-    SPT_HIP(c, hipEventRecord(c->ev_mid, st));
-    SPT_HIP(c, spt_k_finalize(c->d_cells, static_cast<float*>(d_out_rgb), (uint32_t)npix, scale, (flags & SPT_FLAG_NORMALISE) ? 1 : 0, nb, st));
-    SPT_HIP(c, hipEventRecord(c->ev_stop, st));
-    c->pending = true;
-    c->last = spt_stats{};
-    c->last.samples = npix * 4ull * samps;
-    c->last.grid_blocks = (uint32_t)blocks;
-    c->last.block_threads = (uint32_t)threads;
-    return 0;
+    return c->fail("spt_render_rows_device: no kernel for this scene");   // (not reached: every RenderKernel is handled above)
 }
 
 int spt_sync(spt_ctx* c, spt_stats* stats)
@@ -1989,17 +1998,25 @@ int spt_sync(spt_ctx* c, spt_stats* stats)
         c->last.kernel_ms = ms;
         c->last.bounces = ctr[0];
         c->last.max_depth_kills = ctr[1];
-        if (c->mesh_scene && (c->last_kernel == 2 || c->last_kernel == 6 || c->last_kernel == 7 || c->last_kernel == 8) && c->last.samples)
+        if (c->mesh_scene && is_mesh_kernel(c->last_kernel) && c->last.samples)
             c->mesh_ratio = (float)((double)c->last.bounces / (double)c->last.samples);
-        if (c->variant & 0x100u) SPT_HIP(c, hipMemcpy(c->diag, c->d_counters + 2, sizeof c->diag, hipMemcpyDeviceToHost));
+        if (c->variant & kTuneStats) SPT_HIP(c, hipMemcpy(c->diag, c->d_counters + 2, sizeof c->diag, hipMemcpyDeviceToHost));
         c->pending = false;
-        if (c->last_was_pool || c->last_kernel == 4 || c->last_kernel == 5) {
+        if (c->last_kernel == kPool || is_grid_kernel(c->last_kernel)) {
             SPT_HIP(c, hipMemcpy(c->pool_stats, c->d_counters + 2, sizeof c->pool_stats, hipMemcpyDeviceToHost));
             if (c->pool_stats[6] != 0)
                 return c->fail("spt_sync: %llu waves hit the kernel watchdog; the image is incomplete", c->pool_stats[6]);
         }
     }
     if (stats) *stats = c->last;
+    return 0;
+}
+
+// The staging image of the host-buffer renders; a pending launch may still write the old one.
+static int grow_out(spt_ctx* c, size_t nfl)
+{
+    if (nfl > c->out_cap && c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+    SPT_HIP(c, grow(c->d_out, c->out_cap, nfl));
     return 0;
 }
 
@@ -2012,13 +2029,7 @@ int spt_render(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t nfl = (size_t)w * h * 3;
     if (nfl == 0) return c->fail("spt_render: empty image");
-    if (nfl > c->out_cap) {
-        if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), nfl * sizeof(float)));
-        c->out_cap = nfl;
-    }
+    if (grow_out(c, nfl)) return 1;
     if (int rc = spt_render_rows_device(c, cam, w, h, 0, h, samps, seed, flags, c->d_out, nullptr)) return rc;
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
@@ -2051,8 +2062,7 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
     if ((uint64_t)w * h > 0xFFFFFFFFull) return c->fail("%s: w*h exceeds 2^32-1 pixels", who);
     if ((uint64_t)samps * 4 > 0xFFFFFFFFull) return c->fail("%s: spp overflows 32 bits", who);
     if (cam->sampler > SPT_SAMPLER_PINHOLE) return c->fail("%s: unknown camera sampler %u", who, cam->sampler);
-    const uint32_t nb_log2 = samps >= 128u ? 3u : (samps >= 64u ? 2u : (samps >= 32u ? 1u : 0u));   // D9, as spt_render
-    const uint32_t nb = 1u << nb_log2;
+    const uint32_t nb = 1u << sample_blocks_log2(samps);
     const uint64_t npix = (uint64_t)row_count * w;
     const uint64_t qend = (uint64_t)((w + 7u) >> 3) * ((row_count + 7u) >> 3) * 64u * 4u * nb;     // spt_deal.h deal_tiles_end
     if (npix * 4 * nb > 0xF0000000ull || qend > 0xFFFFFFFFull) return c->fail("%s: band has too many sample blocks (%u per pixel); split it", who, 4u * nb);
@@ -2062,29 +2072,10 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
         else SPT_HIP(c, hipEventSynchronize(c->ev_stop));
     }
     const size_t ntasks = (size_t)npix * 4 * nb;
-    if (ntasks * nplanes > c->cells_cap) {
-        if (c->d_cells) (void)hipFree(c->d_cells);
-        c->d_cells = nullptr; c->cells_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_cells), ntasks * nplanes * sizeof(float4)));
-        c->cells_cap = ntasks * nplanes;
-    }
+    SPT_HIP(c, grow(c->d_cells, c->cells_cap, ntasks * nplanes));
     if (set) aov |= spt_aov_set;
     spt::KParams P{};
-    std::memcpy(P.cam_o, cam->origin, 12); std::memcpy(P.cam_d, cam->dir, 12);
-    std::memcpy(P.cam_cx, cam->cx, 12); std::memcpy(P.cam_cy, cam->cy, 12);
-    P.cam_push = cam->push;
-    P.sampler = cam->sampler;
-    P.inv_wf = 1.f / (float)w; P.inv_hf = 1.f / (float)h;
-    P.w = w; P.h = h; P.row_begin = row_begin; P.row_count = row_count;
-    P.rb_log2 = 0u; P.rb_stride = 1u; P.rb_mask = 0u;
-    P.inv_w = 1.0 / (double)w; P.inv_h = 1.0 / (double)h;
-    P.samps = samps; P.ntasks = (uint32_t)ntasks;
-    P.nb_log2 = nb_log2; P.sb = (samps + nb - 1u) / nb;
-    P.s0 = mix32((uint32_t)seed + 0x243F6A88u);
-    P.s1 = mix32((uint32_t)(seed >> 32) ^ P.s0 ^ 0x85A308D3u);
-    P.n = c->mesh_scene ? 0u : c->n; P.n_pad = P.n ? P.n : 1u;
-    P.geom = c->mesh_scene ? nullptr : c->d_geom; P.mat = c->mesh_scene ? nullptr : c->d_mat;
-    P.cells = c->d_cells;
+    fill_kparams(c, cam, w, h, row_begin, row_count, samps, seed, P);
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     uint32_t blocks = 0, threads = 256;
     spt::MParams M{};
@@ -2096,14 +2087,11 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
         if (M.plane_nodes && camera_plane_list(c, cam, st, M)) return 1;
     } else if (c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready) {
         path = 1;
-        const size_t lds = c->grid_global == 1 ? 0 : (c->grid_global == 2 ? spt_grid_lds_bytes_tables(&c->grid) : spt_grid_lds_bytes(&c->grid));
-        const uint32_t per_cu = lds == 0 ? 2u : (lds * 2 <= (size_t)160 * 1024 ? 2u : 1u);   // 1024-thread workgroups, 160 KB of LDS per CU
-        blocks = (uint32_t)(c->cu_count > 0 ? c->cu_count : 1) * per_cu;
+        blocks = grid_query_blocks(c);
         threads = (uint32_t)spt_grid_block_threads();
     } else if (c->sphere_accel != SPT_ACCEL_EXHAUSTIVE && c->sbvh_ready && !c->needs_guard) {
         path = 2;
-        M.bvh_nodes = c->d_sbvh_nodes; M.bvh_tris = c->d_sbvh_geom; M.bvh_index = c->d_sbvh_index;
-        M.always = c->d_sbvh_always; M.nalways = c->sbvh_nalways; M.sphere_mode = 1u;
+        M = sphere_bvh_params(c);
     } else if (c->n > SPT_MAX_SPHERES) {
         return c->fail("%s: %u spheres > SPT_MAX_SPHERES (%u) and no structure over them", who, c->n, SPT_MAX_SPHERES);
     }
@@ -2144,13 +2132,7 @@ int spt_render_aov(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, ui
     const auto t0 = std::chrono::steady_clock::now();
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t nfl = (size_t)w * h * 3;
-    if (nfl > c->out_cap) {
-        if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), nfl * sizeof(float)));
-        c->out_cap = nfl;
-    }
+    if (grow_out(c, nfl)) return 1;
     void* const d_out = c->d_out;
     if (int rc = render_aov_impl(c, "spt_render_aov", cam, w, h, 0, h, samps, seed, false, aov, flags, &d_out, nullptr)) return rc;
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -2181,13 +2163,7 @@ int spt_render_aov_set(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h
     const auto t0 = std::chrono::steady_clock::now();
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t nfl = (size_t)w * h * 3, pitch = (nfl + 3) & ~(size_t)3;       // every plane of the staging buffer 16-byte aligned
-    if (pitch * nplanes > c->out_cap) {
-        if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr; c->out_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), pitch * nplanes * sizeof(float)));
-        c->out_cap = pitch * nplanes;
-    }
+    if (grow_out(c, pitch * nplanes)) return 1;
     void* d_out[6];
     for (uint32_t j = 0; j < nplanes; ++j) d_out[j] = c->d_out + j * pitch;
     if (int rc = render_aov_impl(c, "spt_render_aov_set", cam, w, h, 0, h, samps, seed, true, mask, flags, d_out, nullptr)) return rc;
@@ -2391,7 +2367,7 @@ int spt_chunk_order_snapshot(spt_ctx* c, uint32_t* order, uint32_t cap, uint32_t
 {
     if (!c || !nchunks) return 1;
     *nchunks = 0;
-    if (!c->order_valid || !c->last_was_pool || c->last_nchunks == 0) return 0;
+    if (!c->order_valid || c->last_kernel != kPool || c->last_nchunks == 0) return 0;
     if (!order || cap < c->last_nchunks) return c->fail("spt_chunk_order_snapshot: room for %u words, the order has %u", cap, c->last_nchunks);
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->order_pending) SPT_HIP(c, hipEventSynchronize(c->ev_order));
@@ -2404,9 +2380,9 @@ int spt_chunk_order_snapshot(spt_ctx* c, uint32_t* order, uint32_t cap, uint32_t
 int spt_diag(spt_ctx* c, unsigned long long* out24)
 {
     if (!c || !out24) return 1;
-    if (c->last_was_pool || c->last_kernel == 4 || c->last_kernel == 5) {
+    if (c->last_kernel == kPool || is_grid_kernel(c->last_kernel)) {
         std::memcpy(out24, c->pool_stats, sizeof c->pool_stats);
-        if (c->last_was_pool) out24[23] = (unsigned long long)c->last_share;
+        if (c->last_kernel == kPool) out24[23] = (unsigned long long)c->last_share;
         return 0;
     }
     std::memcpy(out24, c->diag, sizeof c->diag);

@@ -12,22 +12,37 @@
 extern "C" {
 #endif
 
-/* Tuning knobs (0 = default).  blocks_per_cu caps the persistent grid; variant bits 0..7 = number of
- * waiting lanes that triggers a wave's glass-shading pass (0 = default 8), bit 8 = instrumented kernel
- * build (see spt_diag), bit 9 = 512-thread workgroups for tables above 256 spheres, bit 10 = force the megakernel where the pool kernel
- * would run (and the grid kernel), bits 12:11 = pool slots per wave (0: 160, 3: 128; 1: 96 and 2: 192 in -DSPT_POOL_SIZES builds), bits 23:16 = grid kernel:
- * 1 + q, a wave leaves its walk phase when 16 x walking lanes < q x waiting lanes (0 = default q = 16), bits 31:24 = grid cells per sphere
- * (read by spt_set_scene; 0 = default 4).  Results never depend on these. */
+/* Tuning knobs (0 = default).  blocks_per_cu caps the persistent grid; variant bits 0..7 (kTuneParkMask) = number of
+ * waiting lanes that triggers a wave's glass-shading pass (0 = default 8), bit 8 (kTuneStats) = instrumented kernel
+ * build (see spt_diag), bit 9 (kTuneBigBlock) = 512-thread workgroups for tables above 256 spheres, bit 10 (kTuneForceMega) = force the megakernel
+ * where the pool kernel would run (and the grid kernel), bits 12:11 (kTunePoolSize*) = pool slots per wave (0: 160, 3: 128; 1: 96 and 2: 192 in
+ * -DSPT_POOL_SIZES builds), bits 23:16 (kTuneGridLeave*) = grid kernel: 1 + q, a wave leaves its walk phase when 16 x walking lanes < q x waiting
+ * lanes (0 = default q = 16), bits 31:24 (kTuneGridCells*) = grid cells per sphere (read by spt_set_scene; 0 = default 4).  Results never depend on these. */
 int  spt_set_tuning(spt_ctx* ctx, uint32_t blocks_per_cu, uint32_t variant);
+enum {
+    kTuneParkMask = 0xFFu,
+    kTuneStats = 0x100u,
+    kTuneBigBlock = 0x200u,
+    kTuneForceMega = 0x400u,
+    kTunePoolSizeShift = 11, kTunePoolSizeMask = 3u,
+    /* Bits 15:13 mean two things: the grid kernels read them as ONE FIELD, their workgroup size (threads / 128 - 1; 0 = 1024); the pool kernel
+     * reads them as THREE SWITCHES (below).  A launch runs one kernel or the other, so the two readings never meet. */
+    kTuneGridThreadsShift = 13, kTuneGridThreadsMask = 7u,
+    kTuneStaticOrder = 0x2000u,
+    kTuneGenericHit = 0x4000u,
+    kTuneOldLoop = 0x8000u,
+    kTuneGridLeaveShift = 16, kTuneGridLeaveMask = 0xFFu,
+    kTuneGridCellsShift = 24, kTuneGridCellsMask = 0xFFu
+};
 /* Large sphere tables through the uniform grid: lane_owned = 1 keeps the kernel whose lanes own their path (spt_grid.hip) where the
  * default -- wave-private path pools with walker lanes, spt_gpool.hip -- would run; slots / ready / drain / min_batch / walk_iters set
  * the pool geometry (0 = default 192 slots per wave, up to 96 begun walks per wave in LDS, an exchange per 24 finished walker lanes,
  * batches of >= 32 while the walkers starve, 4 walk iterations behind a batch's loads).  Results never depend on these. */
 int  spt_set_grid_pools(spt_ctx* ctx, int lane_owned, uint32_t slots, uint32_t ready, uint32_t drain, uint32_t min_batch, uint32_t walk_iters);
-/* Pool kernel: bit 13 = hand the task chunks out in their static order (no cost-ordered dispatch, spt_kernel.h KParams::chunk_order; the
- * grid kernel reads bits 15:13 as its workgroup size).  Bit 14 = the generic closest hit: no sharing pattern (csrc/spt_share.h) even
- * where the table matches one (A/B; the grid kernel reads it as part of bits 15:13).  Bit 15 = the bounce loop's bookkeeping as it was
- * before it was trimmed -- batch statistics counted per iteration in registers, the push's lane masks from an integer class, the image row
+/* Pool kernel: bit 13 (kTuneStaticOrder) = hand the task chunks out in their static order (no cost-ordered dispatch, spt_kernel.h
+ * KParams::chunk_order; the grid kernel reads bits 15:13 as its workgroup size).  Bit 14 (kTuneGenericHit) = the generic closest hit: no sharing
+ * pattern (csrc/spt_share.h) even where the table matches one (A/B; the grid kernel reads it as part of bits 15:13).  Bit 15 (kTuneOldLoop) = the
+ * bounce loop's bookkeeping as it was before it was trimmed -- batch statistics counted per iteration in registers, the push's lane masks from an integer class, the image row
  * by an integer division -- for the default pool size (A/B; the other sizes run the trimmed loop only; the grid kernel reads it as part of bits 15:13). */
 /* Pool kernel, cost-ordered dispatch: copies the chunk order that the last pool launch left for the next launch of the same view
  * (a permutation of 0 .. nchunks - 1, most expensive chunk first) to `order` (room for `cap` words).  *nchunks = 0 when that
@@ -49,6 +64,10 @@ int  spt_set_watchdog(spt_ctx* ctx, double seconds);
  * After a pool launch spt_diag returns out24[0..2] = batches per class (GEN, DIFF, REFR), [3..5] = lanes per class, [23] = the sharing
  * pattern its closest hit ran (csrc/spt_share.h: 0 = generic, 1 = box prefix, 2 = Cornell-9). */
 int  spt_last_kernel(spt_ctx* ctx);
+enum RenderKernel {
+    kRefused = -1,            /* (never reported: the route choice found no kernel that takes the table) */
+    kMega = 0, kPool = 1, kMesh = 2, kSphereBvh = 3, kGrid = 4, kGridPools = 5, kMeshBvh = 6, kMeshBvhFast = 7, kMeshInst = 8
+};
 /* Where the grid kernels of the current sphere scene read their tables (spt_grid.hip WHERE): 0 = sphere records, cell headers and references
  * staged in LDS, 1 = everything from global memory, 2 = the records from global memory and the grid tables staged in LDS; -1 = the current
  * scene has no grid (a mesh scene, or a table the grid refuses).  Chosen by spt_set_scene; spt_set_grid_pools' lane_owned = 2 / 3 forces
