@@ -482,6 +482,65 @@ int  spt_progressive_end(spt_ctx* ctx);
 int  spt_progressive_aov_begin(spt_ctx* ctx, uint32_t mask);
 int  spt_progressive_aov_frame(spt_ctx* ctx, const spt_camera* cam, uint32_t samps_per_cell, uint64_t seed, int clear, spt_stats* stats);
 int  spt_progressive_aov_snapshot(spt_ctx* ctx, uint32_t kind_bit, float* out_rgb);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over the feature buffers: what takes the buffers above.  It
+ * turns a few-spp image into a usable picture on the device, guided by the first-hit normal, albedo, position and hit count.
+ *   Images: every image is w*h packed float3, row 0 = bottom.  The inputs are UN-NORMALISED SUMS: `beauty` as spt_render_rows_device
+ *     writes it without SPT_FLAG_NORMALISE (or as the radiance accumBuffer holds it); normal, albedo, position and coverage as
+ *     spt_render_aov_set_rows_device writes SPT_AOVSET_NORMAL / _ALBEDO / _POSITION / _COVERAGE without SPT_FLAG_NORMALISE (or as the
+ *     feature accumulators hold them).  aov_samples = samples per pixel summed into the guides: 4 * samps for one launch,
+ *     frames * 4 * samps for the progressive loop.  The output is the filtered un-normalised sum: the filter is linear in the colour, so
+ *     the caller's display weight 1 / (frames * spp) applies unchanged.  The output may not alias an input.
+ *   Arithmetic: float32, one rounding per operation, no contraction, correctly rounded division.  Pinned bit for bit by
+ *     tests/denoise_expected.py (numpy) and tests/test_gpu_denoise.py.
+ *   Guides of a pixel, from the sums N, A, P and c = coverage channel 0:
+ *     c > 0:      n = N / c, a = A / c, x = P / c, component by component, one division each;
+ *     otherwise:  n = a = x = 0 (the N / A / P sums of such a pixel are not read into the result);
+ *     k = c / (float)aov_samples.
+ *   Weight of tap q for centre p; hx, hy from the B3 row (1/16, 1/4, 3/8, 1/4, 1/16), whose values and products are exact in binary:
+ *     dn = n_p - n_q;   en = (dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z
+ *     da = a_p - a_q;   ea likewise
+ *     dx = x_q - x_p;   pl = (n_p.x*dx.x + n_p.y*dx.y) + n_p.z*dx.z;   ep = pl*pl
+ *     dk = k_p - k_q;   ek = dk*dk
+ *     D  = 1.0f + (((sigma_normal*en + sigma_plane*ep) + sigma_albedo*ea) + sigma_coverage*ek)
+ *     wt = (hy*hx) / D
+ *     The falloff is rational on purpose: no exp, nothing that needs an exact-math proof.  The centre tap takes the same formula
+ *     (D = 1).  The distance to the centre's tangent PLANE is used, not the distance between the points, so a floor seen at a
+ *     grazing angle still filters along itself.  A pixel without hits has all-zero guides and k = 0: it mixes with other background
+ *     pixels and sigma_coverage cuts it off from hit pixels.
+ *   Pass i = 0 .. levels - 1, step s = 2^i: for pixel p, dy = -2 .. 2 in the outer loop, dx = -2 .. 2 in the inner loop,
+ *     q = p + s * (dx, dy); taps outside the image are skipped.  Starting from 0.0f: num_j += wt * colour_q[j] for j = 0, 1, 2, then
+ *     den += wt.  out_j = num_j / den (the centre tap keeps den >= 9/64).  Pass 0 reads beauty, pass i the output of pass i - 1; the
+ *     guides are the same in every pass.
+ *   Failures (message in spt_last_error, nothing written, nothing launched): levels outside 1..5; a strength that is negative or not
+ *     finite; aov_samples == 0; w or h of 0 (or w*h above 2^31 - 1); a NULL pointer; a device pointer that is not 4-byte aligned -- the
+ *     kernels need no 16-byte alignment of the caller's buffers --; d_out equal to an input.  Non-finite pixel values are outside the contract.
+ *   Scratch (the packed guides and two colour images, 80 bytes per pixel) belongs to the context, is grown on demand and freed by
+ *     spt_destroy and spt_progressive_end; a failed allocation fails the call and leaves the context usable.  Calls of one context run
+ *     one after another, whatever their streams (they share the scratch).  A call changes no render state.
+ *   Out of scope: albedo demodulation; variance-guided colour edge stopping (the library has no second-moment buffer); temporal
+ *     reprojection; the multi-GPU front; the async lanes (they stay radiance-only). */
+typedef struct spt_denoise_params {
+    uint32_t levels;      /* 1..5 passes; pass i uses step 2^i pixels */
+    float sigma_normal, sigma_plane, sigma_albedo, sigma_coverage;  /* each finite and >= 0 */
+} spt_denoise_params;
+/* Host-only: 5 levels, sigma_normal = 32, sigma_plane = 0.2, sigma_albedo = 64, sigma_coverage = 16.  sigma_plane is in
+ * 1 / (scene length)^2: the default suits the Cornell box's scale of about 100; a caller with a scene of another size scales it. */
+void spt_denoise_params_default(spt_denoise_params* params);
+/* DEVICE buffers of this context's device, enqueued on `hip_stream` (NULL = the context's stream); returns without waiting. */
+int  spt_denoise_device(spt_ctx* ctx, const void* d_beauty, const void* d_normal, const void* d_albedo, const void* d_position,
+                        const void* d_coverage, uint32_t w, uint32_t h, uint32_t aov_samples,
+                        const spt_denoise_params* params, void* d_out, void* hip_stream);
+/* Host buffers, blocking. */
+int  spt_denoise(spt_ctx* ctx, const float* beauty, const float* normal, const float* albedo, const float* position,
+                 const float* coverage, uint32_t w, uint32_t h, uint32_t aov_samples,
+                 const spt_denoise_params* params, float* out);
+/* The filter as a snapshot of the progressive loop: requires spt_progressive_aov_begin with at least NORMAL | ALBEDO | POSITION |
+ * COVERAGE selected (else it fails and names the missing kinds).  Like spt_progressive_snapshot it waits for every accumulation issued
+ * so far; it filters the radiance accumBuffer under the feature accumulators and copies the result to host memory in
+ * spt_progressive_snapshot's layout.  It modifies neither accumulator nor the render state (chunk-order records, spt_last_kernel,
+ * SPT_ACCEL_AUTO's bounce share).  The result is, bit for bit, spt_denoise applied to the five snapshots. */
+int  spt_progressive_denoised_snapshot(spt_ctx* owner, uint32_t aov_samples, const spt_denoise_params* params, float* out_rgb);
 /* The same loop with SEVERAL FRAMES IN FLIGHT.  The reference overlaps its render thread with the GL thread (smallpt.cpp:895-962);
  * on the GPU the end of a 4-spp frame is a handful of long specular chains that leave most of the chip idle, so a host that
  * issues frame k+1 before frame k has drained keeps it busy.  A context renders one frame at a time (its scratch buffers belong

@@ -36,6 +36,11 @@ class SptMaterial(C.Structure):      # Material, scene.h:66-73
     _fields_ = [("emission", C.c_float * 3), ("color", C.c_float * 3), ("refl", C.c_int32), ("pad", C.c_uint32)]
 
 
+class SptDenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_coverage", C.c_float)]
+
+
 class SptInstance(C.Structure):      # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
     _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
 
@@ -93,6 +98,10 @@ SYMBOLS = {
     "spt_progressive_aov_begin": (C.c_int, [_P, C.c_uint32]),
     "spt_progressive_aov_frame": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int, C.POINTER(SptStats)]),
     "spt_progressive_aov_snapshot": (C.c_int, [_P, C.c_uint32, _P]),
+    "spt_denoise_params_default": (None, [C.POINTER(SptDenoiseParams)]),
+    "spt_denoise_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseParams), _P, _P]),
+    "spt_denoise": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseParams), _P]),
+    "spt_progressive_denoised_snapshot": (C.c_int, [_P, C.c_uint32, C.POINTER(SptDenoiseParams), _P]),
     "spt_progressive_attach": (C.c_int, [_P, _P]),
     "spt_progressive_frame_async": (C.c_int, [_P, _P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int]),
     "spt_progressive_wait": (C.c_int, [_P, C.POINTER(SptStats)]),
@@ -124,6 +133,9 @@ INTERNAL_SYMBOLS = {
     "spt_last_query_path": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "spt_selftest_query_route": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P]),
     "spt_chunk_order_snapshot": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "spt_set_denoise_form": (C.c_int, [_P, C.c_int]),
+    "spt_set_denoise_timing": (C.c_int, [_P, C.c_int]),
+    "spt_denoise_last_ms": (C.c_int, [_P, C.POINTER(C.c_float * 6)]),
 }
 
 class SptMultiStats(C.Structure):

@@ -9,6 +9,7 @@
 #include "spt_query.h"
 #include "spt_aov.h"
 #include "spt_instance.h"
+#include "spt_denoise.h"
 
 #include <chrono>
 #include <cmath>
@@ -123,6 +124,16 @@ struct spt_ctx {
     uint32_t prog_w = 0, prog_h = 0;
     uint32_t aov_mask = 0;         // spt_progressive_aov_*: the selected kinds; per kind an accumulation buffer and a frame, w*h*3 floats each
     float* d_aov_accum[6] = {}; float* d_aov_frame[6] = {};
+    // spt_denoise*: packed guides (3 planes of float4), two float4 colour images (ping-pong) and the float3 result of the progressive
+    // snapshot, grown on demand; calls of one context run one after another, whatever their streams (they share these)
+    float4* d_dn_guides = nullptr; size_t dn_guides_cap = 0;
+    float4* d_dn_ping = nullptr; size_t dn_ping_cap = 0;
+    float4* d_dn_pong = nullptr; size_t dn_pong_cap = 0;
+    float* d_dn_out = nullptr; size_t dn_out_cap = 0;
+    hipEvent_t ev_denoise = nullptr; bool denoise_recorded = false;
+    int denoise_form = 0;          // spt_set_denoise_form (spt_internal.h): 1 = the direct-load pass at every step
+    bool denoise_timed = false;    // spt_set_denoise_timing: events around every kernel of a filter call (spt_denoise_last_ms)
+    hipEvent_t dn_ev[7] = {}; uint32_t dn_ev_count = 0;
     hipEvent_t ev_acc = nullptr;   // owner of an accumBuffer: completion of the most recent accumulation (any lane's stream)
     bool acc_recorded = false;
     bool frame_in_flight = false;  // a spt_progressive_frame_async of this lane has not been waited for
@@ -248,6 +259,16 @@ int spt_create(int device_id, spt_ctx** out)
     return 0;
 }
 
+static void denoise_free(spt_ctx* c)
+{
+    if (c->d_dn_guides) (void)hipFree(c->d_dn_guides);
+    if (c->d_dn_ping) (void)hipFree(c->d_dn_ping);
+    if (c->d_dn_pong) (void)hipFree(c->d_dn_pong);
+    if (c->d_dn_out) (void)hipFree(c->d_dn_out);
+    c->d_dn_guides = c->d_dn_ping = c->d_dn_pong = nullptr; c->d_dn_out = nullptr;
+    c->dn_guides_cap = c->dn_ping_cap = c->dn_pong_cap = c->dn_out_cap = 0;
+}
+
 static void progressive_aov_free(spt_ctx* c)
 {
     for (int k = 0; k < 6; ++k) {
@@ -272,6 +293,9 @@ void spt_destroy(spt_ctx* c)
     if (c->d_accum) (void)hipFree(c->d_accum);
     if (c->d_frame) (void)hipFree(c->d_frame);
     progressive_aov_free(c);
+    denoise_free(c);
+    if (c->ev_denoise) (void)hipEventDestroy(c->ev_denoise);
+    for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
     if (c->d_tris) (void)hipFree(c->d_tris);
     if (c->d_tri_index) (void)hipFree(c->d_tri_index);
     if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
@@ -2202,6 +2226,9 @@ int spt_progressive_end(spt_ctx* c)
     if (c->d_frame) (void)hipFree(c->d_frame);
     c->d_accum = c->d_frame = nullptr;
     progressive_aov_free(c);
+    if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));   // a filter a caller's stream still runs
+    c->denoise_recorded = false;
+    denoise_free(c);
     c->prog_w = c->prog_h = 0;
     c->acc_recorded = false;
     c->frame_in_flight = false;
@@ -2359,6 +2386,159 @@ int spt_progressive_aov_snapshot(spt_ctx* c, uint32_t kind_bit, float* out_rgb)
     const int k = __builtin_ctz(kind_bit);
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_aov_accum[k], (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- edge-avoiding wavelet filter over the feature buffers (spt_denoise.hip; the arithmetic is stated in include/smallpt_mi355x.h) ----
+void spt_denoise_params_default(spt_denoise_params* p)
+{
+    if (!p) return;
+    p->levels = 5;
+    p->sigma_normal = 32.0f;
+    p->sigma_plane = 0.2f;
+    p->sigma_albedo = 64.0f;
+    p->sigma_coverage = 16.0f;
+}
+
+static int denoise_check(spt_ctx* c, const char* who, uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_params* p)
+{
+    if (!p) return c->fail("%s: NULL argument", who);
+    if (w == 0 || h == 0) return c->fail("%s: empty image", who);
+    if ((uint64_t)w * h > 0x7FFFFFFFull) return c->fail("%s: w*h exceeds 2^31-1 pixels", who);
+    if (aov_samples == 0) return c->fail("%s: aov_samples == 0", who);
+    if (p->levels < 1 || p->levels > 5) return c->fail("%s: levels = %u outside 1..5", who, p->levels);
+    const float s[4] = {p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage};
+    static const char* const names[4] = {"sigma_normal", "sigma_plane", "sigma_albedo", "sigma_coverage"};
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(s[i]) || s[i] < 0.f) return c->fail("%s: %s = %g is negative or not finite", who, names[i], (double)s[i]);
+    return 0;
+}
+
+// Validated arguments, device set.  Enqueues the guide pack and the passes on st behind the context's previous filter.
+static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, const float* normal, const float* albedo, const float* position,
+                           const float* coverage, uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_params* p, float* out,
+                           hipStream_t st)
+{
+    const size_t npix = (size_t)w * h;
+    if (npix > c->dn_guides_cap || npix > c->dn_ping_cap || npix > c->dn_pong_cap) {
+        if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));   // the previous filter may still read the old scratch
+        hipError_t e = grow(c->d_dn_guides, c->dn_guides_cap, npix, 3 * npix);
+        if (e == hipSuccess) e = grow(c->d_dn_ping, c->dn_ping_cap, npix);
+        if (e == hipSuccess) e = grow(c->d_dn_pong, c->dn_pong_cap, npix);
+        if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: scratch for %u x %u pixels: %s", who, w, h, hipGetErrorString(e)); }
+    }
+    if (!c->ev_denoise) SPT_HIP(c, hipEventCreateWithFlags(&c->ev_denoise, hipEventDisableTiming));
+    if (c->denoise_recorded) SPT_HIP(c, hipStreamWaitEvent(st, c->ev_denoise, 0));
+    const bool timed = c->denoise_timed;
+    c->dn_ev_count = 0;
+    if (timed) {
+        for (hipEvent_t& e : c->dn_ev) if (!e) SPT_HIP(c, hipEventCreate(&e));
+        SPT_HIP(c, hipEventRecord(c->dn_ev[0], st));
+    }
+    SPT_HIP(c, spt_denoise_pack_launch(beauty, normal, albedo, position, coverage, (uint32_t)npix, (float)aov_samples, c->d_dn_ping, c->d_dn_guides, st));
+    const float sigma[4] = {p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage};
+    if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[1], st));
+    float4* src = c->d_dn_ping;
+    float4* dst = c->d_dn_pong;
+    for (uint32_t i = 0; i < p->levels; ++i) {
+        const bool last = i + 1 == p->levels;
+        SPT_HIP(c, spt_denoise_pass_launch(src, c->d_dn_guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
+        if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[2 + i], st));
+        std::swap(src, dst);
+    }
+    if (timed) c->dn_ev_count = 2 + p->levels;
+    SPT_HIP(c, hipEventRecord(c->ev_denoise, st));
+    c->denoise_recorded = true;
+    return 0;
+}
+
+int spt_denoise_device(spt_ctx* c, const void* d_beauty, const void* d_normal, const void* d_albedo, const void* d_position, const void* d_coverage,
+                       uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_params* p, void* d_out, void* hip_stream)
+{
+    if (!c) return 1;
+    if (!d_beauty || !d_normal || !d_albedo || !d_position || !d_coverage || !d_out) return c->fail("spt_denoise_device: NULL argument");
+    if (int rc = denoise_check(c, "spt_denoise_device", w, h, aov_samples, p)) return rc;
+    const void* const ptrs[6] = {d_beauty, d_normal, d_albedo, d_position, d_coverage, d_out};
+    for (const void* q : ptrs)
+        if (reinterpret_cast<uintptr_t>(q) & 3u) return c->fail("spt_denoise_device: buffers must be 4-byte aligned");
+    for (int i = 0; i < 5; ++i)
+        if (ptrs[i] == d_out) return c->fail("spt_denoise_device: d_out aliases an input");
+    SPT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return denoise_enqueue(c, "spt_denoise_device", static_cast<const float*>(d_beauty), static_cast<const float*>(d_normal), static_cast<const float*>(d_albedo),
+                           static_cast<const float*>(d_position), static_cast<const float*>(d_coverage), w, h, aov_samples, p, static_cast<float*>(d_out), st);
+}
+
+int spt_denoise(spt_ctx* c, const float* beauty, const float* normal, const float* albedo, const float* position, const float* coverage,
+                uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_params* p, float* out)
+{
+    if (!c) return 1;
+    if (!beauty || !normal || !albedo || !position || !coverage || !out) return c->fail("spt_denoise: NULL argument");
+    if (int rc = denoise_check(c, "spt_denoise", w, h, aov_samples, p)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t nfl = (size_t)w * h * 3, pitch = (nfl + 3) & ~(size_t)3;
+    if (grow_out(c, pitch * 6)) return 1;
+    const float* const host[5] = {beauty, normal, albedo, position, coverage};
+    for (int j = 0; j < 5; ++j)
+        SPT_HIP(c, hipMemcpyAsync(c->d_out + j * pitch, host[j], nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float* const d = c->d_out;
+    if (int rc = denoise_enqueue(c, "spt_denoise", d, d + pitch, d + 2 * pitch, d + 3 * pitch, d + 4 * pitch, w, h, aov_samples, p, d + 5 * pitch, c->stream)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out, d + 5 * pitch, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int spt_progressive_denoised_snapshot(spt_ctx* c, uint32_t aov_samples, const spt_denoise_params* p, float* out_rgb)
+{
+    if (!c) return 1;
+    if (!c->d_accum || !out_rgb) return c->fail("spt_progressive_denoised_snapshot: no accumulation buffer or out_rgb is NULL");
+    const uint32_t need = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE, missing = need & ~c->aov_mask;
+    if (missing)
+        return c->fail("spt_progressive_denoised_snapshot: spt_progressive_aov_begin has not selected%s%s%s%s", (missing & SPT_AOVSET_NORMAL) ? " NORMAL" : "",
+                       (missing & SPT_AOVSET_ALBEDO) ? " ALBEDO" : "", (missing & SPT_AOVSET_POSITION) ? " POSITION" : "", (missing & SPT_AOVSET_COVERAGE) ? " COVERAGE" : "");
+    if (int rc = denoise_check(c, "spt_progressive_denoised_snapshot", c->prog_w, c->prog_h, aov_samples, p)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t nfl = (size_t)c->prog_w * c->prog_h * 3;
+    if (nfl > c->dn_out_cap) {
+        if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));
+        const hipError_t e = grow(c->d_dn_out, c->dn_out_cap, nfl);
+        if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("spt_progressive_denoised_snapshot: scratch: %s", hipGetErrorString(e)); }
+    }
+    if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
+    if (int rc = denoise_enqueue(c, "spt_progressive_denoised_snapshot", c->d_accum, c->d_aov_accum[SPT_AOV_NORMAL], c->d_aov_accum[SPT_AOV_ALBEDO],
+                                 c->d_aov_accum[4], c->d_aov_accum[5], c->prog_w, c->prog_h, aov_samples, p, c->d_dn_out, c->stream)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_dn_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Test / measurement hook (spt_internal.h)
+int spt_set_denoise_form(spt_ctx* c, int form)
+{
+    if (!c) return 1;
+    if (form != 0 && form != 1) return c->fail("spt_set_denoise_form: form %d (0 = tiles in LDS at steps 1 and 2, 1 = direct loads at every step)", form);
+    c->denoise_form = form;
+    return 0;
+}
+
+int spt_set_denoise_timing(spt_ctx* c, int on)
+{
+    if (!c) return 1;
+    c->denoise_timed = on != 0;
+    c->dn_ev_count = 0;
+    return 0;
+}
+
+int spt_denoise_last_ms(spt_ctx* c, float* ms6)
+{
+    if (!c || !ms6) return 1;
+    if (c->dn_ev_count < 2) return c->fail("spt_denoise_last_ms: no filter call has run under spt_set_denoise_timing(ctx, 1)");
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipEventSynchronize(c->dn_ev[c->dn_ev_count - 1]));
+    for (uint32_t i = 0; i < 6; ++i) {
+        ms6[i] = 0.f;
+        if (i + 1 < c->dn_ev_count) SPT_HIP(c, hipEventElapsedTime(&ms6[i], c->dn_ev[i], c->dn_ev[i + 1]));
+    }
     return 0;
 }
 

@@ -144,6 +144,15 @@ int  spt_last_query_path(spt_ctx* ctx, uint64_t* fallback_rays);
  * Returns 0, 2 = the grid does not take this table, 1 = builder error. */
 int  spt_selftest_query_route(const spt_sphere* spheres, uint32_t n, uint32_t structure, const spt_ray* rays, uint64_t nrays, uint32_t* route, float* t_ok);
 
+/* spt_denoise*: which form of the filter pass runs steps 1 and 2 -- 0 = the workgroup tile staged in LDS (the default), 1 = direct loads, the
+ * form steps 4, 8 and 16 always run.  Both run the same tap function: results never depend on it (tests compare them; tools/bench_denoise.py
+ * times them).  Any other value fails with a message. */
+int  spt_set_denoise_form(spt_ctx* ctx, int form);
+/* Measurement (tools/bench_denoise.py): on != 0 makes every later filter call of this context record a HIP event around each of its kernels;
+ * spt_denoise_last_ms waits for the last such call and returns ms6[0] = the guide pack, ms6[1 + i] = pass i (0 beyond its levels). */
+int  spt_set_denoise_timing(spt_ctx* ctx, int on);
+int  spt_denoise_last_ms(spt_ctx* ctx, float* ms6);
+
 /* libsmallpt_mi355x_multi.so: kernel watchdog (spt_set_watchdog) of ONE rank's context, so that a test can make exactly one
  * device's render fail and check that spt_multi_render returns its error instead of hanging in the exchange. */
 struct spt_multi;

@@ -72,6 +72,32 @@ public:
         return out;
     }
 
+    // Edge-avoiding wavelet filter over the feature buffers (spt_denoise): beauty and the four guides as UN-NORMALISED sums (render() and
+    // renderAovSet(..., SPT_AOVSET_NORMAL | _ALBEDO | _POSITION | _COVERAGE) with the same camera, samples and seed), aovSamples = samples
+    // per pixel summed into the guides; returns the filtered un-normalised sum.  params = nullptr: spt_denoise_params_default.
+    std::vector<float3> denoise(const std::vector<float3>& beauty, const std::vector<float3>& normal, const std::vector<float3>& albedo,
+                                const std::vector<float3>& position, const std::vector<float3>& coverage, size_t imageWidth, size_t imageHeight,
+                                size_t aovSamples, const spt_denoise_params* params = nullptr)
+    {
+        const size_t n = imageWidth * imageHeight;
+        if (beauty.size() != n || normal.size() != n || albedo.size() != n || position.size() != n || coverage.size() != n)
+            throw std::runtime_error("denoise: five images of imageWidth * imageHeight pixels");
+        spt_denoise_params p;
+        if (params) p = *params; else spt_denoise_params_default(&p);
+        std::vector<float3> out(n);
+        auto f = [](const std::vector<float3>& v) { return reinterpret_cast<const float*>(v.data()); };
+        check(spt_denoise(ctx_, f(beauty), f(normal), f(albedo), f(position), f(coverage), (uint32_t)imageWidth, (uint32_t)imageHeight,
+                          (uint32_t)aovSamples, &p, reinterpret_cast<float*>(out.data())));
+        return out;
+    }
+    // ... and as a snapshot of the progressive loop (spt_progressive_denoised_snapshot): accumBuffer filtered under the feature accumulators
+    void progressiveDenoisedSnapshot(size_t aovSamples, std::vector<float3>& image, const spt_denoise_params* params = nullptr)
+    {
+        spt_denoise_params p;
+        if (params) p = *params; else spt_denoise_params_default(&p);
+        check(spt_progressive_denoised_snapshot(ctx_, (uint32_t)aovSamples, &p, reinterpret_cast<float*>(image.data())));
+    }
+
     // accumBuffer of the viewer loop in HBM (spt_progressive_*, smallpt.cpp:881-883,922-937,955-959)
     void progressiveBegin(size_t w, size_t h) { check(spt_progressive_begin(ctx_, (uint32_t)w, (uint32_t)h)); }
     void progressiveFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool clear)

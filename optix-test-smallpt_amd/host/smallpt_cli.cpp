@@ -11,6 +11,9 @@
 //                                                              --single-triangle --aov normal: the reference program's own image (smallpt.cpp:179-183)
 //                  [--aov kind,kind,...]                          several buffers of the same samples from one launch (spt_render_aov_set):
 //                                                              --out img.ppm writes img.<kind>.ppm per kind
+//                  [--denoise [LEVELS]]                           radiance and the normal / albedo / position / coverage set of the same camera, samples
+//                                                              and seed, filtered by spt_denoise (default parameters, LEVELS = 1..5 passes);
+//                                                              --out gets the filtered image divided by spp
 //                  [--devices 0,1,...] [--self-exchange]      row bands over several GPUs + RCCL exchange (MultiRenderer)
 //                  [--env r,g,b] [--print-environment]         radiance of escaped paths (overrides the scene file's "environment"); print it
 //                                                              as loaded and overridden, then exit (host only)
@@ -51,6 +54,7 @@ int main(int argc, char* argv[])
     int aov = -1;                                  // --aov: SPT_AOV_* (-1: radiance)
     uint32_t aov_mask = 0;                         // --aov with a comma list, or position / coverage alone: SPT_AOVSET_* bits (spt_render_aov_set)
     bool aov_list = false;                         // a comma list: one file per kind (a kind alone is written to --out itself)
+    int denoise_levels = -1;                       // --denoise: 0 = the default level count, 1..5 = that many passes (-1: off)
     bool parse_only = false, viewer = false, threaded = false, self_exchange = false;
     int frames = 1, frames_after = 0;
     std::vector<int> devices;
@@ -97,6 +101,13 @@ int main(int argc, char* argv[])
             }
             if (!aov_list && aov < 4) aov_mask = 0;               // one of the four old kinds alone: spt_render_aov, as before
         }
+        else if (a == "--denoise") {
+            denoise_levels = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                denoise_levels = std::atoi(argv[++i]);
+                if (denoise_levels < 1 || denoise_levels > 5) { std::fprintf(stderr, "--denoise [1..5]\n"); return 2; }
+            }
+        }
         else if (a == "--single-triangle") single_triangle = true;   // SingleTriangleScene of main(), smallpt.cpp:818-832
         else if (a == "--viewer") viewer = true;
         else if (a == "--threaded") threaded = true;
@@ -142,6 +153,7 @@ int main(int argc, char* argv[])
         }
         const int samps = spp / 4 > 0 ? spp / 4 : 1;                               // :276
         if (aov >= 0 && viewer) throw std::runtime_error("--aov renders one offline image (no --viewer)");
+        if (denoise_levels >= 0 && (aov >= 0 || viewer || !devices.empty())) throw std::runtime_error("--denoise filters one offline radiance image on one device (no --aov, --viewer, --devices)");
         if (viewer) {
             // main() of the reference (smallpt.cpp:840-1005) without GLFW/GL: render thread + request queue + accumulation
             Renderer renderer(device);
@@ -233,9 +245,21 @@ int main(int argc, char* argv[])
         std::vector<std::vector<float3>> set;
         if (aov_mask) set = renderer.renderAovSet(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, aov_mask, /*normalise=*/true);
         std::vector<float3> c = aov_mask ? std::vector<float3>() : aov >= 0 ? renderer.renderAov(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, (uint32_t)aov, /*normalise=*/true)
-                                         : renderer.render(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, /*normalise=*/true);
+                                         : renderer.render(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, /*normalise=*/denoise_levels < 0);
+        const spt_stats radiance = renderer.stats();
+        if (denoise_levels >= 0) {
+            // beauty (above, un-normalised) and the guides of the same samples, filtered; the display weight 1 / spp applies to the filtered sum
+            const std::vector<std::vector<float3>> g = renderer.renderAovSet(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed,
+                                                                             SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE);
+            spt_denoise_params dp;
+            spt_denoise_params_default(&dp);
+            if (denoise_levels > 0) dp.levels = (uint32_t)denoise_levels;
+            c = renderer.denoise(c, g[0], g[1], g[2], g[3], (size_t)w, (size_t)h, (size_t)samps * 4, &dp);
+            const float inv = 1.0f / (float)(samps * 4);
+            for (float3& px : c) { px.x *= inv; px.y *= inv; px.z *= inv; }
+        }
         const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
-        const spt_stats& st = renderer.stats();
+        const spt_stats& st = denoise_levels >= 0 ? radiance : renderer.stats();
         std::fprintf(stderr, "Rendering (%d spp) 100.00%%\nElapsed time: %lld ms\n", samps * 4, (long long)ms);   // :368,373
         std::fprintf(stderr, "kernel %.3f ms, %.1f Msamples/s, %.3f bounces/sample, grid %u x %u\n", st.kernel_ms,
                      st.samples / (st.kernel_ms * 1e3), (double)st.bounces / (double)st.samples, st.grid_blocks, st.block_threads);

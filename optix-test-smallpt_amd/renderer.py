@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SptCamera, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
+from ._lib import SptCamera, SptDenoiseParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
 from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
@@ -155,6 +155,33 @@ def _aov_kind(aov):
     if not isinstance(aov, str) or aov not in AOV_KINDS:
         raise ValueError(f"unknown aov {aov!r}: one of {', '.join(AOV_KINDS)}")
     return AOV_KINDS[aov]
+
+
+class DenoiseParams:
+    """Parameters of the edge-avoiding wavelet filter (spt_denoise_params): ``levels`` passes (1..5, pass i at step 2^i pixels) and the four
+    edge-stopping strengths, each finite and >= 0.  Anything left None takes the library's default (spt_denoise_params_default);
+    ``sigma_plane`` is in 1/(scene length)^2 and the default suits the Cornell box's scale of about 100."""
+    FIELDS = ("levels", "sigma_normal", "sigma_plane", "sigma_albedo", "sigma_coverage")
+
+    def __init__(self, levels=None, sigma_normal=None, sigma_plane=None, sigma_albedo=None, sigma_coverage=None):
+        c = SptDenoiseParams()
+        load_library().spt_denoise_params_default(C.byref(c))
+        given = (levels, sigma_normal, sigma_plane, sigma_albedo, sigma_coverage)
+        for name, v in zip(self.FIELDS, given):
+            setattr(self, name, getattr(c, name) if v is None else (int(v) if name == "levels" else float(v)))
+
+    def as_c(self):
+        c = SptDenoiseParams()
+        for name in self.FIELDS:
+            setattr(c, name, getattr(self, name))
+        return c
+
+    def __repr__(self):
+        return "DenoiseParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.FIELDS) + ")"
+
+
+def _denoise_params(params):
+    return (params if params is not None else DenoiseParams()).as_c()
 
 
 class SptError(RuntimeError):
@@ -569,6 +596,88 @@ class Renderer:
         self._check(self._lib.spt_render_aov_set_rows_device(
             self._h, C.byref(cam), w, h, row_begin, row_count, samps_per_cell, seed, mask,
             FLAG_NORMALISE if normalise else 0, ptrs, C.c_void_p(stream) if stream else None))
+
+    def denoise(self, beauty, normal, albedo, position, coverage, aov_samples, params=None):
+        """Edge-avoiding wavelet filter (spt_denoise) of ``beauty`` guided by the four feature buffers: five (h, w, 3) float32 images,
+        all UN-NORMALISED sums (``render(..., normalise=False)`` and ``render_aov_set(..., kinds=('normal', 'albedo', 'position',
+        'coverage'))`` of the same camera, samples and seed); ``aov_samples`` = samples per pixel summed into the guides (4 * samps per
+        launch).  Returns the filtered un-normalised sum, (h, w, 3) float32: divide by the sample count for display."""
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (beauty, normal, albedo, position, coverage)]
+        if imgs[0].ndim != 3 or imgs[0].shape[2] != 3 or any(a.shape != imgs[0].shape for a in imgs):
+            raise ValueError("denoise: five (h, w, 3) images of one size")
+        h, w, _ = imgs[0].shape
+        out = np.empty((h, w, 3), dtype=np.float32)
+        p = _denoise_params(params)
+        self._check(self._lib.spt_denoise(self._h, *[a.ctypes.data_as(C.c_void_p) for a in imgs], w, h, int(aov_samples), C.byref(p),
+                                          out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoise_device(self, beauty_t, normal_t, albedo_t, position_t, coverage_t, out_t, w, h, aov_samples, params=None, stream=None):
+        """The same on contiguous float32 CUDA tensors of w*h*3 elements (spt_denoise_device); asynchronous on ``stream`` (a raw
+        hipStream_t, None = the context's stream).  ``out_t`` may not alias an input."""
+        ts = (beauty_t, normal_t, albedo_t, position_t, coverage_t, out_t)
+        for t in ts:
+            if t.numel() != w * h * 3 or not t.is_contiguous() or str(t.dtype) != "torch.float32" or t.device.type != "cuda":
+                raise ValueError("denoise_device: contiguous float32 tensors of w*h*3 elements on the GPU")
+        p = _denoise_params(params)
+        self._check(self._lib.spt_denoise_device(self._h, *[C.c_void_p(t.data_ptr()) for t in ts[:5]], w, h, int(aov_samples), C.byref(p),
+                                                 C.c_void_p(out_t.data_ptr()), C.c_void_p(stream) if stream else None))
+
+    # The render thread's loop behind the C-ABI (spt_progressive_*): radiance and feature accumulators resident on the device.
+    def progressive_begin(self, w, h, aov_kinds=None):
+        """spt_progressive_begin, and spt_progressive_aov_begin for ``aov_kinds`` (names as ``render_aov_set``) when given."""
+        self._check(self._lib.spt_progressive_begin(self._h, w, h))
+        self._prog = (w, h, ())
+        if aov_kinds is not None:
+            mask, names = _aov_set(aov_kinds)
+            self._check(self._lib.spt_progressive_aov_begin(self._h, mask))
+            self._prog = (w, h, tuple(names))
+
+    def progressive_frame(self, samps_per_cell, seed, clear=False, camera=None):
+        """One radiance frame added to (``clear``: replacing) accumBuffer; blocking.  Returns the stats."""
+        w, h, _ = self._prog_size("progressive_frame")
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        st = SptStats()
+        self._check(self._lib.spt_progressive_frame(self._h, C.byref(cam), samps_per_cell, seed, 1 if clear else 0, C.byref(st)))
+        return _stats_dict(st)
+
+    def progressive_aov_frame(self, samps_per_cell, seed, clear=False, camera=None):
+        """One fused launch of the selected feature buffers added to (``clear``: replacing) their accumulators; blocking."""
+        w, h, _ = self._prog_size("progressive_aov_frame")
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        st = SptStats()
+        self._check(self._lib.spt_progressive_aov_frame(self._h, C.byref(cam), samps_per_cell, seed, 1 if clear else 0, C.byref(st)))
+        return _stats_dict(st)
+
+    def progressive_snapshot(self, kind=None):
+        """accumBuffer (kind None) or the accumulator of one selected feature kind: (h, w, 3) float32, un-normalised."""
+        w, h, _ = self._prog_size("progressive_snapshot")
+        out = np.empty((h, w, 3), dtype=np.float32)
+        if kind is None:
+            self._check(self._lib.spt_progressive_snapshot(self._h, out.ctypes.data_as(C.c_void_p)))
+        else:
+            self._check(self._lib.spt_progressive_aov_snapshot(self._h, 1 << AOV_SET_KINDS[kind], out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def progressive_denoised_snapshot(self, aov_samples, params=None):
+        """accumBuffer filtered under the feature accumulators (spt_progressive_denoised_snapshot): needs ``progressive_begin`` with at
+        least normal, albedo, position and coverage.  ``aov_samples`` = frames * 4 * samps accumulated into the features.  Returns the
+        filtered un-normalised sum, (h, w, 3) float32; neither accumulator changes."""
+        w, h, _ = self._prog_size("progressive_denoised_snapshot")
+        out = np.empty((h, w, 3), dtype=np.float32)
+        p = _denoise_params(params)
+        self._check(self._lib.spt_progressive_denoised_snapshot(self._h, int(aov_samples), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def progressive_end(self):
+        self._check(self._lib.spt_progressive_end(self._h))
+        self._prog = None
+
+    def _prog_size(self, who):
+        prog = getattr(self, "_prog", None)
+        if prog is None:
+            raise SptError(f"{who}: call progressive_begin first")
+        return prog
 
     def set_watchdog(self, seconds):
         """Pool kernel: a launch whose waves run longer than this fails in sync() instead of hanging (0 = off)."""
