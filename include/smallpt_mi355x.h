@@ -441,6 +441,13 @@ int  spt_render_aov_set_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_
  * d_accum[i] = clear ? d_frame[i] : d_accum[i] + d_frame[i] for n floats (both 16-byte aligned, on this device);
  * enqueued on hip_stream (NULL = the context's stream).  Display weight = 1/(frames*spp) (smallpt.cpp:957). */
 int  spt_accumulate_device(spt_ctx* ctx, void* d_accum, const void* d_frame, uint64_t n, int clear, void* hip_stream);
+/* The same accumulation of npix packed float3 pixels together with the per-pixel second moment of the frame's luminance, by one kernel
+ * that reads the frame once (csrc/spt_denoise_var.hip).  Per pixel with frame value f, in float32, one rounding per operation, no
+ * contraction:
+ *     d_accum (clear ? = : +=) f, component by component -- the adds of spt_accumulate_device, so d_accum is bit-identical to its result;
+ *     L = (0.2126f*f.x + 0.7152f*f.y) + 0.0722f*f.z;   d_m2 (clear ? = : +=) L*L.
+ * d_accum and d_frame: 3*npix floats, 16-byte aligned; d_m2: npix floats, 4-byte aligned; npix need be a multiple of nothing. */
+int  spt_accumulate_moments_device(spt_ctx* ctx, void* d_accum, void* d_m2, const void* d_frame, uint64_t npix, int clear, void* hip_stream);
 
 /* The same for a rank of a multi-GPU render whose rows are dealt out round-robin in blocks of `block_rows` rows (a power of
  * two): block t of the image (rows [t*B, (t+1)*B)) belongs to rank t % world.  Contiguous bands of a Cornell-like image
@@ -518,8 +525,7 @@ int  spt_progressive_aov_snapshot(spt_ctx* ctx, uint32_t kind_bit, float* out_rg
  *   Scratch (the packed guides and two colour images, 80 bytes per pixel) belongs to the context, is grown on demand and freed by
  *     spt_destroy and spt_progressive_end; a failed allocation fails the call and leaves the context usable.  Calls of one context run
  *     one after another, whatever their streams (they share the scratch).  A call changes no render state.
- *   Out of scope: albedo demodulation; variance-guided colour edge stopping (the library has no second-moment buffer); temporal
- *     reprojection; the multi-GPU front; the async lanes (they stay radiance-only). */
+ *   Out of scope: albedo demodulation; temporal reprojection; the multi-GPU front; the async lanes (they stay radiance-only). */
 typedef struct spt_denoise_params {
     uint32_t levels;      /* 1..5 passes; pass i uses step 2^i pixels */
     float sigma_normal, sigma_plane, sigma_albedo, sigma_coverage;  /* each finite and >= 0 */
@@ -541,6 +547,58 @@ int  spt_denoise(spt_ctx* ctx, const float* beauty, const float* normal, const f
  * spt_progressive_snapshot's layout.  It modifies neither accumulator nor the render state (chunk-order records, spt_last_kernel,
  * SPT_ACCEL_AUTO's bounce share).  The result is, bit for bit, spt_denoise applied to the five snapshots. */
 int  spt_progressive_denoised_snapshot(spt_ctx* owner, uint32_t aov_samples, const spt_denoise_params* params, float* out_rgb);
+
+/* Per-pixel variance over the frames of the progressive loop, and the filter guided by it (csrc/spt_denoise_var.hip).
+ *   spt_progressive_moments_begin(ctx)   after spt_progressive_begin: one zeroed w*h float buffer M2 on the device and a frame count n = 0,
+ *     both the owner's; freed by spt_progressive_end and by the next spt_progressive_begin.  From then on the accumulation step of
+ *     spt_progressive_frame / _frame_async runs spt_accumulate_moments_device's kernel in place of spt_accumulate_device's: accumBuffer stays
+ *     bit-identical, M2 (clear ? = : +=) L*L of the frame, and n becomes 1 on a clearing frame, else n + 1.  Frames of attached lanes land in
+ *     the owner's M2 and n in call order, like their accumulations.  The variance is defined once a frame with clear != 0 has been issued
+ *     since the begin; until then the entry points below fail.
+ *   spt_progressive_variance_snapshot(owner, out_var, frames)   waits like spt_progressive_snapshot, then writes w*h floats (row 0 =
+ *     bottom) to host memory and n to *frames (may be NULL).  Per pixel, computed on the device, with lum(c) = (0.2126f*c.x + 0.7152f*c.y) +
+ *     0.0722f*c.z and nf = (float)n:
+ *         m = lum(accum) / nf;   s = M2 / nf;   v = s - m*m;   v = v > 0 ? v : 0
+ *     the BIASED variance estimate of ONE frame's luminance (a display divides by n for the variance of the mean).  There is no Bessel
+ *     factor n / (n - 1): it would cost a division per pixel and the filter's sigma_colour absorbs it.  With n == 1 the result is exactly 0.
+ *   Variance-guided filter: spt_denoise* with the luminance edge-stopping term of SVGF (Schied et al. 2017), so that edges of the lighting
+ *     that are no edges of the geometry -- contact shadows, caustics, reflections -- survive as far as the frames' variance tells them from
+ *     noise.  Images, guides n, a, x, k, validation, scratch, streams and "changes no render state" are those of spt_denoise*; in addition
+ *     `m2` (w*h floats: the sum over `frames` frames of L*L) and `frames` >= 2 (else it fails), sigma_colour finite and >= 0, and d_out may
+ *     not equal d_m2 either.  Arithmetic as there (float32, one rounding per operation, no contraction, correctly rounded division):
+ *       The colour image is {r, g, b, var}.  Initially var = nf * v with v as above from (beauty, m2, frames): the variance of the SUM of n
+ *       independent frames, as the colour is the un-normalised sum.
+ *       Per pass and centre p:
+ *         gv = 3 x 3 binomial of the current var around p at +-1 pixel whatever the step, coordinates clamped to the image: dy = -1 .. 1
+ *              outer, dx = -1 .. 1 inner, from 0.0f: gv += (g(dy)*g(dx)) * var_q with g = (1/4, 1/2, 1/4) (the products are exact);
+ *         Lp = lum(colour_p) of the current iterate, Lq likewise per tap;
+ *         per tap (order and skipping as spt_denoise), en, ep, ea, ek as there:
+ *           dl = Lp - Lq;   el = (dl*dl) / (gv + 1e-12f)
+ *           D  = 1.0f + ((((sigma_normal*en + sigma_plane*ep) + sigma_albedo*ea) + sigma_coverage*ek) + sigma_colour*el)
+ *           wt = (hy*hx) / D
+ *           num_j += wt * colour_q[j];   den += wt;   vnum += (wt*wt) * var_q
+ *         out_j = num_j / den;   out_var = vnum / (den*den).  The last pass writes the packed float3 only.
+ *       The falloff stays rational (no exp).  With sigma_colour == 0 the term adds +0.0f to a non-negative sum: the result is bit-identical
+ *       to spt_denoise with the same four strengths.  Inputs for which dl*dl / (gv + 1e-12f) overflows are outside the contract, like
+ *       non-finite pixels.  Pinned bit for bit by tests/denoise_var_expected.py (numpy) and tests/test_gpu_denoise_var.py.
+ *   spt_progressive_denoised_var_snapshot   spt_progressive_denoised_snapshot with accumBuffer, M2 and n of the loop: needs the four feature
+ *     accumulators, moments begun and defined, and n >= 2.  Bit for bit spt_denoise_var of the five snapshots, M2 and n. */
+typedef struct spt_denoise_var_params {
+    uint32_t levels;      /* 1..5 */
+    float sigma_normal, sigma_plane, sigma_albedo, sigma_coverage;  /* as spt_denoise_params */
+    float sigma_colour;   /* finite and >= 0; dimensionless: it weighs a squared luminance difference in units of the variance */
+} spt_denoise_var_params;
+/* Host-only: the defaults of spt_denoise_params_default and sigma_colour = 0.5 (chosen on the Cornell box). */
+void spt_denoise_var_params_default(spt_denoise_var_params* params);
+int  spt_progressive_moments_begin(spt_ctx* ctx);
+int  spt_progressive_variance_snapshot(spt_ctx* owner, float* out_var, uint32_t* frames);
+int  spt_denoise_var_device(spt_ctx* ctx, const void* d_beauty, const void* d_normal, const void* d_albedo, const void* d_position,
+                            const void* d_coverage, const void* d_m2, uint32_t w, uint32_t h, uint32_t aov_samples, uint32_t frames,
+                            const spt_denoise_var_params* params, void* d_out, void* hip_stream);
+int  spt_denoise_var(spt_ctx* ctx, const float* beauty, const float* normal, const float* albedo, const float* position,
+                     const float* coverage, const float* m2, uint32_t w, uint32_t h, uint32_t aov_samples, uint32_t frames,
+                     const spt_denoise_var_params* params, float* out);
+int  spt_progressive_denoised_var_snapshot(spt_ctx* owner, uint32_t aov_samples, const spt_denoise_var_params* params, float* out_rgb);
 /* The same loop with SEVERAL FRAMES IN FLIGHT.  The reference overlaps its render thread with the GL thread (smallpt.cpp:895-962);
  * on the GPU the end of a 4-spp frame is a handful of long specular chains that leave most of the chip idle, so a host that
  * issues frame k+1 before frame k has drained keeps it busy.  A context renders one frame at a time (its scratch buffers belong

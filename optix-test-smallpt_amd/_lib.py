@@ -41,6 +41,11 @@ class SptDenoiseParams(C.Structure):
                 ("sigma_coverage", C.c_float)]
 
 
+class SptDenoiseVarParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_coverage", C.c_float), ("sigma_colour", C.c_float)]
+
+
 class SptInstance(C.Structure):      # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
     _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
 
@@ -92,6 +97,7 @@ SYMBOLS = {
     "spt_render_interleaved_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.c_uint64, C.c_uint32, _P, _P]),
     "spt_accumulate_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _P]),
+    "spt_accumulate_moments_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int, _P]),
     "spt_progressive_begin": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "spt_progressive_frame": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int, C.POINTER(SptStats)]),
     "spt_progressive_snapshot": (C.c_int, [_P, _P]),
@@ -102,6 +108,12 @@ SYMBOLS = {
     "spt_denoise_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseParams), _P, _P]),
     "spt_denoise": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseParams), _P]),
     "spt_progressive_denoised_snapshot": (C.c_int, [_P, C.c_uint32, C.POINTER(SptDenoiseParams), _P]),
+    "spt_denoise_var_params_default": (None, [C.POINTER(SptDenoiseVarParams)]),
+    "spt_progressive_moments_begin": (C.c_int, [_P]),
+    "spt_progressive_variance_snapshot": (C.c_int, [_P, _P, C.POINTER(C.c_uint32)]),
+    "spt_denoise_var_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseVarParams), _P, _P]),
+    "spt_denoise_var": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseVarParams), _P]),
+    "spt_progressive_denoised_var_snapshot": (C.c_int, [_P, C.c_uint32, C.POINTER(SptDenoiseVarParams), _P]),
     "spt_progressive_attach": (C.c_int, [_P, _P]),
     "spt_progressive_frame_async": (C.c_int, [_P, _P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int]),
     "spt_progressive_wait": (C.c_int, [_P, C.POINTER(SptStats)]),

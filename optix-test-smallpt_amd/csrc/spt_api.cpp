@@ -10,6 +10,7 @@
 #include "spt_aov.h"
 #include "spt_instance.h"
 #include "spt_denoise.h"
+#include "spt_denoise_var.h"
 
 #include <chrono>
 #include <cmath>
@@ -124,6 +125,9 @@ struct spt_ctx {
     uint32_t prog_w = 0, prog_h = 0;
     uint32_t aov_mask = 0;         // spt_progressive_aov_*: the selected kinds; per kind an accumulation buffer and a frame, w*h*3 floats each
     float* d_aov_accum[6] = {}; float* d_aov_frame[6] = {};
+    // spt_progressive_moments_begin (owner): per-pixel sum of the frames' squared luminance (w*h floats), the frames summed into it and into
+    // accumBuffer since the last clearing frame, and whether a clearing frame has been issued since the begin (the variance is defined)
+    float* d_m2 = nullptr; uint32_t m2_frames = 0; bool m2_valid = false;
     // spt_denoise*: packed guides (3 planes of float4), two float4 colour images (ping-pong) and the float3 result of the progressive
     // snapshot, grown on demand; calls of one context run one after another, whatever their streams (they share these)
     float4* d_dn_guides = nullptr; size_t dn_guides_cap = 0;
@@ -269,6 +273,12 @@ static void denoise_free(spt_ctx* c)
     c->dn_guides_cap = c->dn_ping_cap = c->dn_pong_cap = c->dn_out_cap = 0;
 }
 
+static void moments_free(spt_ctx* c)
+{
+    if (c->d_m2) (void)hipFree(c->d_m2);
+    c->d_m2 = nullptr; c->m2_frames = 0; c->m2_valid = false;
+}
+
 static void progressive_aov_free(spt_ctx* c)
 {
     for (int k = 0; k < 6; ++k) {
@@ -293,6 +303,7 @@ void spt_destroy(spt_ctx* c)
     if (c->d_accum) (void)hipFree(c->d_accum);
     if (c->d_frame) (void)hipFree(c->d_frame);
     progressive_aov_free(c);
+    moments_free(c);
     denoise_free(c);
     if (c->ev_denoise) (void)hipEventDestroy(c->ev_denoise);
     for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
@@ -2214,6 +2225,20 @@ int spt_accumulate_device(spt_ctx* c, void* d_accum, const void* d_frame, uint64
     return 0;
 }
 
+// The same with the per-pixel second moment of the frame's luminance (spt_denoise_var.hip): npix pixels, d_m2 npix floats.
+int spt_accumulate_moments_device(spt_ctx* c, void* d_accum, void* d_m2, const void* d_frame, uint64_t npix, int clear, void* hip_stream)
+{
+    if (!c) return 1;
+    if (!d_accum || !d_m2 || !d_frame || !npix) return c->fail("spt_accumulate_moments_device: bad argument (a NULL pointer or npix == 0)");
+    if ((reinterpret_cast<uintptr_t>(d_accum) | reinterpret_cast<uintptr_t>(d_frame)) & 15u)
+        return c->fail("spt_accumulate_moments_device: d_accum and d_frame must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_m2) & 3u) return c->fail("spt_accumulate_moments_device: d_m2 must be 4-byte aligned");
+    SPT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    SPT_HIP(c, spt_moments_accumulate_launch(static_cast<float*>(d_accum), static_cast<float*>(d_m2), static_cast<const float*>(d_frame), (size_t)npix, clear, st));
+    return 0;
+}
+
 // ---- render-thread frame loop with the accumulation buffer in HBM (smallpt.cpp:881-883,895-942,955-959) ----
 int spt_progressive_end(spt_ctx* c)
 {
@@ -2226,6 +2251,7 @@ int spt_progressive_end(spt_ctx* c)
     if (c->d_frame) (void)hipFree(c->d_frame);
     c->d_accum = c->d_frame = nullptr;
     progressive_aov_free(c);
+    moments_free(c);
     if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));   // a filter a caller's stream still runs
     c->denoise_recorded = false;
     denoise_free(c);
@@ -2302,7 +2328,13 @@ int spt_progressive_frame_async(spt_ctx* c, spt_ctx* owner, const spt_camera* ca
     if (rrc) return rrc;
     // :927-937 accumBuffer (clear ? = : +=) outImage, behind the previous accumulation whichever lane issued it
     if (owner->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, owner->ev_acc, 0));
-    SPT_HIP(c, spt_k_accumulate(owner->d_accum, c->d_frame, (size_t)c->prog_w * c->prog_h * 3, clear, c->stream));
+    if (owner->d_m2) {          // moments on: the same adds and the squared luminance from one read of the frame (spt_denoise_var.hip)
+        SPT_HIP(c, spt_moments_accumulate_launch(owner->d_accum, owner->d_m2, c->d_frame, (size_t)c->prog_w * c->prog_h, clear, c->stream));
+        owner->m2_frames = clear ? 1u : owner->m2_frames + 1u;
+        if (clear) owner->m2_valid = true;
+    } else {
+        SPT_HIP(c, spt_k_accumulate(owner->d_accum, c->d_frame, (size_t)c->prog_w * c->prog_h * 3, clear, c->stream));
+    }
     SPT_HIP(c, hipEventRecord(owner->ev_acc, c->stream));
     owner->acc_recorded = true;
     c->frame_in_flight = true;
@@ -2334,6 +2366,48 @@ int spt_progressive_snapshot(spt_ctx* c, float* out_rgb)
     if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_accum, (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- second moment of the frames' luminance beside accumBuffer: from now on the loop's accumulation step also sums lum(frame)^2 ----
+int spt_progressive_moments_begin(spt_ctx* c)
+{
+    if (!c) return 1;
+    if (!c->d_accum) return c->fail("spt_progressive_moments_begin: call spt_progressive_begin first");
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->acc_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_acc));   // accumulations other lanes still have in flight
+    moments_free(c);
+    const size_t bytes = (size_t)c->prog_w * c->prog_h * sizeof(float);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_m2), bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_m2, 0, bytes, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev_acc, c->stream);     // later accumulations (any lane) run behind the clearing
+    if (e != hipSuccess) { (void)hipGetLastError(); moments_free(c); return c->fail("spt_progressive_moments_begin: %s", hipGetErrorString(e)); }
+    c->acc_recorded = true;
+    return 0;
+}
+
+// Moments on and a clearing frame issued since: what every variance entry point needs
+static int moments_check(spt_ctx* c, const char* who)
+{
+    if (!c->d_m2) return c->fail("%s: call spt_progressive_moments_begin first", who);
+    if (!c->m2_valid) return c->fail("%s: no frame with clear != 0 has been issued since spt_progressive_moments_begin", who);
+    return 0;
+}
+
+int spt_progressive_variance_snapshot(spt_ctx* c, float* out_var, uint32_t* frames)
+{
+    if (!c) return 1;
+    if (!c->d_accum || !out_var) return c->fail("spt_progressive_variance_snapshot: no accumulation buffer or out_var is NULL");
+    if (int rc = moments_check(c, "spt_progressive_variance_snapshot")) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->prog_w * c->prog_h;
+    if (grow_out(c, npix)) return 1;
+    if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
+    SPT_HIP(c, spt_moments_variance_launch(c->d_accum, c->d_m2, npix, (float)c->m2_frames, c->d_out, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(out_var, c->d_out, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (frames) *frames = c->m2_frames;
     return 0;
 }
 
@@ -2414,10 +2488,33 @@ static int denoise_check(spt_ctx* c, const char* who, uint32_t w, uint32_t h, ui
     return 0;
 }
 
-// Validated arguments, device set.  Enqueues the guide pack and the passes on st behind the context's previous filter.
+void spt_denoise_var_params_default(spt_denoise_var_params* p)
+{
+    if (!p) return;
+    spt_denoise_params four;
+    spt_denoise_params_default(&four);
+    p->levels = four.levels;
+    p->sigma_normal = four.sigma_normal; p->sigma_plane = four.sigma_plane; p->sigma_albedo = four.sigma_albedo; p->sigma_coverage = four.sigma_coverage;
+    p->sigma_colour = 0.5f;
+}
+
+// denoise_check of the four old fields (copied to *four) plus the two conditions of the variance-guided filter
+static int denoise_var_check(spt_ctx* c, const char* who, uint32_t w, uint32_t h, uint32_t aov_samples, uint32_t frames, const spt_denoise_var_params* p,
+                             spt_denoise_params* four)
+{
+    if (!p) return c->fail("%s: NULL argument", who);
+    *four = spt_denoise_params{p->levels, p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage};
+    if (int rc = denoise_check(c, who, w, h, aov_samples, four)) return rc;
+    if (!std::isfinite(p->sigma_colour) || p->sigma_colour < 0.f) return c->fail("%s: sigma_colour = %g is negative or not finite", who, (double)p->sigma_colour);
+    if (frames < 2) return c->fail("%s: frames = %u: the variance of the frames needs at least 2", who, frames);
+    return 0;
+}
+
+// Validated arguments, device set.  Enqueues the guide pack and the passes on st behind the context's previous filter.  m2 != nullptr
+// selects the variance-guided kernels (spt_denoise_var.hip) with the second moments of `frames` frames and sigma_colour.
 static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, const float* normal, const float* albedo, const float* position,
                            const float* coverage, uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_params* p, float* out,
-                           hipStream_t st)
+                           hipStream_t st, const float* m2 = nullptr, uint32_t frames = 0, float sigma_colour = 0.f)
 {
     const size_t npix = (size_t)w * h;
     if (npix > c->dn_guides_cap || npix > c->dn_ping_cap || npix > c->dn_pong_cap) {
@@ -2435,14 +2532,16 @@ static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, con
         for (hipEvent_t& e : c->dn_ev) if (!e) SPT_HIP(c, hipEventCreate(&e));
         SPT_HIP(c, hipEventRecord(c->dn_ev[0], st));
     }
-    SPT_HIP(c, spt_denoise_pack_launch(beauty, normal, albedo, position, coverage, (uint32_t)npix, (float)aov_samples, c->d_dn_ping, c->d_dn_guides, st));
-    const float sigma[4] = {p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage};
+    if (m2) SPT_HIP(c, spt_denoise_var_pack_launch(beauty, normal, albedo, position, coverage, m2, (uint32_t)npix, (float)aov_samples, (float)frames, c->d_dn_ping, c->d_dn_guides, st));
+    else SPT_HIP(c, spt_denoise_pack_launch(beauty, normal, albedo, position, coverage, (uint32_t)npix, (float)aov_samples, c->d_dn_ping, c->d_dn_guides, st));
+    const float sigma[5] = {p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage, sigma_colour};
     if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[1], st));
     float4* src = c->d_dn_ping;
     float4* dst = c->d_dn_pong;
     for (uint32_t i = 0; i < p->levels; ++i) {
         const bool last = i + 1 == p->levels;
-        SPT_HIP(c, spt_denoise_pass_launch(src, c->d_dn_guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
+        if (m2) SPT_HIP(c, spt_denoise_var_pass_launch(src, c->d_dn_guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
+        else SPT_HIP(c, spt_denoise_pass_launch(src, c->d_dn_guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
         if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[2 + i], st));
         std::swap(src, dst);
     }
@@ -2488,26 +2587,88 @@ int spt_denoise(spt_ctx* c, const float* beauty, const float* normal, const floa
     return 0;
 }
 
-int spt_progressive_denoised_snapshot(spt_ctx* c, uint32_t aov_samples, const spt_denoise_params* p, float* out_rgb)
+// The two filtered snapshots of the progressive loop: vp == nullptr is the guide-only filter under *p
+static int progressive_denoised(spt_ctx* c, const char* who, uint32_t aov_samples, const spt_denoise_params* p, const spt_denoise_var_params* vp,
+                                float* out_rgb)
 {
-    if (!c) return 1;
-    if (!c->d_accum || !out_rgb) return c->fail("spt_progressive_denoised_snapshot: no accumulation buffer or out_rgb is NULL");
+    if (!c->d_accum || !out_rgb) return c->fail("%s: no accumulation buffer or out_rgb is NULL", who);
     const uint32_t need = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE, missing = need & ~c->aov_mask;
     if (missing)
-        return c->fail("spt_progressive_denoised_snapshot: spt_progressive_aov_begin has not selected%s%s%s%s", (missing & SPT_AOVSET_NORMAL) ? " NORMAL" : "",
+        return c->fail("%s: spt_progressive_aov_begin has not selected%s%s%s%s", who, (missing & SPT_AOVSET_NORMAL) ? " NORMAL" : "",
                        (missing & SPT_AOVSET_ALBEDO) ? " ALBEDO" : "", (missing & SPT_AOVSET_POSITION) ? " POSITION" : "", (missing & SPT_AOVSET_COVERAGE) ? " COVERAGE" : "");
-    if (int rc = denoise_check(c, "spt_progressive_denoised_snapshot", c->prog_w, c->prog_h, aov_samples, p)) return rc;
+    spt_denoise_params four;
+    if (vp) {
+        if (int rc = moments_check(c, who)) return rc;
+        if (int rc = denoise_var_check(c, who, c->prog_w, c->prog_h, aov_samples, c->m2_frames, vp, &four)) return rc;
+        p = &four;
+    } else if (int rc = denoise_check(c, who, c->prog_w, c->prog_h, aov_samples, p)) return rc;
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t nfl = (size_t)c->prog_w * c->prog_h * 3;
     if (nfl > c->dn_out_cap) {
         if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));
         const hipError_t e = grow(c->d_dn_out, c->dn_out_cap, nfl);
-        if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("spt_progressive_denoised_snapshot: scratch: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: scratch: %s", who, hipGetErrorString(e)); }
     }
     if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
-    if (int rc = denoise_enqueue(c, "spt_progressive_denoised_snapshot", c->d_accum, c->d_aov_accum[SPT_AOV_NORMAL], c->d_aov_accum[SPT_AOV_ALBEDO],
-                                 c->d_aov_accum[4], c->d_aov_accum[5], c->prog_w, c->prog_h, aov_samples, p, c->d_dn_out, c->stream)) return rc;
+    if (int rc = denoise_enqueue(c, who, c->d_accum, c->d_aov_accum[SPT_AOV_NORMAL], c->d_aov_accum[SPT_AOV_ALBEDO], c->d_aov_accum[4], c->d_aov_accum[5],
+                                 c->prog_w, c->prog_h, aov_samples, p, c->d_dn_out, c->stream, vp ? c->d_m2 : nullptr, c->m2_frames, vp ? vp->sigma_colour : 0.f)) return rc;
     SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_dn_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int spt_progressive_denoised_snapshot(spt_ctx* c, uint32_t aov_samples, const spt_denoise_params* p, float* out_rgb)
+{
+    if (!c) return 1;
+    return progressive_denoised(c, "spt_progressive_denoised_snapshot", aov_samples, p, nullptr, out_rgb);
+}
+
+int spt_progressive_denoised_var_snapshot(spt_ctx* c, uint32_t aov_samples, const spt_denoise_var_params* p, float* out_rgb)
+{
+    if (!c) return 1;
+    if (!p) return c->fail("spt_progressive_denoised_var_snapshot: NULL argument");
+    return progressive_denoised(c, "spt_progressive_denoised_var_snapshot", aov_samples, nullptr, p, out_rgb);
+}
+
+// ---- the variance-guided filter on a caller's images (spt_denoise_var.hip) ----
+int spt_denoise_var_device(spt_ctx* c, const void* d_beauty, const void* d_normal, const void* d_albedo, const void* d_position, const void* d_coverage,
+                           const void* d_m2, uint32_t w, uint32_t h, uint32_t aov_samples, uint32_t frames, const spt_denoise_var_params* p, void* d_out,
+                           void* hip_stream)
+{
+    if (!c) return 1;
+    if (!d_beauty || !d_normal || !d_albedo || !d_position || !d_coverage || !d_m2 || !d_out) return c->fail("spt_denoise_var_device: NULL argument");
+    spt_denoise_params four;
+    if (int rc = denoise_var_check(c, "spt_denoise_var_device", w, h, aov_samples, frames, p, &four)) return rc;
+    const void* const ptrs[7] = {d_beauty, d_normal, d_albedo, d_position, d_coverage, d_m2, d_out};
+    for (const void* q : ptrs)
+        if (reinterpret_cast<uintptr_t>(q) & 3u) return c->fail("spt_denoise_var_device: buffers must be 4-byte aligned");
+    for (int i = 0; i < 6; ++i)
+        if (ptrs[i] == d_out) return c->fail("spt_denoise_var_device: d_out aliases an input");
+    SPT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return denoise_enqueue(c, "spt_denoise_var_device", static_cast<const float*>(d_beauty), static_cast<const float*>(d_normal), static_cast<const float*>(d_albedo),
+                           static_cast<const float*>(d_position), static_cast<const float*>(d_coverage), w, h, aov_samples, &four, static_cast<float*>(d_out), st,
+                           static_cast<const float*>(d_m2), frames, p->sigma_colour);
+}
+
+int spt_denoise_var(spt_ctx* c, const float* beauty, const float* normal, const float* albedo, const float* position, const float* coverage, const float* m2,
+                    uint32_t w, uint32_t h, uint32_t aov_samples, uint32_t frames, const spt_denoise_var_params* p, float* out)
+{
+    if (!c) return 1;
+    if (!beauty || !normal || !albedo || !position || !coverage || !m2 || !out) return c->fail("spt_denoise_var: NULL argument");
+    spt_denoise_params four;
+    if (int rc = denoise_var_check(c, "spt_denoise_var", w, h, aov_samples, frames, p, &four)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t nfl = (size_t)w * h * 3, pitch = (nfl + 3) & ~(size_t)3;
+    if (grow_out(c, pitch * 7)) return 1;
+    const float* const host[5] = {beauty, normal, albedo, position, coverage};
+    for (int j = 0; j < 5; ++j)
+        SPT_HIP(c, hipMemcpyAsync(c->d_out + j * pitch, host[j], nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float* const d = c->d_out;
+    SPT_HIP(c, hipMemcpyAsync(d + 6 * pitch, m2, (size_t)w * h * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int rc = denoise_enqueue(c, "spt_denoise_var", d, d + pitch, d + 2 * pitch, d + 3 * pitch, d + 4 * pitch, w, h, aov_samples, &four, d + 5 * pitch, c->stream,
+                                 d + 6 * pitch, frames, p->sigma_colour)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out, d + 5 * pitch, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -15,12 +15,9 @@
 //     direct form  (steps 4, 8, 16) the taps of one pixel are far apart but the taps of a row of lanes are contiguous: a 64 x 4
 //                  workgroup, one wave per image row segment, four coalesced 16-byte loads per tap (1 KiB per wave-instruction).
 #include "spt_denoise.h"
+#include "spt_denoise_tap.h"
 
 namespace spt {
-
-constexpr int kDnThreads = 256;
-constexpr int kDnTileW = 32, kDnTileH = 8;       // tile form
-constexpr int kDnRowW = 64, kDnRowH = 4;         // direct form
 
 __global__ __launch_bounds__(kDnThreads) void denoise_pack(const float* __restrict__ beauty, const float* __restrict__ normal,
                                                            const float* __restrict__ albedo, const float* __restrict__ position,
@@ -44,24 +41,12 @@ __global__ __launch_bounds__(kDnThreads) void denoise_pack(const float* __restri
     }
 }
 
-// B3 row (1/16, 1/4, 3/8, 1/4, 1/16): every value and every product of two is exact in binary
-__device__ __forceinline__ float b3(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
-
 // One tap q for the centre p.  p0 / q0 = {n, k}, p1 / q1 = {x, a.x}, p2 / q2 = {a.y, a.z, -, -}; hw = hy * hx.
 __device__ __forceinline__ void denoise_tap(const float4 col, const float4 q0, const float4 q1, const float4 q2, const float4 p0,
                                             const float4 p1, const float4 p2, const float hw, const float4 sigma, float& n0, float& n1,
                                             float& n2, float& den)
 {
-    const float dnx = p0.x - q0.x, dny = p0.y - q0.y, dnz = p0.z - q0.z;
-    const float en = (dnx * dnx + dny * dny) + dnz * dnz;
-    const float dax = p1.w - q1.w, day = p2.x - q2.x, daz = p2.y - q2.y;
-    const float ea = (dax * dax + day * day) + daz * daz;
-    const float dxx = q1.x - p1.x, dxy = q1.y - p1.y, dxz = q1.z - p1.z;
-    const float pl = (p0.x * dxx + p0.y * dxy) + p0.z * dxz;
-    const float ep = pl * pl;
-    const float dk = p0.w - q0.w;
-    const float ek = dk * dk;
-    const float D = 1.0f + (((sigma.x * en + sigma.y * ep) + sigma.z * ea) + sigma.w * ek);
+    const float D = 1.0f + denoise_edges(q0, q1, q2, p0, p1, p2, sigma);
     const float wt = hw / D;
     n0 += wt * col.x;
     n1 += wt * col.y;

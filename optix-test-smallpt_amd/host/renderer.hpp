@@ -98,6 +98,44 @@ public:
         check(spt_progressive_denoised_snapshot(ctx_, (uint32_t)aovSamples, &p, reinterpret_cast<float*>(image.data())));
     }
 
+    // Variance-guided filter (spt_denoise_var): denoise() with m2 = the sum over `frames` >= 2 frames of the squared frame luminance, beauty
+    // being the sum of the same frames.  params = nullptr: spt_denoise_var_params_default.
+    std::vector<float3> denoiseVar(const std::vector<float3>& beauty, const std::vector<float3>& normal, const std::vector<float3>& albedo,
+                                   const std::vector<float3>& position, const std::vector<float3>& coverage, const std::vector<float>& m2,
+                                   size_t imageWidth, size_t imageHeight, size_t aovSamples, size_t frames, const spt_denoise_var_params* params = nullptr)
+    {
+        const size_t n = imageWidth * imageHeight;
+        if (beauty.size() != n || normal.size() != n || albedo.size() != n || position.size() != n || coverage.size() != n || m2.size() != n)
+            throw std::runtime_error("denoiseVar: six images of imageWidth * imageHeight pixels");
+        spt_denoise_var_params p;
+        if (params) p = *params; else spt_denoise_var_params_default(&p);
+        std::vector<float3> out(n);
+        auto f = [](const std::vector<float3>& v) { return reinterpret_cast<const float*>(v.data()); };
+        check(spt_denoise_var(ctx_, f(beauty), f(normal), f(albedo), f(position), f(coverage), m2.data(), (uint32_t)imageWidth, (uint32_t)imageHeight,
+                              (uint32_t)aovSamples, (uint32_t)frames, &p, reinterpret_cast<float*>(out.data())));
+        return out;
+    }
+    // ... and over the progressive loop: feature accumulators (spt_progressive_aov_*), second moments (spt_progressive_moments_begin),
+    // the per-pixel variance of a frame's luminance and the variance-guided snapshot
+    void progressiveAovBegin(uint32_t mask) { check(spt_progressive_aov_begin(ctx_, mask)); }
+    void progressiveAovFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool clear)
+    {
+        check(spt_progressive_aov_frame(ctx_, &camera, (uint32_t)sampleCountPerJitterCell, (uint64_t)seed, clear ? 1 : 0, nullptr));
+    }
+    void progressiveMomentsBegin() { check(spt_progressive_moments_begin(ctx_)); }
+    uint32_t progressiveVarianceSnapshot(std::vector<float>& variance)
+    {
+        uint32_t frames = 0;
+        check(spt_progressive_variance_snapshot(ctx_, variance.data(), &frames));
+        return frames;
+    }
+    void progressiveDenoisedVarSnapshot(size_t aovSamples, std::vector<float3>& image, const spt_denoise_var_params* params = nullptr)
+    {
+        spt_denoise_var_params p;
+        if (params) p = *params; else spt_denoise_var_params_default(&p);
+        check(spt_progressive_denoised_var_snapshot(ctx_, (uint32_t)aovSamples, &p, reinterpret_cast<float*>(image.data())));
+    }
+
     // accumBuffer of the viewer loop in HBM (spt_progressive_*, smallpt.cpp:881-883,922-937,955-959)
     void progressiveBegin(size_t w, size_t h) { check(spt_progressive_begin(ctx_, (uint32_t)w, (uint32_t)h)); }
     void progressiveFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool clear)

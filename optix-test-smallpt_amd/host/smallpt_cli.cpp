@@ -14,6 +14,10 @@
 //                  [--denoise [LEVELS]]                           radiance and the normal / albedo / position / coverage set of the same camera, samples
 //                                                              and seed, filtered by spt_denoise (default parameters, LEVELS = 1..5 passes);
 //                                                              --out gets the filtered image divided by spp
+//                  [--denoise [LEVELS] --frames N]                N >= 2 progressive frames of spp each (seeds seed .. seed+N-1, clear on the first) with
+//                                                              the feature accumulators and the second moments, filtered by
+//                                                              spt_progressive_denoised_var_snapshot (variance-guided, default parameters);
+//                                                              --out gets the filtered sum divided by N * spp
 //                  [--devices 0,1,...] [--self-exchange]      row bands over several GPUs + RCCL exchange (MultiRenderer)
 //                  [--env r,g,b] [--print-environment]         radiance of escaped paths (overrides the scene file's "environment"); print it
 //                                                              as loaded and overridden, then exit (host only)
@@ -57,6 +61,7 @@ int main(int argc, char* argv[])
     int denoise_levels = -1;                       // --denoise: 0 = the default level count, 1..5 = that many passes (-1: off)
     bool parse_only = false, viewer = false, threaded = false, self_exchange = false;
     int frames = 1, frames_after = 0;
+    bool have_frames = false;
     std::vector<int> devices;
     std::vector<std::string> requests;
     std::string dump_raw;
@@ -112,7 +117,7 @@ int main(int argc, char* argv[])
         else if (a == "--viewer") viewer = true;
         else if (a == "--threaded") threaded = true;
         else if (a == "--self-exchange") self_exchange = true;
-        else if (a == "--frames") frames = std::atoi(next());
+        else if (a == "--frames") { frames = std::atoi(next()); have_frames = true; }
         else if (a == "--frames-after") frames_after = std::atoi(next());
         else if (a == "--request") requests.push_back(next());
         else if (a == "--dump-raw") dump_raw = next();
@@ -128,6 +133,7 @@ int main(int argc, char* argv[])
         else if (a[0] != '-') spp = std::atoi(a.c_str());
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (denoise_levels >= 0 && have_frames && frames < 2) { std::fprintf(stderr, "--denoise [LEVELS] --frames N: N >= 2\n"); return 2; }
     try {
         Scene scene = scene_path.empty() ? cornell9() : (scene_path == "shipped-meshes" ? shipped_two_sphere_mesh_scene() : load_scene_file(scene_path));
         if (have_env) scene.environment = make_float3(env[0], env[1], env[2]);
@@ -241,6 +247,32 @@ int main(int argc, char* argv[])
         }
         Renderer renderer(device);
         upload(renderer);
+        if (denoise_levels >= 0 && have_frames) {
+            // the render thread's loop for `frames` frames with moments and the four guides, then the variance-guided snapshot
+            const uint32_t spp_frame = (uint32_t)samps * 4u;
+            renderer.progressiveBegin((size_t)w, (size_t)h);
+            renderer.progressiveAovBegin(SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE);
+            renderer.progressiveMomentsBegin();
+            for (int f = 0; f < frames; ++f) {
+                renderer.progressiveFrame(cam, (size_t)samps, (size_t)seed + (size_t)f, f == 0);
+                renderer.progressiveAovFrame(cam, (size_t)samps, (size_t)seed + (size_t)f, f == 0);
+            }
+            spt_denoise_var_params dp;
+            spt_denoise_var_params_default(&dp);
+            if (denoise_levels > 0) dp.levels = (uint32_t)denoise_levels;
+            std::vector<float3> c((size_t)w * h);
+            renderer.progressiveDenoisedVarSnapshot((size_t)frames * spp_frame, c, &dp);
+            renderer.progressiveEnd();
+            const float inv = 1.0f / (float)((uint32_t)frames * spp_frame);
+            for (float3& px : c) { px.x *= inv; px.y *= inv; px.z *= inv; }
+            const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
+            std::fprintf(stderr, "Rendering (%d frames of %u spp) 100.00%%\nElapsed time: %lld ms\n", frames, spp_frame, (long long)ms);
+            if (spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(c.data()), (uint32_t)w, (uint32_t)h)) {
+                std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
+                return 1;
+            }
+            return 0;
+        }
         renderer.setOneShot(true);                               // cpuRender renders its view once
         std::vector<std::vector<float3>> set;
         if (aov_mask) set = renderer.renderAovSet(cam, (size_t)w, (size_t)h, (size_t)samps, (size_t)seed, aov_mask, /*normalise=*/true);

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SptCamera, SptDenoiseParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
+from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
 from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
@@ -182,6 +182,32 @@ class DenoiseParams:
 
 def _denoise_params(params):
     return (params if params is not None else DenoiseParams()).as_c()
+
+
+class DenoiseVarParams:
+    """Parameters of the variance-guided filter (spt_denoise_var_params): those of ``DenoiseParams`` and ``sigma_colour`` (finite, >= 0),
+    the strength of the luminance edge-stopping term; 0 gives ``denoise`` bit for bit.  None takes spt_denoise_var_params_default."""
+    FIELDS = DenoiseParams.FIELDS + ("sigma_colour",)
+
+    def __init__(self, levels=None, sigma_normal=None, sigma_plane=None, sigma_albedo=None, sigma_coverage=None, sigma_colour=None):
+        c = SptDenoiseVarParams()
+        load_library().spt_denoise_var_params_default(C.byref(c))
+        given = (levels, sigma_normal, sigma_plane, sigma_albedo, sigma_coverage, sigma_colour)
+        for name, v in zip(self.FIELDS, given):
+            setattr(self, name, getattr(c, name) if v is None else (int(v) if name == "levels" else float(v)))
+
+    def as_c(self):
+        c = SptDenoiseVarParams()
+        for name in self.FIELDS:
+            setattr(c, name, getattr(self, name))
+        return c
+
+    def __repr__(self):
+        return "DenoiseVarParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.FIELDS) + ")"
+
+
+def _denoise_var_params(params):
+    return (params if params is not None else DenoiseVarParams()).as_c()
 
 
 class SptError(RuntimeError):
@@ -623,15 +649,58 @@ class Renderer:
         self._check(self._lib.spt_denoise_device(self._h, *[C.c_void_p(t.data_ptr()) for t in ts[:5]], w, h, int(aov_samples), C.byref(p),
                                                  C.c_void_p(out_t.data_ptr()), C.c_void_p(stream) if stream else None))
 
+    def denoise_var(self, beauty, normal, albedo, position, coverage, m2, aov_samples, frames, params=None):
+        """Variance-guided filter (spt_denoise_var): ``denoise`` with ``m2`` = (h, w) float32, the sum over ``frames`` >= 2 frames of the
+        squared frame luminance (``progressive_begin(..., moments=True)`` / ``accumulate_moments_device``), ``beauty`` being the sum of
+        the same frames.  Returns the filtered un-normalised sum, (h, w, 3) float32."""
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (beauty, normal, albedo, position, coverage)]
+        m2 = np.ascontiguousarray(m2, dtype=np.float32)
+        if imgs[0].ndim != 3 or imgs[0].shape[2] != 3 or any(a.shape != imgs[0].shape for a in imgs) or m2.shape != imgs[0].shape[:2]:
+            raise ValueError("denoise_var: five (h, w, 3) images and one (h, w) image of one size")
+        h, w, _ = imgs[0].shape
+        out = np.empty((h, w, 3), dtype=np.float32)
+        p = _denoise_var_params(params)
+        self._check(self._lib.spt_denoise_var(self._h, *[a.ctypes.data_as(C.c_void_p) for a in imgs], m2.ctypes.data_as(C.c_void_p), w, h,
+                                              int(aov_samples), int(frames), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoise_var_device(self, beauty_t, normal_t, albedo_t, position_t, coverage_t, m2_t, out_t, w, h, aov_samples, frames, params=None,
+                           stream=None):
+        """The same on contiguous float32 CUDA tensors (spt_denoise_var_device): w*h*3 elements each, ``m2_t`` w*h; asynchronous on
+        ``stream`` (a raw hipStream_t, None = the context's stream).  ``out_t`` may not alias an input."""
+        ts = (beauty_t, normal_t, albedo_t, position_t, coverage_t, out_t, m2_t)
+        for t, n in zip(ts, (w * h * 3,) * 6 + (w * h,)):
+            if t.numel() != n or not t.is_contiguous() or str(t.dtype) != "torch.float32" or t.device.type != "cuda":
+                raise ValueError("denoise_var_device: contiguous float32 tensors of w*h*3 (m2_t: w*h) elements on the GPU")
+        p = _denoise_var_params(params)
+        self._check(self._lib.spt_denoise_var_device(self._h, *[C.c_void_p(t.data_ptr()) for t in ts[:5]], C.c_void_p(m2_t.data_ptr()), w, h,
+                                                     int(aov_samples), int(frames), C.byref(p), C.c_void_p(out_t.data_ptr()),
+                                                     C.c_void_p(stream) if stream else None))
+
+    def accumulate_moments_device(self, accum_t, m2_t, frame_t, clear=False, stream=None):
+        """accum (``clear``: =, else +=) frame and m2 (=, +=) the squared luminance of frame, one kernel (spt_accumulate_moments_device):
+        contiguous float32 CUDA tensors, ``accum_t`` and ``frame_t`` of npix*3 elements and 16-byte aligned, ``m2_t`` of npix elements.
+        Asynchronous on ``stream`` (a raw hipStream_t, None = the context's stream)."""
+        npix = m2_t.numel()
+        for t, n in ((accum_t, npix * 3), (frame_t, npix * 3), (m2_t, npix)):
+            if t.numel() != n or not t.is_contiguous() or str(t.dtype) != "torch.float32" or t.device.type != "cuda":
+                raise ValueError("accumulate_moments_device: contiguous float32 tensors of npix*3, npix and npix*3 elements on the GPU")
+        self._check(self._lib.spt_accumulate_moments_device(self._h, C.c_void_p(accum_t.data_ptr()), C.c_void_p(m2_t.data_ptr()),
+                                                            C.c_void_p(frame_t.data_ptr()), npix, 1 if clear else 0,
+                                                            C.c_void_p(stream) if stream else None))
+
     # The render thread's loop behind the C-ABI (spt_progressive_*): radiance and feature accumulators resident on the device.
-    def progressive_begin(self, w, h, aov_kinds=None):
-        """spt_progressive_begin, and spt_progressive_aov_begin for ``aov_kinds`` (names as ``render_aov_set``) when given."""
+    def progressive_begin(self, w, h, aov_kinds=None, moments=False):
+        """spt_progressive_begin, spt_progressive_aov_begin for ``aov_kinds`` (names as ``render_aov_set``) when given, and
+        spt_progressive_moments_begin when ``moments``: the loop then also sums the frames' squared luminance per pixel."""
         self._check(self._lib.spt_progressive_begin(self._h, w, h))
         self._prog = (w, h, ())
         if aov_kinds is not None:
             mask, names = _aov_set(aov_kinds)
             self._check(self._lib.spt_progressive_aov_begin(self._h, mask))
             self._prog = (w, h, tuple(names))
+        if moments:
+            self._check(self._lib.spt_progressive_moments_begin(self._h))
 
     def progressive_frame(self, samps_per_cell, seed, clear=False, camera=None):
         """One radiance frame added to (``clear``: replacing) accumBuffer; blocking.  Returns the stats."""
@@ -667,6 +736,24 @@ class Renderer:
         out = np.empty((h, w, 3), dtype=np.float32)
         p = _denoise_params(params)
         self._check(self._lib.spt_progressive_denoised_snapshot(self._h, int(aov_samples), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def progressive_variance_snapshot(self):
+        """((h, w) float32, frames): the biased variance estimate of one frame's luminance per pixel and the frames accumulated since the
+        last clearing frame (spt_progressive_variance_snapshot); needs ``progressive_begin(..., moments=True)`` and a clearing frame."""
+        w, h, _ = self._prog_size("progressive_variance_snapshot")
+        out = np.empty((h, w), dtype=np.float32)
+        n = C.c_uint32(0)
+        self._check(self._lib.spt_progressive_variance_snapshot(self._h, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out, int(n.value)
+
+    def progressive_denoised_var_snapshot(self, aov_samples, params=None):
+        """accumBuffer under the variance-guided filter (spt_progressive_denoised_var_snapshot): ``progressive_denoised_snapshot`` with
+        the loop's second moments; needs ``moments=True``, a clearing frame and at least two frames since."""
+        w, h, _ = self._prog_size("progressive_denoised_var_snapshot")
+        out = np.empty((h, w, 3), dtype=np.float32)
+        p = _denoise_var_params(params)
+        self._check(self._lib.spt_progressive_denoised_var_snapshot(self._h, int(aov_samples), C.byref(p), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def progressive_end(self):
