@@ -35,6 +35,10 @@
  *   accumBuffer += outImage under accumBufferMutex and the      spt_progressive_begin / _frame / _snapshot / _end
  *     GL thread's copy of it (smallpt.cpp:881-883,924-940,       (accumulation buffer resident in HBM)
  *     955-959)
+ *   drawWeightedRGBImage(image, w, h, weight3): the weighted    spt_display / spt_display_device /
+ *     image as 8-bit colour (smallpt.cpp:953-962,                spt_progressive_display_snapshot (on the device,
+ *     glutils.cpp:230-256) and toInt per channel before the      bit-exact to toInt), spt_write_ppm_rgb8
+ *     PPM (smallpt.cpp:52,136-142)
  *   "Elapsed time" stderr line (smallpt.cpp:371-373,809-811)    spt_stats
  *   CHK_PRIME / rtpContextGetLastErrorString                    int status + spt_last_error()
  *     (smallpt.cpp:381-393)
@@ -624,6 +628,71 @@ int  spt_sync(spt_ctx* ctx, spt_stats* stats);
  * ASCII P3 writer (:136-142).  rgb is w*h*3 floats, row 0 = bottom; the file gets the flipped image. */
 int  spt_to_int(float x);
 int  spt_write_ppm(const char* path, const float* rgb, uint32_t w, uint32_t h);
+
+/* 8-bit display transform on the device (csrc/spt_display.hip): the last step of the reference's pipeline -- the GL thread hands accumBuffer
+ * and weight3 to drawWeightedRGBImage, which shows image * weight as 8-bit colour (smallpt.cpp:953-962, glutils.cpp:230-256), and the file
+ * output pushes every channel through toInt (smallpt.cpp:52, :136-142) -- without the 12 bytes per pixel of float sums crossing the host
+ * link and without a pow per channel on the host.
+ *   Contract per pixel p and channel j of a w*h packed-float3 un-normalised sum image S (row 0 = bottom):
+ *       v = S[p][j] * weight[j]          one float32 multiply, no contraction
+ *       q = number of k in 1..255 with T[k] <= v      (float compare; NaN compares false everywhere, so NaN -> 0)
+ *     where T[k] is the smallest float32 with spt_to_int >= k.  Hence -0, negatives and NaN give 0; values >= T[255], including everything
+ *     above 1 and +inf, give 255; and q == spt_to_int(v) for every non-NaN float32 v.  spt_to_int(NaN) is undefined behaviour on the host
+ *     (an int conversion of NaN); this contract DEFINES NaN as 0.  inf * 0 is NaN and therefore 0.
+ *   Why a table is exact: spt_to_int is non-decreasing over the float32 values and rises exactly 255 times between 0 and 1, so the 255
+ *     thresholds describe it completely and the device needs no transcendental: it counts, by an 8-step binary search over the table
+ *     staged in LDS.  The table is built once per process with spt_to_int itself (bisection on the bit patterns of [0, 1]) and verified:
+ *     spt_to_int(T[k]) == k, spt_to_int(the float below T[k]) == k - 1, T strictly increasing; a failed verification (a non-monotone libm)
+ *     fails the calling entry point with a message.  tools/verify_display_table.cpp walks every float32 of [0, 1].
+ *   format: SPT_DISPLAY_RGB8 = 3 bytes per pixel (r, g, b); SPT_DISPLAY_RGBA8 = 4 bytes per pixel, alpha = 255.
+ *   flags: SPT_DISPLAY_FLIP_Y: output row r is image row h-1-r (flipY, smallpt.cpp:125-134: top row first, the order of a PPM body and of
+ *     most window systems); without it the rows stay bottom-first (GL's order).
+ *   spt_display_device: d_rgb_sum (w*h*3 floats, 4-byte aligned) and d_out8 (w*h*3 or w*h*4 bytes, any alignment) on this context's device;
+ *     enqueued on `hip_stream` (NULL = the context's stream), returns without waiting.  A 16-byte aligned input and a 4-byte (RGB8) or
+ *     16-byte (RGBA8) aligned output take the four-pixels-per-thread form (with FLIP_Y when also w % 4 == 0), anything else one pixel per
+ *     thread; the bytes are the same.  Device calls share only the read-only table, so they are ordered by their streams alone.
+ *   spt_display: host buffers, blocking.  The host forms and the snapshot run on the context's stream in call order; their 8-bit device
+ *     image belongs to the context, is grown on demand and freed by spt_destroy and spt_progressive_end; a failed allocation fails the call
+ *     and leaves the context usable.
+ *   spt_progressive_display_snapshot(owner, filter, aov_samples, filter_params, params, out8): waits like spt_progressive_snapshot, runs
+ *     the selected filter (if any) into the context's scratch and the display kernel after it, and copies only w*h*(3|4) bytes to the host.
+ *       SPT_DISPLAY_SRC_ACCUM         the radiance accumBuffer; filter_params must be NULL, aov_samples is ignored;
+ *       SPT_DISPLAY_SRC_DENOISED      filter_params = spt_denoise_params*; preconditions of spt_progressive_denoised_snapshot;
+ *       SPT_DISPLAY_SRC_DENOISED_VAR  filter_params = spt_denoise_var_params*; preconditions of spt_progressive_denoised_var_snapshot.
+ *     The caller supplies the weight 1/(sampleCount*sampleCountPerPixel) exactly as the reference does (:957-961).  The result is, byte for
+ *     byte, spt_display applied to the matching float snapshot.  It modifies no accumulator and no render state.
+ *   Failures (message in spt_last_error, nothing launched, nothing written): a NULL pointer; w or h of 0, or w*h above 2^31 - 1; an unknown
+ *     format, flag bit or filter; a weight that is negative or not finite; a d_rgb_sum that is not 4-byte aligned; filter_params given
+ *     with SPT_DISPLAY_SRC_ACCUM; the filter's own preconditions (its message is passed through).
+ *   Out of scope: other transfer curves (sRGB piecewise, filmic); dithering; the multi-GPU front; the async lanes. */
+#define SPT_DISPLAY_RGB8   0u
+#define SPT_DISPLAY_RGBA8  1u
+#define SPT_DISPLAY_FLIP_Y 1u
+enum { SPT_DISPLAY_SRC_ACCUM = 0, SPT_DISPLAY_SRC_DENOISED = 1, SPT_DISPLAY_SRC_DENOISED_VAR = 2 };
+typedef struct spt_display_params {
+    float    weight[3];   /* per channel, finite and >= 0 */
+    uint32_t format;      /* SPT_DISPLAY_RGB8 / SPT_DISPLAY_RGBA8 */
+    uint32_t flags;       /* SPT_DISPLAY_FLIP_Y or 0 */
+} spt_display_params;
+#if defined(__cplusplus)
+static_assert(sizeof(spt_display_params) == 20, "spt_display_params: 20 bytes");
+#else
+_Static_assert(sizeof(spt_display_params) == 20, "spt_display_params: 20 bytes");
+#endif
+/* Host-only: weight (1, 1, 1), SPT_DISPLAY_RGB8, no flip. */
+void spt_display_params_default(spt_display_params* params);
+int  spt_display_device(spt_ctx* ctx, const void* d_rgb_sum, uint32_t w, uint32_t h, const spt_display_params* params, void* d_out8,
+                        void* hip_stream);
+int  spt_display(spt_ctx* ctx, const float* rgb_sum, uint32_t w, uint32_t h, const spt_display_params* params, uint8_t* out8);
+int  spt_progressive_display_snapshot(spt_ctx* owner, uint32_t filter, uint32_t aov_samples, const void* filter_params,
+                                      const spt_display_params* params, uint8_t* out8);
+/* Host-only: the 255 thresholds T[1..255] (0 = ok; non-zero when the verification above failed). */
+int  spt_display_thresholds(float out[255]);
+/* Host-only: out[i] = the table count of v[i] on the CPU, the arithmetic of the device's search without the multiply (0 = ok). */
+int  spt_display_quantise_host(const float* v, uint64_t n, uint8_t* out);
+/* Host-only: the ASCII P3 file of spt_write_ppm for an image that is already RGB8 and top row first (what spt_display writes with
+ * SPT_DISPLAY_RGB8 | SPT_DISPLAY_FLIP_Y): spt_write_ppm(rgb) and spt_write_ppm_rgb8(display of rgb) produce the same bytes. */
+int  spt_write_ppm_rgb8(const char* path, const uint8_t* rgb8_top_first, uint32_t w, uint32_t h);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,10 @@ class SptDenoiseVarParams(C.Structure):
                 ("sigma_coverage", C.c_float), ("sigma_colour", C.c_float)]
 
 
+class SptDisplayParams(C.Structure):  # spt_display_params: 20 bytes
+    _fields_ = [("weight", C.c_float * 3), ("format", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class SptInstance(C.Structure):      # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
     _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
 
@@ -121,6 +125,13 @@ SYMBOLS = {
     "spt_sync": (C.c_int, [_P, C.POINTER(SptStats)]),
     "spt_to_int": (C.c_int, [C.c_float]),
     "spt_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_uint32, C.c_uint32]),
+    "spt_display_params_default": (None, [C.POINTER(SptDisplayParams)]),
+    "spt_display_device": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(SptDisplayParams), _P, _P]),
+    "spt_display": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(SptDisplayParams), _P]),
+    "spt_progressive_display_snapshot": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.POINTER(SptDisplayParams), _P]),
+    "spt_display_thresholds": (C.c_int, [_P]),
+    "spt_display_quantise_host": (C.c_int, [_P, C.c_uint64, _P]),
+    "spt_write_ppm_rgb8": (C.c_int, [C.c_char_p, _P, C.c_uint32, C.c_uint32]),
 }
 
 # test / tuning hooks declared in csrc/spt_internal.h (not part of the drop-in boundary)

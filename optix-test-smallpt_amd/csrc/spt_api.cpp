@@ -11,6 +11,7 @@
 #include "spt_instance.h"
 #include "spt_denoise.h"
 #include "spt_denoise_var.h"
+#include "spt_display.h"
 
 #include <chrono>
 #include <cmath>
@@ -138,6 +139,10 @@ struct spt_ctx {
     int denoise_form = 0;          // spt_set_denoise_form (spt_internal.h): 1 = the direct-load pass at every step
     bool denoise_timed = false;    // spt_set_denoise_timing: events around every kernel of a filter call (spt_denoise_last_ms)
     hipEvent_t dn_ev[7] = {}; uint32_t dn_ev_count = 0;
+    // spt_display*: the threshold table {T[1..255], +inf} on the device (uploaded by the first display call, kept until spt_destroy) and the
+    // 8-bit image of the host forms and the snapshot, grown on demand (they run on the context's stream and block, so nothing else reads it)
+    float* d_disp_table = nullptr;
+    uint8_t* d_disp8 = nullptr; size_t disp8_cap = 0;
     hipEvent_t ev_acc = nullptr;   // owner of an accumBuffer: completion of the most recent accumulation (any lane's stream)
     bool acc_recorded = false;
     bool frame_in_flight = false;  // a spt_progressive_frame_async of this lane has not been waited for
@@ -273,6 +278,12 @@ static void denoise_free(spt_ctx* c)
     c->dn_guides_cap = c->dn_ping_cap = c->dn_pong_cap = c->dn_out_cap = 0;
 }
 
+static void display_free(spt_ctx* c)
+{
+    if (c->d_disp8) (void)hipFree(c->d_disp8);
+    c->d_disp8 = nullptr; c->disp8_cap = 0;
+}
+
 static void moments_free(spt_ctx* c)
 {
     if (c->d_m2) (void)hipFree(c->d_m2);
@@ -305,6 +316,8 @@ void spt_destroy(spt_ctx* c)
     progressive_aov_free(c);
     moments_free(c);
     denoise_free(c);
+    display_free(c);
+    if (c->d_disp_table) (void)hipFree(c->d_disp_table);
     if (c->ev_denoise) (void)hipEventDestroy(c->ev_denoise);
     for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
     if (c->d_tris) (void)hipFree(c->d_tris);
@@ -2255,6 +2268,7 @@ int spt_progressive_end(spt_ctx* c)
     if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));   // a filter a caller's stream still runs
     c->denoise_recorded = false;
     denoise_free(c);
+    display_free(c);
     c->prog_w = c->prog_h = 0;
     c->acc_recorded = false;
     c->frame_in_flight = false;
@@ -2587,11 +2601,10 @@ int spt_denoise(spt_ctx* c, const float* beauty, const float* normal, const floa
     return 0;
 }
 
-// The two filtered snapshots of the progressive loop: vp == nullptr is the guide-only filter under *p
-static int progressive_denoised(spt_ctx* c, const char* who, uint32_t aov_samples, const spt_denoise_params* p, const spt_denoise_var_params* vp,
-                                float* out_rgb)
+// The two filters of the progressive loop, enqueued on the context's stream into d_dn_out (w*h*3 floats) behind every accumulation issued
+// so far: vp == nullptr is the guide-only filter under *p
+static int progressive_denoised_enqueue(spt_ctx* c, const char* who, uint32_t aov_samples, const spt_denoise_params* p, const spt_denoise_var_params* vp)
 {
-    if (!c->d_accum || !out_rgb) return c->fail("%s: no accumulation buffer or out_rgb is NULL", who);
     const uint32_t need = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE, missing = need & ~c->aov_mask;
     if (missing)
         return c->fail("%s: spt_progressive_aov_begin has not selected%s%s%s%s", who, (missing & SPT_AOVSET_NORMAL) ? " NORMAL" : "",
@@ -2612,7 +2625,16 @@ static int progressive_denoised(spt_ctx* c, const char* who, uint32_t aov_sample
     if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
     if (int rc = denoise_enqueue(c, who, c->d_accum, c->d_aov_accum[SPT_AOV_NORMAL], c->d_aov_accum[SPT_AOV_ALBEDO], c->d_aov_accum[4], c->d_aov_accum[5],
                                  c->prog_w, c->prog_h, aov_samples, p, c->d_dn_out, c->stream, vp ? c->d_m2 : nullptr, c->m2_frames, vp ? vp->sigma_colour : 0.f)) return rc;
-    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_dn_out, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+// The two filtered snapshots
+static int progressive_denoised(spt_ctx* c, const char* who, uint32_t aov_samples, const spt_denoise_params* p, const spt_denoise_var_params* vp,
+                                float* out_rgb)
+{
+    if (!c->d_accum || !out_rgb) return c->fail("%s: no accumulation buffer or out_rgb is NULL", who);
+    if (int rc = progressive_denoised_enqueue(c, who, aov_samples, p, vp)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_dn_out, (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2671,6 +2693,98 @@ int spt_denoise_var(spt_ctx* c, const float* beauty, const float* normal, const 
     SPT_HIP(c, hipMemcpyAsync(out, d + 5 * pitch, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// ---- 8-bit display transform (spt_display.hip; the contract is stated in include/smallpt_mi355x.h) ----
+static int display_check(spt_ctx* c, const char* who, uint32_t w, uint32_t h, const spt_display_params* p)
+{
+    if (!p) return c->fail("%s: NULL argument", who);
+    if (w == 0 || h == 0) return c->fail("%s: empty image", who);
+    if ((uint64_t)w * h > 0x7FFFFFFFull) return c->fail("%s: w*h exceeds 2^31-1 pixels", who);
+    if (p->format != SPT_DISPLAY_RGB8 && p->format != SPT_DISPLAY_RGBA8) return c->fail("%s: format = %u is neither SPT_DISPLAY_RGB8 nor SPT_DISPLAY_RGBA8", who, p->format);
+    if (p->flags & ~SPT_DISPLAY_FLIP_Y) return c->fail("%s: flags = 0x%x has bits beyond SPT_DISPLAY_FLIP_Y", who, p->flags);
+    for (int j = 0; j < 3; ++j)
+        if (!std::isfinite(p->weight[j]) || p->weight[j] < 0.f) return c->fail("%s: weight[%d] = %g is negative or not finite", who, j, (double)p->weight[j]);
+    return 0;
+}
+
+// Device set.  The verified table of this process on the context's device: built and uploaded by the first call
+static int display_table(spt_ctx* c, const char* who)
+{
+    if (c->d_disp_table) return 0;
+    char msg[256];
+    const float* t = spt_display_table(msg, sizeof msg);
+    if (!t) return c->fail("%s: %s", who, msg);
+    float* d = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), SPT_DISPLAY_TABLE * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d, t, SPT_DISPLAY_TABLE * sizeof(float), hipMemcpyHostToDevice);   // blocking: in place before any stream reads it
+    if (e != hipSuccess) { (void)hipGetLastError(); if (d) (void)hipFree(d); return c->fail("%s: threshold table: %s", who, hipGetErrorString(e)); }
+    c->d_disp_table = d;
+    return 0;
+}
+
+static size_t display_bytes(uint32_t w, uint32_t h, const spt_display_params* p) { return (size_t)w * h * (p->format == SPT_DISPLAY_RGBA8 ? 4 : 3); }
+
+// Validated arguments, device set, table present: d_sum -> the context's 8-bit image on its stream -> out8 (host); blocking
+static int display_to_host(spt_ctx* c, const char* who, const float* d_sum, uint32_t w, uint32_t h, const spt_display_params* p, uint8_t* out8)
+{
+    const size_t bytes = display_bytes(w, h, p);
+    const hipError_t e = grow(c->d_disp8, c->disp8_cap, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: 8-bit image of %u x %u pixels: %s", who, w, h, hipGetErrorString(e)); }
+    SPT_HIP(c, spt_display_launch(d_sum, c->d_disp_table, w, h, p->weight, p->format == SPT_DISPLAY_RGBA8 ? 4 : 3, (p->flags & SPT_DISPLAY_FLIP_Y) != 0, c->d_disp8, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(out8, c->d_disp8, bytes, hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int spt_display_device(spt_ctx* c, const void* d_rgb_sum, uint32_t w, uint32_t h, const spt_display_params* p, void* d_out8, void* hip_stream)
+{
+    if (!c) return 1;
+    if (!d_rgb_sum || !d_out8) return c->fail("spt_display_device: NULL argument");
+    if (int rc = display_check(c, "spt_display_device", w, h, p)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_rgb_sum) & 3u) return c->fail("spt_display_device: d_rgb_sum must be 4-byte aligned");
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (int rc = display_table(c, "spt_display_device")) return rc;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    SPT_HIP(c, spt_display_launch(static_cast<const float*>(d_rgb_sum), c->d_disp_table, w, h, p->weight, p->format == SPT_DISPLAY_RGBA8 ? 4 : 3,
+                                  (p->flags & SPT_DISPLAY_FLIP_Y) != 0, static_cast<uint8_t*>(d_out8), st));
+    return 0;
+}
+
+int spt_display(spt_ctx* c, const float* rgb_sum, uint32_t w, uint32_t h, const spt_display_params* p, uint8_t* out8)
+{
+    if (!c) return 1;
+    if (!rgb_sum || !out8) return c->fail("spt_display: NULL argument");
+    if (int rc = display_check(c, "spt_display", w, h, p)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (int rc = display_table(c, "spt_display")) return rc;
+    const size_t nfl = (size_t)w * h * 3;
+    if (grow_out(c, nfl)) return 1;
+    SPT_HIP(c, hipMemcpyAsync(c->d_out, rgb_sum, nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return display_to_host(c, "spt_display", c->d_out, w, h, p, out8);
+}
+
+int spt_progressive_display_snapshot(spt_ctx* c, uint32_t filter, uint32_t aov_samples, const void* filter_params, const spt_display_params* p, uint8_t* out8)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_display_snapshot";
+    if (!c->d_accum || !out8) return c->fail("%s: no accumulation buffer or out8 is NULL", who);
+    if (filter > SPT_DISPLAY_SRC_DENOISED_VAR) return c->fail("%s: filter = %u is none of SPT_DISPLAY_SRC_ACCUM, _DENOISED, _DENOISED_VAR", who, filter);
+    if (filter == SPT_DISPLAY_SRC_ACCUM && filter_params) return c->fail("%s: SPT_DISPLAY_SRC_ACCUM takes no filter_params", who);
+    if (filter != SPT_DISPLAY_SRC_ACCUM && !filter_params) return c->fail("%s: NULL argument (filter_params)", who);
+    if (int rc = display_check(c, who, c->prog_w, c->prog_h, p)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (int rc = display_table(c, who)) return rc;
+    const float* src = c->d_accum;
+    if (filter == SPT_DISPLAY_SRC_ACCUM) {
+        if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
+    } else {
+        const bool var = filter == SPT_DISPLAY_SRC_DENOISED_VAR;
+        if (int rc = progressive_denoised_enqueue(c, who, aov_samples, var ? nullptr : static_cast<const spt_denoise_params*>(filter_params),
+                                                  var ? static_cast<const spt_denoise_var_params*>(filter_params) : nullptr)) return rc;
+        src = c->d_dn_out;
+    }
+    return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);
 }
 
 // Test / measurement hook (spt_internal.h)
@@ -2819,13 +2933,6 @@ int spt_selftest_range(spt_ctx* c, int op, uint32_t first, uint32_t count, uint6
     *mismatches = out[0];
     *first_bad = (uint32_t)out[1];
     return 0;
-}
-
-// smallpt.cpp:52
-int spt_to_int(float x)
-{
-    const float cl = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);
-    return (int)(std::pow((double)cl, 1 / 2.2) * 255 + .5);
 }
 
 // flipY (smallpt.cpp:125-134) + writeImage (smallpt.cpp:136-142); unlike the reference the file is closed.

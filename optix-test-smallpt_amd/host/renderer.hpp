@@ -136,6 +136,31 @@ public:
         check(spt_progressive_denoised_var_snapshot(ctx_, (uint32_t)aovSamples, &p, reinterpret_cast<float*>(image.data())));
     }
 
+    // 8-bit display transform on the device (spt_display): drawWeightedRGBImage's image * weight through toInt (smallpt.cpp:52,953-962,
+    // glutils.cpp:230-256), bit-exact; rgbSum = an un-normalised sum, row 0 = bottom.  Returns w*h*3 (SPT_DISPLAY_RGB8) or w*h*4
+    // (SPT_DISPLAY_RGBA8, alpha 255) bytes, top row first with SPT_DISPLAY_FLIP_Y.  params = nullptr: spt_display_params_default.
+    std::vector<uint8_t> display(const std::vector<float3>& rgbSum, size_t imageWidth, size_t imageHeight, const spt_display_params* params = nullptr)
+    {
+        if (rgbSum.size() != imageWidth * imageHeight) throw std::runtime_error("display: an image of imageWidth * imageHeight pixels");
+        spt_display_params p;
+        if (params) p = *params; else spt_display_params_default(&p);
+        std::vector<uint8_t> out(imageWidth * imageHeight * (p.format == SPT_DISPLAY_RGBA8 ? 4 : 3));
+        check(spt_display(ctx_, reinterpret_cast<const float*>(rgbSum.data()), (uint32_t)imageWidth, (uint32_t)imageHeight, &p, out.data()));
+        return out;
+    }
+    // the same on device buffers of this context's device, enqueued on `hipStream` (nullptr: the context's stream) without waiting
+    void displayDevice(const void* dRgbSum, size_t imageWidth, size_t imageHeight, const spt_display_params& params, void* dOut8, void* hipStream = nullptr)
+    {
+        check(spt_display_device(ctx_, dRgbSum, (uint32_t)imageWidth, (uint32_t)imageHeight, &params, dOut8, hipStream));
+    }
+    // ... and as a snapshot of the progressive loop (spt_progressive_display_snapshot): accumBuffer (SPT_DISPLAY_SRC_ACCUM, filterParams =
+    // nullptr) or one of its filtered forms (spt_denoise_params* / spt_denoise_var_params*) as 8-bit colour; image must hold w*h*(3|4) bytes
+    void progressiveDisplaySnapshot(std::vector<uint8_t>& image, const spt_display_params& params, uint32_t filter = SPT_DISPLAY_SRC_ACCUM,
+                                    size_t aovSamples = 0, const void* filterParams = nullptr)
+    {
+        check(spt_progressive_display_snapshot(ctx_, filter, (uint32_t)aovSamples, filterParams, &params, image.data()));
+    }
+
     // accumBuffer of the viewer loop in HBM (spt_progressive_*, smallpt.cpp:881-883,922-937,955-959)
     void progressiveBegin(size_t w, size_t h) { check(spt_progressive_begin(ctx_, (uint32_t)w, (uint32_t)h)); }
     void progressiveFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool clear)

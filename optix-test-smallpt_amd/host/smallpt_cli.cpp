@@ -19,6 +19,9 @@
 //                                                              spt_progressive_denoised_var_snapshot (variance-guided, default parameters);
 //                                                              --out gets the filtered sum divided by N * spp
 //                  [--devices 0,1,...] [--self-exchange]      row bands over several GPUs + RCCL exchange (MultiRenderer)
+//                  [--display-device]                             every PPM goes through the device's 8-bit display transform (spt_display, or
+//                                                              spt_progressive_display_snapshot for --viewer) and spt_write_ppm_rgb8 instead
+//                                                              of the host's toInt loop in spt_write_ppm: the same file
 //                  [--env r,g,b] [--print-environment]         radiance of escaped paths (overrides the scene file's "environment"); print it
 //                                                              as loaded and overridden, then exit (host only)
 //   smallpt_mi355x [spp] --viewer [--frames N] [--request JSON] [--frames-after M] [--threaded] [--org x,y,z]
@@ -69,6 +72,7 @@ int main(int argc, char* argv[])
     bool have_org = false;
     float env[3] = {0, 0, 0};
     bool have_env = false, print_env = false;
+    bool display_device = false;                   // --display-device
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value after %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -129,6 +133,7 @@ int main(int argc, char* argv[])
             have_env = true;
         }
         else if (a == "--print-environment") print_env = true;
+        else if (a == "--display-device") display_device = true;
         else if (a == "--devices") { const char* p = next(); while (*p) { devices.push_back((int)std::strtol(p, const_cast<char**>(&p), 10)); if (*p == ',') ++p; } }
         else if (a[0] != '-') spp = std::atoi(a.c_str());
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
@@ -151,6 +156,16 @@ int main(int argc, char* argv[])
             std::ofstream f(dump_path);
             f << scene_to_json(scene) << "\n";
         }
+        // writeImage: the host's toInt loop, or with --display-device the device's transform of the same normalised image (weight 1, top row
+        // first) and the 8-bit writer; 0 = written
+        auto write_image = [&](Renderer* rr, const std::string& path, const std::vector<float3>& image) -> int {
+            if (!display_device) return spt_write_ppm(path.c_str(), reinterpret_cast<const float*>(image.data()), (uint32_t)w, (uint32_t)h);
+            spt_display_params dp;
+            spt_display_params_default(&dp);
+            dp.flags = SPT_DISPLAY_FLIP_Y;
+            const std::vector<uint8_t> rgb8 = rr->display(image, (size_t)w, (size_t)h, &dp);
+            return spt_write_ppm_rgb8(path.c_str(), rgb8.data(), (uint32_t)w, (uint32_t)h);
+        };
         if (print_env) { std::printf("environment %.9g %.9g %.9g\n", scene.environment.x, scene.environment.y, scene.environment.z); return 0; }
         if (parse_only) {   // host-only path (no GPU): used by the CPU tests of the JSON loader
             const std::vector<spt_sphere> abi = to_abi(scene.spheres);
@@ -218,8 +233,16 @@ int main(int argc, char* argv[])
                 std::ofstream f(dump_raw, std::ios::binary);
                 f.write(reinterpret_cast<const char*>(image.data()), (std::streamsize)(image.size() * sizeof(float3)));
             }
-            const std::vector<float3> fin = prog.finalImage();                          // :995-1001
-            if (spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(fin.data()), (uint32_t)w, (uint32_t)h)) {   // :1003-1004
+            int wrc;
+            if (display_device) {                // accumBuffer * weight through toInt on the device, top row first: the exit path's file
+                std::vector<uint8_t> rgb8;
+                prog.snapshotDisplay(rgb8, SPT_DISPLAY_RGB8, /*flipY=*/true);
+                wrc = spt_write_ppm_rgb8(out_path.c_str(), rgb8.data(), (uint32_t)w, (uint32_t)h);
+            } else {
+                const std::vector<float3> fin = prog.finalImage();                      // :995-1001
+                wrc = spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(fin.data()), (uint32_t)w, (uint32_t)h);   // :1003-1004
+            }
+            if (wrc) {
                 std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
                 return 1;
             }
@@ -239,7 +262,8 @@ int main(int argc, char* argv[])
             std::fprintf(stderr, "Rendering (%d spp) 100.00%%\nElapsed time: %lld ms\n", samps * 4, (long long)ms);
             std::fprintf(stderr, "%u device(s): render %.3f ms, RCCL exchange %.3f ms, %.1f Msamples/s, %.3f bounces/sample\n", st.ndev,
                          st.render_ms, st.gather_ms, st.samples / (st.total_ms * 1e3), (double)st.bounces / (double)st.samples);
-            if (spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(c.data()), (uint32_t)w, (uint32_t)h)) {
+            std::unique_ptr<Renderer> shower(display_device ? new Renderer(devices[0]) : nullptr);   // the transform runs on the root device
+            if (write_image(shower.get(), out_path, c)) {
                 std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
                 return 1;
             }
@@ -267,7 +291,7 @@ int main(int argc, char* argv[])
             for (float3& px : c) { px.x *= inv; px.y *= inv; px.z *= inv; }
             const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
             std::fprintf(stderr, "Rendering (%d frames of %u spp) 100.00%%\nElapsed time: %lld ms\n", frames, spp_frame, (long long)ms);
-            if (spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(c.data()), (uint32_t)w, (uint32_t)h)) {
+            if (write_image(&renderer, out_path, c)) {
                 std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
                 return 1;
             }
@@ -303,12 +327,12 @@ int main(int argc, char* argv[])
             for (int k = 0; k < 6; ++k) {
                 if (!((aov_mask >> k) & 1u)) continue;
                 const std::string path = (ext ? out_path.substr(0, dot) : out_path) + "." + kAovNames[k] + (ext ? out_path.substr(dot) : std::string());
-                if (spt_write_ppm(path.c_str(), reinterpret_cast<const float*>(set[j++].data()), (uint32_t)w, (uint32_t)h)) {
+                if (write_image(&renderer, path, set[j++])) {
                     std::fprintf(stderr, "cannot write %s\n", path.c_str());
                     return 1;
                 }
             }
-        } else if (spt_write_ppm(out_path.c_str(), reinterpret_cast<const float*>(c.data()), (uint32_t)w, (uint32_t)h)) {  // :375-376
+        } else if (write_image(&renderer, out_path, c)) {  // :375-376
             std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
             return 1;
         }

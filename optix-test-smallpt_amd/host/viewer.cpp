@@ -141,6 +141,20 @@ void ProgressiveRenderer::snapshot(std::vector<float3>& image, float weight3[3])
     weight3[0] = weight3[1] = weight3[2] = weight;   // :961
 }
 
+void ProgressiveRenderer::snapshotDisplay(std::vector<uint8_t>& image, uint32_t format, bool flipY)
+{
+    std::unique_lock<std::mutex> l{accumMutex_};     // :956
+    const size_t sampleCountPerPixel = 4 * samps_;
+    const float weight = 1.f / (sampleCount_ * sampleCountPerPixel);   // :957
+    spt_display_params p;
+    spt_display_params_default(&p);
+    p.weight[0] = p.weight[1] = p.weight[2] = weight;                  // :961
+    p.format = format;
+    p.flags = flipY ? SPT_DISPLAY_FLIP_Y : 0u;
+    image.resize(w_ * h_ * (format == SPT_DISPLAY_RGBA8 ? 4 : 3));
+    renderer_.progressiveDisplaySnapshot(image, p);
+}
+
 std::vector<float3> ProgressiveRenderer::finalImage()
 {
     std::vector<float3> image;

@@ -6,7 +6,8 @@
 //     render(seed = sampleCount), accumBuffer (+)= outImage            for a deterministic single frame
 //   Vector<json> renderRequests + mutex (:889-891, :905-920)          postRequest(json text) -- {"action":"update_camera","org":[x,y,z]}
 //   GL loop: weight = 1/(sampleCount*sampleCountPerPixel), image =    snapshot(image, &weight3) -> hand to
-//     accumBuffer under the mutex, drawWeightedRGBImage (:955-962)      drawWeightedRGBImage(const float*, w, h, weight[3]) (glutils.h:153)
+//     accumBuffer under the mutex, drawWeightedRGBImage (:955-962)      drawWeightedRGBImage(const float*, w, h, weight[3]) (glutils.h:153),
+//                                                                       or snapshotDisplay(image8): the 8-bit picture made on the device
 //   keys UP/DOWN move org.y by 0.01 and post a request (:968-985)     moveCamera(dy)
 //   exit: accumBuffer /= sampleCount*spp, flipY, writeImage (:995-1004)  finalImage()
 //
@@ -62,6 +63,9 @@ public:
 
     // :955-959: copies accumBuffer and returns the display weight in weight3 (all three equal, :961)
     void snapshot(std::vector<float3>& image, float weight3[3]);
+    // the same picture as 8-bit colour straight from the device (spt_progressive_display_snapshot): image * weight through toInt, the
+    // weight computed as in snapshot() and under the same lock; format = SPT_DISPLAY_RGB8 / _RGBA8, flipY = top row first
+    void snapshotDisplay(std::vector<uint8_t>& image, uint32_t format = SPT_DISPLAY_RGB8, bool flipY = false);
     std::vector<float3> finalImage();               // :995-1001 (before flipY / writeImage)
     size_t sampleCount();                           // frames accumulated since the last clear
     size_t framesRendered() const { return framesRendered_; }

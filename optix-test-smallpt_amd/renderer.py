@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
+from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
 from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
@@ -208,6 +208,49 @@ class DenoiseVarParams:
 
 def _denoise_var_params(params):
     return (params if params is not None else DenoiseVarParams()).as_c()
+
+
+DISPLAY_RGB8, DISPLAY_RGBA8 = 0, 1
+DISPLAY_FLIP_Y = 1
+DISPLAY_SRC_ACCUM, DISPLAY_SRC_DENOISED, DISPLAY_SRC_DENOISED_VAR = 0, 1, 2
+
+
+class DisplayParams:
+    """Parameters of the 8-bit display transform (spt_display_params): ``weight`` (one number or three, each finite and >= 0: the
+    reference's 1/(sampleCount*sampleCountPerPixel)), ``format`` 'rgb8' or 'rgba8' (alpha = 255) and ``flip_y`` (top row first, the order
+    of a PPM body; default bottom row first, GL's order).  Defaults as spt_display_params_default: weight 1, rgb8, no flip."""
+    FORMATS = {"rgb8": DISPLAY_RGB8, "rgba8": DISPLAY_RGBA8}
+
+    def __init__(self, weight=None, format="rgb8", flip_y=False):
+        c = SptDisplayParams()
+        load_library().spt_display_params_default(C.byref(c))
+        if weight is None:
+            self.weight = tuple(float(v) for v in c.weight)
+        else:
+            wt = np.atleast_1d(np.asarray(weight, dtype=np.float32))
+            if wt.shape not in ((1,), (3,)):
+                raise ValueError("DisplayParams: weight is one number or three")
+            self.weight = tuple(float(v) for v in np.broadcast_to(wt, (3,)))
+        self.format = self.FORMATS[format] if isinstance(format, str) else int(format)
+        self.flags = DISPLAY_FLIP_Y if flip_y is True else int(flip_y)
+
+    @property
+    def channels(self):
+        return 4 if self.format == DISPLAY_RGBA8 else 3
+
+    def as_c(self):
+        c = SptDisplayParams()
+        c.weight[:] = self.weight
+        c.format = self.format
+        c.flags = self.flags
+        return c
+
+    def __repr__(self):
+        return f"DisplayParams(weight={self.weight!r}, format={self.format!r}, flags={self.flags!r})"
+
+
+def _display_params(params):
+    return params if params is not None else DisplayParams()
 
 
 class SptError(RuntimeError):
@@ -677,6 +720,36 @@ class Renderer:
                                                      int(aov_samples), int(frames), C.byref(p), C.c_void_p(out_t.data_ptr()),
                                                      C.c_void_p(stream) if stream else None))
 
+    def display(self, rgb_sum, params=None):
+        """8-bit display transform on the device (spt_display): q = toInt(rgb_sum * weight) per channel of an (h, w, 3) float32 image
+        (row 0 = bottom), bit-exact to toInt (NaN -> 0).  Returns uint8 (h, w, 3) or (h, w, 4) per ``params`` (a ``DisplayParams``)."""
+        img = np.ascontiguousarray(rgb_sum, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("display: one (h, w, 3) image")
+        h, w, _ = img.shape
+        dp = _display_params(params)
+        out = np.empty((h, w, dp.channels), dtype=np.uint8)
+        p = dp.as_c()
+        self._check(self._lib.spt_display(self._h, img.ctypes.data_as(C.c_void_p), w, h, C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def display_device(self, rgb_sum_t, w, h, params=None, out_t=None, stream=None):
+        """The same on a float32 CUDA tensor of w*h*3 elements (spt_display_device); asynchronous on ``stream`` (a raw hipStream_t, None =
+        the context's stream).  ``out_t``: a contiguous uint8 CUDA tensor of w*h*(3|4) elements (any alignment), allocated when None.
+        Returns ``out_t`` viewed as (h, w, 3|4)."""
+        dp = _display_params(params)
+        if rgb_sum_t.numel() != w * h * 3 or not rgb_sum_t.is_contiguous() or str(rgb_sum_t.dtype) != "torch.float32" or rgb_sum_t.device.type != "cuda":
+            raise ValueError("display_device: a contiguous float32 tensor of w*h*3 elements on the GPU")
+        if out_t is None:
+            import torch
+            out_t = torch.empty(w * h * dp.channels, dtype=torch.uint8, device=rgb_sum_t.device)
+        if out_t.numel() != w * h * dp.channels or not out_t.is_contiguous() or str(out_t.dtype) != "torch.uint8" or out_t.device.type != "cuda":
+            raise ValueError("display_device: out_t is a contiguous uint8 tensor of w*h*(3|4) elements on the GPU")
+        p = dp.as_c()
+        self._check(self._lib.spt_display_device(self._h, C.c_void_p(rgb_sum_t.data_ptr()), w, h, C.byref(p), C.c_void_p(out_t.data_ptr()),
+                                                 C.c_void_p(stream) if stream else None))
+        return out_t.view(h, w, dp.channels)
+
     def accumulate_moments_device(self, accum_t, m2_t, frame_t, clear=False, stream=None):
         """accum (``clear``: =, else +=) frame and m2 (=, +=) the squared luminance of frame, one kernel (spt_accumulate_moments_device):
         contiguous float32 CUDA tensors, ``accum_t`` and ``frame_t`` of npix*3 elements and 16-byte aligned, ``m2_t`` of npix elements.
@@ -754,6 +827,27 @@ class Renderer:
         out = np.empty((h, w, 3), dtype=np.float32)
         p = _denoise_var_params(params)
         self._check(self._lib.spt_progressive_denoised_var_snapshot(self._h, int(aov_samples), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def progressive_display_snapshot(self, params=None, source="accum", aov_samples=0, filter_params=None):
+        """The loop's picture as 8-bit colour straight from the device (spt_progressive_display_snapshot): ``source`` 'accum' (accumBuffer),
+        'denoised' (``filter_params`` a ``DenoiseParams`` or None) or 'denoised_var' (a ``DenoiseVarParams`` or None), the filters with
+        ``aov_samples`` as in ``progressive_denoised_snapshot``; then ``display`` with ``params`` -- the caller puts the weight
+        1/(frames * spp) there.  Only w*h*(3|4) bytes cross the host link.  Returns uint8 (h, w, 3|4); nothing of the loop changes."""
+        w, h, _ = self._prog_size("progressive_display_snapshot")
+        dp = _display_params(params)
+        out = np.empty((h, w, dp.channels), dtype=np.uint8)
+        p = dp.as_c()
+        src = {"accum": DISPLAY_SRC_ACCUM, "denoised": DISPLAY_SRC_DENOISED, "denoised_var": DISPLAY_SRC_DENOISED_VAR}.get(source, source)
+        fp = None
+        if src == DISPLAY_SRC_DENOISED:
+            fp = _denoise_params(filter_params)
+        elif src == DISPLAY_SRC_DENOISED_VAR:
+            fp = _denoise_var_params(filter_params)
+        elif filter_params is not None:
+            raise ValueError("progressive_display_snapshot: source 'accum' takes no filter_params")
+        self._check(self._lib.spt_progressive_display_snapshot(self._h, int(src), int(aov_samples), C.byref(fp) if fp is not None else None, C.byref(p),
+                                                               out.ctypes.data_as(C.c_void_p)))
         return out
 
     def progressive_end(self):
@@ -1084,4 +1178,31 @@ def write_ppm(path, rgb):
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     h, w, _ = rgb.shape
     if load_library().spt_write_ppm(str(path).encode(), rgb.ctypes.data_as(C.c_void_p), w, h):
+        raise SptError(f"cannot write {path}")
+
+
+def display_thresholds():
+    """The 255 float32 thresholds T[1..255] of toInt (spt_display_thresholds): T[k] = the smallest float with toInt >= k."""
+    out = np.empty(255, dtype=np.float32)
+    if load_library().spt_display_thresholds(out.ctypes.data_as(C.c_void_p)):
+        raise SptError("spt_display_thresholds: toInt is not monotone on this machine")
+    return out
+
+
+def display_quantise_host(v):
+    """The display transform's table count on the CPU (spt_display_quantise_host): uint8 of v's shape, == toInt(v), NaN -> 0."""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    out = np.empty(v.shape, dtype=np.uint8)
+    if load_library().spt_display_quantise_host(v.ctypes.data_as(C.c_void_p), v.size, out.ctypes.data_as(C.c_void_p)):
+        raise SptError("spt_display_quantise_host failed")
+    return out
+
+
+def write_ppm_rgb8(path, rgb8):
+    """writeImage (smallpt.cpp:136-142) for an (h, w, 3) uint8 image whose row 0 is the TOP row (``display`` with ``flip_y``)."""
+    rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    if rgb8.ndim != 3 or rgb8.shape[2] != 3:
+        raise ValueError("write_ppm_rgb8: one (h, w, 3) uint8 image")
+    h, w, _ = rgb8.shape
+    if load_library().spt_write_ppm_rgb8(str(path).encode(), rgb8.ctypes.data_as(C.c_void_p), w, h):
         raise SptError(f"cannot write {path}")
