@@ -39,6 +39,8 @@
  *     image as 8-bit colour (smallpt.cpp:953-962,                spt_progressive_display_snapshot (on the device,
  *     glutils.cpp:230-256) and toInt per channel before the      bit-exact to toInt), spt_write_ppm_rgb8
  *     PPM (smallpt.cpp:52,136-142)
+ *   needClearBuffer on a camera update (smallpt.cpp:903-915,    spt_temporal_accumulate* / spt_progressive_temporal_*: history
+ *     931-933): the accumulation restarts                        reprojected across the move instead of a restart
  *   "Elapsed time" stderr line (smallpt.cpp:371-373,809-811)    spt_stats
  *   CHK_PRIME / rtpContextGetLastErrorString                    int status + spt_last_error()
  *     (smallpt.cpp:381-393)
@@ -529,7 +531,7 @@ int  spt_progressive_aov_snapshot(spt_ctx* ctx, uint32_t kind_bit, float* out_rg
  *   Scratch (the packed guides and two colour images, 80 bytes per pixel) belongs to the context, is grown on demand and freed by
  *     spt_destroy and spt_progressive_end; a failed allocation fails the call and leaves the context usable.  Calls of one context run
  *     one after another, whatever their streams (they share the scratch).  A call changes no render state.
- *   Out of scope: albedo demodulation; temporal reprojection; the multi-GPU front; the async lanes (they stay radiance-only). */
+ *   Out of scope: albedo demodulation; the multi-GPU front; the async lanes (they stay radiance-only). */
 typedef struct spt_denoise_params {
     uint32_t levels;      /* 1..5 passes; pass i uses step 2^i pixels */
     float sigma_normal, sigma_plane, sigma_albedo, sigma_coverage;  /* each finite and >= 0 */
@@ -693,6 +695,119 @@ int  spt_display_quantise_host(const float* v, uint64_t n, uint8_t* out);
 /* Host-only: the ASCII P3 file of spt_write_ppm for an image that is already RGB8 and top row first (what spt_display writes with
  * SPT_DISPLAY_RGB8 | SPT_DISPLAY_FLIP_Y): spt_write_ppm(rgb) and spt_write_ppm_rgb8(display of rgb) produce the same bytes. */
 int  spt_write_ppm_rgb8(const char* path, const uint8_t* rgb8_top_first, uint32_t w, uint32_t h);
+
+/* Temporal accumulation with reprojection across camera moves (csrc/spt_temporal.hip): the temporal stage of SVGF (Schied et al. 2017).
+ * The loop above sums frames under ONE frame count, so a camera change has to clear it (needClearBuffer, smallpt.cpp:931-933) and a moving
+ * viewer shows single frames.  This is a second, self-contained loop over NORMALISED MEANS with a PER-PIXEL history length: each pixel looks
+ * its mean hit point up in the previous camera's image and keeps the history it finds there.  It is fed by buffers the library already
+ * produces and drained by the filters it already has; it touches no accumulator, result or render state of the loops above.
+ *   Arithmetic: float32, one rounding per operation, no contraction, correctly rounded division.  Images are w*h, row 0 = bottom.  Pinned
+ *     bit for bit by tests/temporal_expected.py (numpy) and tests/test_gpu_temporal.py.
+ *   Inputs of one step: F = the frame's un-normalised beauty sum as spt_render_rows_device writes it; N, P, C = the NORMAL, POSITION and
+ *     COVERAGE sums of the SAME camera, samps and seed as spt_render_aov_set_rows_device writes them (packed float3 each; c = channel 0 of
+ *     C); frame_samples = 4 * samps; the current camera, the previous camera and the previous history (or none: NULL).
+ *   History: three float4 planes of w*h pixels each, plane k at float4 offset k*w*h, 48 bytes per pixel:
+ *       plane 0  {mean r, g, b, len}     len = the pixel's history length (float, >= 1)
+ *       plane 1  {n.x, n.y, n.z, c}      n = N / c, the guide of the frame that wrote the pixel (0 when !(c > 0)); c as given
+ *       plane 2  {x.x, x.y, x.z, m2}     x = P / c likewise; m2 = the running mean of the squared luminance
+ *     spt_temporal_history_bytes(w, h) = 48*w*h.  The caller owns two such buffers and ping-pongs them.
+ *   Camera inverse: spt_camera_inverse(cam, W) = the inverse of the 3x3 matrix with COLUMNS cx, cy, dir, row-major, in double by the cofactor
+ *     / adj / det sequence of spt_instance_inverse (adj from the nine 2x2 cofactors, each a*b - c*d; det = (a00 adj00 + a01 adj10) +
+ *     a02 adj20; Wd = adj / det), W = (float)Wd.  Rejected when an entry of cx, cy, dir is not finite, det == 0 or an entry of W is not finite.
+ *   Per pixel p:
+ *     Current sample: ws = 1.0f / (float)frame_samples (once, on the host); cur_j = F_j * ws; with lum(v) = (0.2126f*v.x + 0.7152f*v.y) +
+ *       0.0722f*v.z (the expression of spt_accumulate_moments_device): Lc = lum(cur); m2c = Lc*Lc.
+ *     Guides: c_p > 0: n_p = N / c_p, x_p = P / c_p component by component; otherwise n_p = x_p = 0.
+ *     No history -- there is no previous buffer, or !(c_p > 0), or the projection fails, or no tap is valid: out = cur, len = 1, m2 = m2c.
+ *     Reprojection into the PREVIOUS camera {o, cx, cy, dir, push, sampler} with W its inverse:
+ *       v = x_p - o;   q_i = (W[i][0]*v.x + W[i][1]*v.y) + W[i][2]*v.z;   the projection fails unless q.z > push;
+ *       ax = q.x / q.z;   ay = q.y / q.z;
+ *       ux = ax + 0.5f for SPT_SAMPLER_SMALLPT, (ax + 1.0f) * 0.5f for SPT_SAMPLER_PINHOLE (the inverses of the two samplers' pixel -> ax
+ *         maps); uy likewise from ay;
+ *       sx = ux * (float)w - 0.5f;   sy = uy * (float)h - 0.5f;
+ *       range test IN FLOAT, before any conversion to int: -1.0f <= sx && sx < (float)w, the same for sy and h; NaN fails it;
+ *       x0 = floor(sx);  fx = sx - x0;   y0 = floor(sy);  fy = sy - y0.
+ *     Taps: dy = 0, 1 in the outer loop, dx = 0, 1 in the inner loop, t = (x0 + dx, y0 + dy).  A tap is skipped when it lies outside the
+ *       image, when !(c_t > 0) in the previous history, or unless both
+ *         en = |n_p - n_t|^2 <= tau_normal   and   ep = (n_p . (x_t - x_p))^2 <= tau_plane
+ *       with both sums in spt_denoise's order (dn = n_p - n_t; en = (dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z; d = x_t - x_p; pl = (n_p.x*d.x +
+ *       n_p.y*d.y) + n_p.z*d.z; ep = pl*pl); NaN fails a comparison.
+ *       wt = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy).  Starting from 0.0f: num_k += wt * hist_t[k] for k = r, g, b, len, m2 in that
+ *       order, then wsum += wt.  If wsum > 0: hv = num / wsum (five divisions); otherwise the pixel has no history.
+ *     Blend: t = hv.len + 1.0f;  len' = t < max_len ? t : max_len;  r = 1.0f / len';  a = alpha > r ? alpha : r;
+ *       out_j = hv_j + a * (cur_j - hv_j);   m2 = hv.m2 + a * (m2c - hv.m2);   len = len'.
+ *     Identity rule: when every field of the two cameras compares equal as floats (origin, dir, cx, cy, push) and the samplers match, the
+ *       mapping is t = p: hv = the stored {mean, len, m2} of pixel p of the previous history, no arithmetic, no validation, pixels with
+ *       !(c_p > 0) included.  With alpha = 0 and max_len above the frame count a camera at rest converges like the plain progressive mean
+ *       (a = 1 / len: the running mean).  Reprojecting a camera at rest instead would lose the silhouette pixels to the validation.
+ *     Written: the three history planes of p; optionally (NULL = skipped) the packed float3 mean image out_rgb -- what spt_display_device
+ *       takes with weight 1 and spt_denoise_device as `beauty` (with aov_samples = frame_samples and the frame's guide sums: the filter is
+ *       linear, a mean is as good as a sum) --; optionally w*h floats out_var: L = lum(out); v = m2 - L*L; v = v > 0 ? v : 0, exactly 0
+ *       for a pixel without history; optionally w*h floats out_len.
+ *   Parameters: alpha in [0, 1] (the floor of the blend weight: 0 = pure running mean up to max_len); max_len >= 1; tau_normal, tau_plane
+ *     >= 0; every field finite.  Defaults (spt_temporal_params_default): 0.1, 32, 0.5, 10.  tau_plane is in (scene length)^2, like
+ *     1 / sigma_plane: the default suits the Cornell box's scale of about 100.
+ *   spt_temporal_accumulate_device: DEVICE buffers of this context's device; the packed-float3 images and d_out_var / d_out_len need 4-byte
+ *     alignment, the histories 16-byte; enqueued on `hip_stream` (NULL = the context's stream), returns without waiting.  It uses no scratch
+ *     and no state of the context, so calls are ordered by their streams alone.  d_hist_prev = NULL: no history (prev_cam is then ignored).
+ *   spt_temporal_accumulate: host buffers, blocking; staged through the context's scratch (grown on demand, freed by spt_destroy; a failed
+ *     allocation fails the call and leaves the context usable).
+ *   The loop:
+ *     spt_progressive_temporal_begin(ctx, params)   after spt_progressive_begin: two histories, one frame, one set of NORMAL, ALBEDO,
+ *       POSITION, COVERAGE frames and one {mean, var, len} image on the device (176 bytes per pixel); replaces an earlier begin.
+ *     spt_progressive_temporal_frame(ctx, cam, samps, seed, reset, stats)   blocking: the radiance launch spt_progressive_frame makes, into
+ *       the loop's own frame; the spt_render_aov_set launch of NORMAL | ALBEDO | POSITION | COVERAGE with the same camera, samps and seed;
+ *       the step above against the remembered previous camera; then the histories swap and `cam` is remembered.  reset != 0, or the first
+ *       frame since the begin, means no history.  `cam` is validated before anything is launched: a NULL camera, an unknown sampler or a
+ *       {cx | cy | dir} that spt_camera_inverse rejects fails the call and leaves the loop -- frames, history, picture -- as it was, so
+ *       the remembered previous camera always has an inverse.  stats are the radiance launch's.  It touches neither accumBuffer, M2, n nor the feature
+ *       accumulators.
+ *     spt_progressive_temporal_snapshot(ctx, out_rgb, out_var, out_len)   copies the last frame's mean image (w*h*3 floats) and, where not
+ *       NULL, its variance and history length (w*h floats each) to host memory.
+ *     spt_progressive_temporal_display_snapshot(ctx, denoise_params, display_params, out8)   the loop's picture as 8-bit colour: with
+ *       denoise_params the filter of spt_denoise* runs on the device with beauty = the mean, the last frame's four guide sums and
+ *       aov_samples = its 4 * samps; the display kernel follows and only the bytes cross the host link.  denoise_params = NULL displays the
+ *       mean itself.  Byte for byte spt_display of (spt_denoise of) the float snapshot (and those guides); the caller's weight is 1 for a mean.
+ *     spt_progressive_end frees everything the loop allocated; so does the next spt_progressive_begin.
+ *   Failures (message in spt_last_error, nothing launched, nothing written): a NULL required pointer (a previous history without its camera
+ *     included); w or h of 0, or w*h above 2^31 - 1; frame_samples == 0; a parameter out of range or not finite; a previous camera whose
+ *     inverse is rejected; a sampler other than the two known ones; a packed-float3 pointer that is not 4-byte aligned; a history pointer
+ *     that is not 16-byte aligned; d_hist_next == d_hist_prev; an output that overlaps an input or another output; a loop entry before its
+ *     begin (spt_progressive_temporal_begin before spt_progressive_begin, the others before spt_progressive_temporal_begin, the snapshots
+ *     before the first frame).
+ *   Known limits: only the camera may move -- after spt_set_scene / spt_set_meshes / spt_set_instances / spt_set_environment the caller
+ *     resets.  The first hit's motion stands for the whole path: reflections and refractions lag until alpha fades them.  The async lanes
+ *     and the multi-GPU front are not covered.  The per-pixel variance is not fed into spt_denoise_var: that entry takes one frame count. */
+typedef struct spt_temporal_params {
+    float alpha;       /* in [0, 1]: lower bound of the weight of the current frame */
+    float max_len;     /* >= 1: cap of the history length */
+    float tau_normal;  /* >= 0: largest squared difference of the unit-ish normals of pixel and tap */
+    float tau_plane;   /* >= 0: largest squared distance of the tap's point from the pixel's tangent plane, (scene length)^2 */
+} spt_temporal_params;
+#if defined(__cplusplus)
+static_assert(sizeof(spt_temporal_params) == 16, "spt_temporal_params: 16 bytes");
+#else
+_Static_assert(sizeof(spt_temporal_params) == 16, "spt_temporal_params: 16 bytes");
+#endif
+/* Host-only: alpha = 0.1, max_len = 32, tau_normal = 0.5, tau_plane = 10. */
+void spt_temporal_params_default(spt_temporal_params* params);
+/* Host-only: 48 * w * h. */
+uint64_t spt_temporal_history_bytes(uint32_t w, uint32_t h);
+/* Host-only: W (row-major 3x3) as stated above.  0 = ok, non-zero = rejected. */
+int  spt_camera_inverse(const spt_camera* cam, float W[9]);
+int  spt_temporal_accumulate_device(spt_ctx* ctx, const void* d_frame, const void* d_normal, const void* d_position, const void* d_coverage,
+                                    uint32_t w, uint32_t h, uint32_t frame_samples, const spt_camera* cam, const spt_camera* prev_cam,
+                                    const void* d_hist_prev, void* d_hist_next, const spt_temporal_params* params, void* d_out_rgb,
+                                    void* d_out_var, void* d_out_len, void* hip_stream);
+int  spt_temporal_accumulate(spt_ctx* ctx, const float* frame, const float* normal, const float* position, const float* coverage,
+                             uint32_t w, uint32_t h, uint32_t frame_samples, const spt_camera* cam, const spt_camera* prev_cam,
+                             const void* hist_prev, void* hist_next, const spt_temporal_params* params, float* out_rgb, float* out_var,
+                             float* out_len);
+int  spt_progressive_temporal_begin(spt_ctx* ctx, const spt_temporal_params* params);
+int  spt_progressive_temporal_frame(spt_ctx* ctx, const spt_camera* cam, uint32_t samps_per_cell, uint64_t seed, int reset, spt_stats* stats);
+int  spt_progressive_temporal_snapshot(spt_ctx* ctx, float* out_rgb, float* out_var, float* out_len);
+int  spt_progressive_temporal_display_snapshot(spt_ctx* ctx, const spt_denoise_params* denoise_params, const spt_display_params* display_params,
+                                               uint8_t* out8);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,10 @@ class SptDisplayParams(C.Structure):  # spt_display_params: 20 bytes
     _fields_ = [("weight", C.c_float * 3), ("format", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class SptTemporalParams(C.Structure):  # spt_temporal_params: 16 bytes
+    _fields_ = [("alpha", C.c_float), ("max_len", C.c_float), ("tau_normal", C.c_float), ("tau_plane", C.c_float)]
+
+
 class SptInstance(C.Structure):      # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
     _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
 
@@ -132,6 +136,17 @@ SYMBOLS = {
     "spt_display_thresholds": (C.c_int, [_P]),
     "spt_display_quantise_host": (C.c_int, [_P, C.c_uint64, _P]),
     "spt_write_ppm_rgb8": (C.c_int, [C.c_char_p, _P, C.c_uint32, C.c_uint32]),
+    "spt_temporal_params_default": (None, [C.POINTER(SptTemporalParams)]),
+    "spt_temporal_history_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "spt_camera_inverse": (C.c_int, [C.POINTER(SptCamera), _P]),
+    "spt_temporal_accumulate_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptCamera), C.POINTER(SptCamera),
+                                                 _P, _P, C.POINTER(SptTemporalParams), _P, _P, _P, _P]),
+    "spt_temporal_accumulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptCamera), C.POINTER(SptCamera),
+                                          _P, _P, C.POINTER(SptTemporalParams), _P, _P, _P]),
+    "spt_progressive_temporal_begin": (C.c_int, [_P, C.POINTER(SptTemporalParams)]),
+    "spt_progressive_temporal_frame": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int, C.POINTER(SptStats)]),
+    "spt_progressive_temporal_snapshot": (C.c_int, [_P, _P, _P, _P]),
+    "spt_progressive_temporal_display_snapshot": (C.c_int, [_P, C.POINTER(SptDenoiseParams), C.POINTER(SptDisplayParams), _P]),
 }
 
 # test / tuning hooks declared in csrc/spt_internal.h (not part of the drop-in boundary)

@@ -12,6 +12,8 @@
 #include "spt_denoise.h"
 #include "spt_denoise_var.h"
 #include "spt_display.h"
+#include "spt_temporal.h"
+#include "spt_temporal_host.h"
 
 #include <chrono>
 #include <cmath>
@@ -143,6 +145,13 @@ struct spt_ctx {
     // 8-bit image of the host forms and the snapshot, grown on demand (they run on the context's stream and block, so nothing else reads it)
     float* d_disp_table = nullptr;
     uint8_t* d_disp8 = nullptr; size_t disp8_cap = 0;
+    // spt_progressive_temporal_*: the parameters of the begin, two histories (hist[cur] holds the last frame's), the loop's own radiance
+    // frame, its NORMAL / ALBEDO / POSITION / COVERAGE frames (one allocation), the {mean rgb | var | len} image of the last frame, that
+    // frame's camera and 4 * samps, and whether hist[cur] is a history yet
+    bool tp_on = false; spt_temporal_params tp_params{};
+    float4* d_tp_hist[2] = {nullptr, nullptr}; int tp_cur = 0; bool tp_have = false;
+    float* d_tp_frame = nullptr; float* d_tp_guides = nullptr; float* d_tp_out = nullptr;
+    spt_camera tp_cam{}; uint32_t tp_samples = 0;
     hipEvent_t ev_acc = nullptr;   // owner of an accumBuffer: completion of the most recent accumulation (any lane's stream)
     bool acc_recorded = false;
     bool frame_in_flight = false;  // a spt_progressive_frame_async of this lane has not been waited for
@@ -290,6 +299,16 @@ static void moments_free(spt_ctx* c)
     c->d_m2 = nullptr; c->m2_frames = 0; c->m2_valid = false;
 }
 
+static void temporal_free(spt_ctx* c)
+{
+    for (float4*& hst : c->d_tp_hist) { if (hst) (void)hipFree(hst); hst = nullptr; }
+    if (c->d_tp_frame) (void)hipFree(c->d_tp_frame);
+    if (c->d_tp_guides) (void)hipFree(c->d_tp_guides);
+    if (c->d_tp_out) (void)hipFree(c->d_tp_out);
+    c->d_tp_frame = c->d_tp_guides = c->d_tp_out = nullptr;
+    c->tp_on = c->tp_have = false; c->tp_cur = 0; c->tp_samples = 0;
+}
+
 static void progressive_aov_free(spt_ctx* c)
 {
     for (int k = 0; k < 6; ++k) {
@@ -315,6 +334,7 @@ void spt_destroy(spt_ctx* c)
     if (c->d_frame) (void)hipFree(c->d_frame);
     progressive_aov_free(c);
     moments_free(c);
+    temporal_free(c);
     denoise_free(c);
     display_free(c);
     if (c->d_disp_table) (void)hipFree(c->d_disp_table);
@@ -2265,6 +2285,7 @@ int spt_progressive_end(spt_ctx* c)
     c->d_accum = c->d_frame = nullptr;
     progressive_aov_free(c);
     moments_free(c);
+    temporal_free(c);
     if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));   // a filter a caller's stream still runs
     c->denoise_recorded = false;
     denoise_free(c);
@@ -2782,6 +2803,208 @@ int spt_progressive_display_snapshot(spt_ctx* c, uint32_t filter, uint32_t aov_s
         const bool var = filter == SPT_DISPLAY_SRC_DENOISED_VAR;
         if (int rc = progressive_denoised_enqueue(c, who, aov_samples, var ? nullptr : static_cast<const spt_denoise_params*>(filter_params),
                                                   var ? static_cast<const spt_denoise_var_params*>(filter_params) : nullptr)) return rc;
+        src = c->d_dn_out;
+    }
+    return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);
+}
+
+// ---- temporal accumulation with reprojection (spt_temporal.hip; the contract is stated in include/smallpt_mi355x.h) ----
+void spt_temporal_params_default(spt_temporal_params* p)
+{
+    if (!p) return;
+    p->alpha = 0.1f;
+    p->max_len = 32.0f;
+    p->tau_normal = 0.5f;
+    p->tau_plane = 10.0f;
+}
+
+uint64_t spt_temporal_history_bytes(uint32_t w, uint32_t h) { return (uint64_t)w * h * 48u; }
+
+int spt_camera_inverse(const spt_camera* cam, float W[9])
+{
+    if (!cam || !W) return 1;
+    return spt::camera_inverse(cam, W);
+}
+
+// Validates (spt_temporal_host.h) and enqueues one step on st; device set.  Every buffer is a device address.
+static int temporal_enqueue(spt_ctx* c, const char* who, const spt::TemporalCall& k, hipStream_t st)
+{
+    spt::TemporalPlan plan;
+    char msg[256];
+    if (spt::temporal_validate(k, who, &plan, msg, sizeof msg)) return c->fail("%s", msg);
+    spt_temporal_args a{};
+    a.frame = static_cast<const float*>(k.frame); a.normal = static_cast<const float*>(k.normal);
+    a.position = static_cast<const float*>(k.position); a.coverage = static_cast<const float*>(k.coverage);
+    a.hist_prev = static_cast<const float4*>(k.hist_prev);
+    a.hist_next = static_cast<float4*>(const_cast<void*>(k.hist_next));
+    a.out_rgb = static_cast<float*>(const_cast<void*>(k.out_rgb));
+    a.out_var = static_cast<float*>(const_cast<void*>(k.out_var));
+    a.out_len = static_cast<float*>(const_cast<void*>(k.out_len));
+    a.w = k.w; a.h = k.h;
+    a.mode = plan.mode;
+    a.ws = plan.ws;
+    for (int i = 0; i < 9; ++i) a.W[i] = plan.W[i];
+    if (plan.mode != SPT_TEMPORAL_NONE) {
+        a.sampler = k.prev_cam->sampler;
+        for (int i = 0; i < 3; ++i) a.o[i] = k.prev_cam->origin[i];
+        a.push = k.prev_cam->push;
+    }
+    a.alpha = k.params->alpha; a.max_len = k.params->max_len; a.tau_normal = k.params->tau_normal; a.tau_plane = k.params->tau_plane;
+    SPT_HIP(c, spt_temporal_launch(&a, st));
+    return 0;
+}
+
+int spt_temporal_accumulate_device(spt_ctx* c, const void* d_frame, const void* d_normal, const void* d_position, const void* d_coverage, uint32_t w,
+                                   uint32_t h, uint32_t frame_samples, const spt_camera* cam, const spt_camera* prev_cam, const void* d_hist_prev,
+                                   void* d_hist_next, const spt_temporal_params* p, void* d_out_rgb, void* d_out_var, void* d_out_len, void* hip_stream)
+{
+    if (!c) return 1;
+    const spt::TemporalCall k{d_frame, d_normal, d_position, d_coverage, d_hist_prev, d_hist_next, d_out_rgb, d_out_var, d_out_len,
+                              w, h, frame_samples, cam, prev_cam, p, true};
+    SPT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return temporal_enqueue(c, "spt_temporal_accumulate_device", k, st);
+}
+
+int spt_temporal_accumulate(spt_ctx* c, const float* frame, const float* normal, const float* position, const float* coverage, uint32_t w, uint32_t h,
+                            uint32_t frame_samples, const spt_camera* cam, const spt_camera* prev_cam, const void* hist_prev, void* hist_next,
+                            const spt_temporal_params* p, float* out_rgb, float* out_var, float* out_len)
+{
+    if (!c) return 1;
+    const char* const who = "spt_temporal_accumulate";
+    {   // the caller's own buffers first: NULLs, sizes, parameters, cameras and overlaps are judged on the host addresses
+        const spt::TemporalCall k{frame, normal, position, coverage, hist_prev, hist_next, out_rgb, out_var, out_len, w, h, frame_samples, cam, prev_cam, p, false};
+        spt::TemporalPlan plan;
+        char msg[256];
+        if (spt::temporal_validate(k, who, &plan, msg, sizeof msg)) return c->fail("%s", msg);
+    }
+    SPT_HIP(c, hipSetDevice(c->device));
+    // staging, in floats, every piece 16-byte aligned: F, N, P, C | previous history | next history | mean | var | len
+    const size_t npix = (size_t)w * h, nfl = npix * 3, pitch = (nfl + 3) & ~(size_t)3, plane = (npix + 3) & ~(size_t)3, hist = npix * 12;
+    if (grow_out(c, 5 * pitch + 2 * hist + 2 * plane)) return 1;
+    float* const d = c->d_out;
+    float* const d_prev = d + 4 * pitch;
+    float* const d_next = d_prev + hist;
+    float* const d_rgb = d_next + hist;
+    float* const d_var = d_rgb + pitch;
+    float* const d_len = d_var + plane;
+    const float* const host[4] = {frame, normal, position, coverage};
+    for (int j = 0; j < 4; ++j)
+        SPT_HIP(c, hipMemcpyAsync(d + j * pitch, host[j], nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (hist_prev) SPT_HIP(c, hipMemcpyAsync(d_prev, hist_prev, hist * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    const spt::TemporalCall k{d, d + pitch, d + 2 * pitch, d + 3 * pitch, hist_prev ? d_prev : nullptr, d_next, out_rgb ? d_rgb : nullptr,
+                              out_var ? d_var : nullptr, out_len ? d_len : nullptr, w, h, frame_samples, cam, prev_cam, p, true};
+    if (int rc = temporal_enqueue(c, who, k, c->stream)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(hist_next, d_next, hist * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb) SPT_HIP(c, hipMemcpyAsync(out_rgb, d_rgb, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_var) SPT_HIP(c, hipMemcpyAsync(out_var, d_var, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_len) SPT_HIP(c, hipMemcpyAsync(out_len, d_len, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The loop's buffers in floats: a packed-float3 image padded to 16 bytes, and the {mean | var | len} image
+static size_t temporal_pitch(const spt_ctx* c) { return ((size_t)c->prog_w * c->prog_h * 3 + 3) & ~(size_t)3; }
+static size_t temporal_plane(const spt_ctx* c) { return ((size_t)c->prog_w * c->prog_h + 3) & ~(size_t)3; }
+
+int spt_progressive_temporal_begin(spt_ctx* c, const spt_temporal_params* p)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_temporal_begin";
+    if (!c->d_accum) return c->fail("%s: call spt_progressive_begin first", who);
+    if (c->attached_to) return c->fail("%s: lanes accumulate radiance only", who);
+    char msg[256];
+    if (spt::temporal_params_check(p, who, msg, sizeof msg)) return c->fail("%s", msg);
+    if ((uint64_t)c->prog_w * c->prog_h > 0x7FFFFFFFull) return c->fail("%s: w*h exceeds 2^31-1 pixels", who);
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    temporal_free(c);
+    const size_t hist = (size_t)spt_temporal_history_bytes(c->prog_w, c->prog_h), pitch = temporal_pitch(c), plane = temporal_plane(c);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_hist[0]), hist);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_hist[1]), hist);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_frame), pitch * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_guides), 4 * pitch * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_out), (pitch + 2 * plane) * sizeof(float));
+    if (e != hipSuccess) { (void)hipGetLastError(); temporal_free(c); return c->fail("%s: %s", who, hipGetErrorString(e)); }
+    c->tp_params = *p;
+    c->tp_on = true;
+    return 0;
+}
+
+int spt_progressive_temporal_frame(spt_ctx* c, const spt_camera* cam, uint32_t samps, uint64_t seed, int reset, spt_stats* stats)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_temporal_frame";
+    if (!c->tp_on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (!cam) return c->fail("%s: NULL argument", who);
+    if (c->frame_in_flight) return c->fail("%s: a radiance frame of this context has not been waited for", who);
+    // everything the step would refuse is refused here, before a launch overwrites the loop's frames: the remembered camera passed this
+    // test in its own frame, and the buffers and parameters are the loop's own
+    if (cam->sampler > SPT_SAMPLER_PINHOLE) return c->fail("%s: unknown camera sampler %u", who, cam->sampler);
+    float w_unused[9];
+    if (spt::camera_inverse(cam, w_unused)) return c->fail("%s: the camera's {cx | cy | dir} has no inverse (det == 0 or not finite)", who);
+    if (samps == 0) return c->fail("%s: samps == 0", who);
+    const uint32_t w = c->prog_w, h = c->prog_h;
+    const size_t pitch = temporal_pitch(c), plane = temporal_plane(c);
+    // :922 the frame is the UN-NORMALISED sum of Renderer::render -- the launch of spt_progressive_frame, into the loop's own frame
+    if (int rc = spt_render_rows_device(c, cam, w, h, 0, h, samps, seed, 0u, c->d_tp_frame, nullptr)) return rc;
+    if (int rc = spt_sync(c, stats)) return rc;
+    float* const g = c->d_tp_guides;
+    void* const guides[4] = {g, g + pitch, g + 2 * pitch, g + 3 * pitch};       // NORMAL, ALBEDO, POSITION, COVERAGE: ascending bit order
+    const uint32_t mask = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE;
+    if (int rc = render_aov_impl(c, who, cam, w, h, 0, h, samps, seed, true, mask, 0u, guides, nullptr)) return rc;
+    const bool have = c->tp_have && !reset;
+    const int next = c->tp_cur ^ 1;
+    const spt::TemporalCall k{c->d_tp_frame, g, g + 2 * pitch, g + 3 * pitch, have ? c->d_tp_hist[c->tp_cur] : nullptr, c->d_tp_hist[next], c->d_tp_out,
+                              c->d_tp_out + pitch, c->d_tp_out + pitch + plane, w, h, 4u * samps, cam, have ? &c->tp_cam : nullptr, &c->tp_params, true};
+    const int rc = temporal_enqueue(c, who, k, c->stream);
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (int src = spt_sync(c, nullptr)) return src;                             // the feature launch's completion
+    if (rc) return rc;
+    c->tp_cur = next;
+    c->tp_have = true;
+    c->tp_cam = *cam;
+    c->tp_samples = 4u * samps;
+    return 0;
+}
+
+int spt_progressive_temporal_snapshot(spt_ctx* c, float* out_rgb, float* out_var, float* out_len)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_temporal_snapshot";
+    if (!c->tp_on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (!out_rgb) return c->fail("%s: NULL argument (out_rgb)", who);
+    if (!c->tp_have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->prog_w * c->prog_h, pitch = temporal_pitch(c), plane = temporal_plane(c);
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_tp_out, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_var) SPT_HIP(c, hipMemcpyAsync(out_var, c->d_tp_out + pitch, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_len) SPT_HIP(c, hipMemcpyAsync(out_len, c->d_tp_out + pitch + plane, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int spt_progressive_temporal_display_snapshot(spt_ctx* c, const spt_denoise_params* dp, const spt_display_params* p, uint8_t* out8)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_temporal_display_snapshot";
+    if (!c->tp_on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (!out8) return c->fail("%s: NULL argument (out8)", who);
+    if (!c->tp_have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
+    if (int rc = display_check(c, who, c->prog_w, c->prog_h, p)) return rc;
+    if (dp) if (int rc = denoise_check(c, who, c->prog_w, c->prog_h, c->tp_samples, dp)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (int rc = display_table(c, who)) return rc;
+    const float* src = c->d_tp_out;
+    if (dp) {
+        const size_t nfl = (size_t)c->prog_w * c->prog_h * 3, pitch = temporal_pitch(c);
+        if (nfl > c->dn_out_cap) {
+            if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));
+            const hipError_t e = grow(c->d_dn_out, c->dn_out_cap, nfl);
+            if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: scratch: %s", who, hipGetErrorString(e)); }
+        }
+        const float* const g = c->d_tp_guides;
+        if (int rc = denoise_enqueue(c, who, c->d_tp_out, g, g + pitch, g + 2 * pitch, g + 3 * pitch, c->prog_w, c->prog_h, c->tp_samples, dp, c->d_dn_out, c->stream)) return rc;
         src = c->d_dn_out;
     }
     return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);

@@ -161,6 +161,63 @@ public:
         check(spt_progressive_display_snapshot(ctx_, filter, (uint32_t)aovSamples, filterParams, &params, image.data()));
     }
 
+    // Temporal accumulation with reprojection (spt_temporal_*): one step on host images -- frame and the NORMAL / POSITION / COVERAGE sums
+    // of the same camera, samples and seed; history = the 12 * w * h floats a previous step returned, or empty for none (prevCamera is
+    // then ignored).  Returns the next history; mean / variance / length are filled where not nullptr.  params = nullptr: the defaults.
+    std::vector<float> temporalAccumulate(const std::vector<float3>& frame, const std::vector<float3>& normal, const std::vector<float3>& position,
+                                          const std::vector<float3>& coverage, size_t imageWidth, size_t imageHeight, size_t frameSamples,
+                                          const spt_camera& camera, const spt_camera* prevCamera, const std::vector<float>& history,
+                                          std::vector<float3>* mean = nullptr, std::vector<float>* variance = nullptr, std::vector<float>* length = nullptr,
+                                          const spt_temporal_params* params = nullptr)
+    {
+        const size_t n = imageWidth * imageHeight;
+        if (frame.size() != n || normal.size() != n || position.size() != n || coverage.size() != n || (!history.empty() && history.size() != 12 * n))
+            throw std::runtime_error("temporalAccumulate: four images of imageWidth * imageHeight pixels and a history of 12 floats per pixel (or none)");
+        spt_temporal_params p;
+        if (params) p = *params; else spt_temporal_params_default(&p);
+        std::vector<float> next(12 * n);
+        if (mean) mean->resize(n);
+        if (variance) variance->resize(n);
+        if (length) length->resize(n);
+        auto f = [](const std::vector<float3>& v) { return reinterpret_cast<const float*>(v.data()); };
+        check(spt_temporal_accumulate(ctx_, f(frame), f(normal), f(position), f(coverage), (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)frameSamples,
+                                      &camera, history.empty() ? nullptr : prevCamera, history.empty() ? nullptr : history.data(), next.data(), &p,
+                                      mean ? reinterpret_cast<float*>(mean->data()) : nullptr, variance ? variance->data() : nullptr,
+                                      length ? length->data() : nullptr));
+        return next;
+    }
+    void temporalAccumulateDevice(const void* dFrame, const void* dNormal, const void* dPosition, const void* dCoverage, size_t imageWidth, size_t imageHeight,
+                                  size_t frameSamples, const spt_camera& camera, const spt_camera* prevCamera, const void* dHistPrev, void* dHistNext,
+                                  const spt_temporal_params& params, void* dOutRgb = nullptr, void* dOutVar = nullptr, void* dOutLen = nullptr,
+                                  void* hipStream = nullptr)
+    {
+        check(spt_temporal_accumulate_device(ctx_, dFrame, dNormal, dPosition, dCoverage, (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)frameSamples,
+                                             &camera, prevCamera, dHistPrev, dHistNext, &params, dOutRgb, dOutVar, dOutLen, hipStream));
+    }
+    // ... and as a second loop beside accumBuffer (spt_progressive_temporal_*): normalised means with a per-pixel history length that
+    // survive camera moves.  The snapshot is a MEAN (display weight 1); image must hold w*h pixels (w*h*(3|4) bytes for the 8-bit form)
+    void progressiveTemporalBegin(const spt_temporal_params* params = nullptr)
+    {
+        spt_temporal_params p;
+        if (params) p = *params; else spt_temporal_params_default(&p);
+        check(spt_progressive_temporal_begin(ctx_, &p));
+    }
+    void progressiveTemporalFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool reset)
+    {
+        check(spt_progressive_temporal_frame(ctx_, &camera, (uint32_t)sampleCountPerJitterCell, (uint64_t)seed, reset ? 1 : 0, &stats_));
+    }
+    void progressiveTemporalSnapshot(std::vector<float3>& image, std::vector<float>* variance = nullptr, std::vector<float>* length = nullptr)
+    {
+        if (variance) variance->resize(image.size());
+        if (length) length->resize(image.size());
+        check(spt_progressive_temporal_snapshot(ctx_, reinterpret_cast<float*>(image.data()), variance ? variance->data() : nullptr,
+                                                length ? length->data() : nullptr));
+    }
+    void progressiveTemporalDisplaySnapshot(std::vector<uint8_t>& image, const spt_display_params& params, const spt_denoise_params* denoiseParams = nullptr)
+    {
+        check(spt_progressive_temporal_display_snapshot(ctx_, denoiseParams, &params, image.data()));
+    }
+
     // accumBuffer of the viewer loop in HBM (spt_progressive_*, smallpt.cpp:881-883,922-937,955-959)
     void progressiveBegin(size_t w, size_t h) { check(spt_progressive_begin(ctx_, (uint32_t)w, (uint32_t)h)); }
     void progressiveFrame(const spt_camera& camera, size_t sampleCountPerJitterCell, size_t seed, bool clear)

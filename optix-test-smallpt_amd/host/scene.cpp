@@ -304,6 +304,18 @@ bool parse_update_camera_request(const std::string& text, float3* org)
     return true;
 }
 
+bool parse_request_temporal(const std::string& text, bool* temporal)
+{
+    Parser p(text);
+    JPtr root = p.parse();
+    if (root->kind != JValue::Object) throw std::runtime_error("render request: expected a JSON object");
+    auto t = root->obj.find("temporal");
+    if (t == root->obj.end()) return false;
+    if (t->second->kind != JValue::Bool) throw std::runtime_error("render request: \"temporal\" must be true or false");
+    *temporal = t->second->b;
+    return true;
+}
+
 Scene load_scene_file(const std::string& path)
 {
     std::ifstream f(path, std::ios::binary);

@@ -24,7 +24,7 @@
 //                                                              of the host's toInt loop in spt_write_ppm: the same file
 //                  [--env r,g,b] [--print-environment]         radiance of escaped paths (overrides the scene file's "environment"); print it
 //                                                              as loaded and overridden, then exit (host only)
-//   smallpt_mi355x [spp] --viewer [--frames N] [--request JSON] [--frames-after M] [--threaded] [--org x,y,z]
+//   smallpt_mi355x [spp] --viewer [--frames N] [--request JSON] [--frames-after M] [--then-request JSON] [--then-frames K] [--threaded] [--org x,y,z]
 //                  [--pipeline L] [--bench-frames N]           L frames in flight (one context each); frames/s of N frames as JSON
 //                  [--dump-raw accum.bin]                      main()'s progressive loop (smallpt.cpp:840-1005) without the
 //                                                              window: N frames, then the request(s), then M frames; writes the
@@ -63,10 +63,10 @@ int main(int argc, char* argv[])
     bool aov_list = false;                         // a comma list: one file per kind (a kind alone is written to --out itself)
     int denoise_levels = -1;                       // --denoise: 0 = the default level count, 1..5 = that many passes (-1: off)
     bool parse_only = false, viewer = false, threaded = false, self_exchange = false;
-    int frames = 1, frames_after = 0;
+    int frames = 1, frames_after = 0, frames_then = 0;
     bool have_frames = false;
     std::vector<int> devices;
-    std::vector<std::string> requests;
+    std::vector<std::string> requests, requests_then;
     std::string dump_raw;
     float org[3] = {0, -1, 0};
     bool have_org = false;
@@ -86,8 +86,13 @@ int main(int argc, char* argv[])
         else if (a == "--parse-request") {   // host-only: one message of the viewer's request queue through the JSON reader
             try {
                 float3 o3;
-                if (parse_update_camera_request(next(), &o3)) std::printf("update_camera %.9g %.9g %.9g\n", o3.x, o3.y, o3.z);
-                else std::printf("ignored\n");
+                bool temporal = false;
+                const std::string msg = next();
+                const bool has_temporal = parse_request_temporal(msg, &temporal);
+                if (parse_update_camera_request(msg, &o3)) std::printf("update_camera %.9g %.9g %.9g", o3.x, o3.y, o3.z);
+                else std::printf("ignored");
+                if (has_temporal) std::printf(" temporal %s", temporal ? "on" : "off");     // the opt-in field of the viewer's render thread
+                std::printf("\n");
                 return 0;
             } catch (const std::exception& e) { std::fprintf(stderr, "error: %s\n", e.what()); return 1; }
         }
@@ -124,6 +129,8 @@ int main(int argc, char* argv[])
         else if (a == "--frames") { frames = std::atoi(next()); have_frames = true; }
         else if (a == "--frames-after") frames_after = std::atoi(next());
         else if (a == "--request") requests.push_back(next());
+        else if (a == "--then-request") requests_then.push_back(next());      // a second round: posted after --frames-after, followed by --then-frames
+        else if (a == "--then-frames") frames_then = std::atoi(next());
         else if (a == "--dump-raw") dump_raw = next();
         else if (a == "--org") { if (std::sscanf(next(), "%f,%f,%f", &org[0], &org[1], &org[2]) != 3) { std::fprintf(stderr, "--org x,y,z\n"); return 2; } have_org = true; }
         else if (a == "--env") {
@@ -225,6 +232,8 @@ int main(int argc, char* argv[])
             run_frames(frames);
             for (const std::string& r : requests) prog.postRequest(r);
             run_frames(frames_after);
+            for (const std::string& r : requests_then) prog.postRequest(r);
+            run_frames(frames_then);
             std::vector<float3> image;
             float weight3[3];
             prog.snapshot(image, weight3);       // what the GL loop hands to drawWeightedRGBImage(image, w, h, weight3), :955-962

@@ -84,7 +84,9 @@ void ProgressiveRenderer::flush()
 void ProgressiveRenderer::postRequest(const std::string& json)
 {
     float3 ignored;
+    bool ignoredFlag;
     (void)parseUpdateCamera(json, &ignored);         // malformed text is refused HERE, on the caller's thread, not in the render thread
+    (void)parse_request_temporal(json, &ignoredFlag);
     std::unique_lock<std::mutex> l{requestsMutex_};  // :980
     requests_.emplace_back(json);
 }
@@ -100,6 +102,7 @@ void ProgressiveRenderer::moveCamera(float dy)
 void ProgressiveRenderer::stepOnce()
 {
     bool needClearBuffer = false;                    // :903
+    bool temporal = false, temporalGiven = false;
     {
         std::unique_lock<std::mutex> l{requestsMutex_};   // :906
         for (const std::string& request : requests_) {    // :909
@@ -108,6 +111,8 @@ void ProgressiveRenderer::stepOnce()
                 camera_ = Camera{camera_.vx, camera_.vy, camera_.vz, newOrg, camera_.nearPlaneDistance};   // :914
                 needClearBuffer = true;                   // :915
             }
+            bool t;
+            if (parse_request_temporal(request, &t)) { temporal = t; temporalGiven = true; }
         }
         requests_.clear();                           // :918
     }
@@ -118,6 +123,22 @@ void ProgressiveRenderer::stepOnce()
     }
     // :922 render + :927-937 accumulate, both on the device; the lock keeps a snapshot from reading a half-added frame
     std::unique_lock<std::mutex> l{accumMutex_};     // :925
+    if (temporalGiven && temporal != temporal_) {
+        for (size_t i = 0; i < lanes_.size(); ++i)   // the two loops take turns on this context: drain what is in flight
+            if (inFlight_[i]) { inFlight_[i] = 0; lanes_[i]->progressiveWait(); }
+        temporal_ = temporal;
+        temporalReset_ = true;                       // the history of an earlier temporal phase is stale
+        if (!temporal_) needClearBuffer = true;      // and so is accumBuffer after one
+    }
+    if (temporal_) {
+        // a camera change does NOT clear: the history is reprojected from the previous frame's camera (spt_progressive_temporal_frame)
+        if (!temporalBegun_) { renderer_.progressiveTemporalBegin(); temporalBegun_ = true; }
+        renderer_.progressiveTemporalFrame(camera_.abi(), samps_, seed, temporalReset_);
+        temporalReset_ = false;
+        ++sampleCount_;
+        ++framesRendered_;
+        return;
+    }
     if (lanes_.size() == 1) {
         renderer_.progressiveFrame(camera_.abi(), samps_, seed, needClearBuffer);
     } else {
@@ -131,14 +152,25 @@ void ProgressiveRenderer::stepOnce()
     ++framesRendered_;
 }
 
+bool ProgressiveRenderer::snapshotLocked(std::vector<float3>& image, float weight3[3])
+{
+    image.resize(w_ * h_);
+    if (temporal_ && !temporalReset_) {              // the temporal loop's picture is a mean already
+        renderer_.progressiveTemporalSnapshot(image);
+        weight3[0] = weight3[1] = weight3[2] = 1.f;
+        return true;
+    }
+    const size_t sampleCountPerPixel = 4 * samps_;   // jitterSize^2 * sampleCountPerJitterCell, :847-848
+    const float weight = 1.f / (sampleCount_ * sampleCountPerPixel);   // :957
+    renderer_.progressiveSnapshot(image);            // image = accumBuffer, :958
+    weight3[0] = weight3[1] = weight3[2] = weight;   // :961
+    return false;
+}
+
 void ProgressiveRenderer::snapshot(std::vector<float3>& image, float weight3[3])
 {
     std::unique_lock<std::mutex> l{accumMutex_};     // :956
-    const size_t sampleCountPerPixel = 4 * samps_;   // jitterSize^2 * sampleCountPerJitterCell, :847-848
-    const float weight = 1.f / (sampleCount_ * sampleCountPerPixel);   // :957
-    image.resize(w_ * h_);
-    renderer_.progressiveSnapshot(image);            // image = accumBuffer, :958
-    weight3[0] = weight3[1] = weight3[2] = weight;   // :961
+    (void)snapshotLocked(image, weight3);
 }
 
 void ProgressiveRenderer::snapshotDisplay(std::vector<uint8_t>& image, uint32_t format, bool flipY)
@@ -152,18 +184,30 @@ void ProgressiveRenderer::snapshotDisplay(std::vector<uint8_t>& image, uint32_t 
     p.format = format;
     p.flags = flipY ? SPT_DISPLAY_FLIP_Y : 0u;
     image.resize(w_ * h_ * (format == SPT_DISPLAY_RGBA8 ? 4 : 3));
+    if (temporal_ && !temporalReset_) {
+        p.weight[0] = p.weight[1] = p.weight[2] = 1.f;
+        renderer_.progressiveTemporalDisplaySnapshot(image, p);
+        return;
+    }
     renderer_.progressiveDisplaySnapshot(image, p);
 }
 
 std::vector<float3> ProgressiveRenderer::finalImage()
 {
+    std::unique_lock<std::mutex> l{accumMutex_};
     std::vector<float3> image;
     float w3[3];
-    snapshot(image, w3);
+    if (snapshotLocked(image, w3)) return image;     // the temporal loop's mean needs no division
     const float div = (float)(sampleCount_ * 4 * samps_);
     const float inv = 1.0f / div;                    // operator/=(float3, float) multiplies by the reciprocal, :999
     for (float3& p : image) { p.x *= inv; p.y *= inv; p.z *= inv; }
     return image;
+}
+
+bool ProgressiveRenderer::temporal()
+{
+    std::unique_lock<std::mutex> l{accumMutex_};
+    return temporal_;
 }
 
 size_t ProgressiveRenderer::sampleCount()

@@ -9,6 +9,9 @@
 //     accumBuffer under the mutex, drawWeightedRGBImage (:955-962)      drawWeightedRGBImage(const float*, w, h, weight[3]) (glutils.h:153),
 //                                                                       or snapshotDisplay(image8): the 8-bit picture made on the device
 //   keys UP/DOWN move org.y by 0.01 and post a request (:968-985)     moveCamera(dy)
+//   needClearBuffer on a camera change (:915, :931-933)               a request may carry "temporal": true (opt-in, default off): from
+//                                                                       then on a frame goes through spt_progressive_temporal_frame and a
+//                                                                       camera change keeps the reprojected history instead of clearing
 //   exit: accumBuffer /= sampleCount*spp, flipY, writeImage (:995-1004)  finalImage()
 //
 // accumBuffer lives in HBM (spt_progressive_*); the mutex guards the frame counter and the request queue like the
@@ -68,9 +71,13 @@ public:
     void snapshotDisplay(std::vector<uint8_t>& image, uint32_t format = SPT_DISPLAY_RGB8, bool flipY = false);
     std::vector<float3> finalImage();               // :995-1001 (before flipY / writeImage)
     size_t sampleCount();                           // frames accumulated since the last clear
+    // whether the render thread currently runs the temporal loop (the last "temporal" field a request carried; off until one does).
+    // While it is on, snapshot() returns the loop's MEAN image with weight 1 and snapshotDisplay() its 8-bit form; extra lanes idle.
+    bool temporal();
     size_t framesRendered() const { return framesRendered_; }
 
 private:
+    bool snapshotLocked(std::vector<float3>& image, float weight3[3]);   // accumMutex_ held; true when the image is the temporal loop's mean
     Renderer& renderer_;
     std::vector<Renderer*> lanes_;                  // lanes_[0] = &renderer_ (owner of accumBuffer)
     std::vector<char> inFlight_;
@@ -82,6 +89,7 @@ private:
     std::mutex requestsMutex_, accumMutex_;
     std::vector<std::string> requests_;
     size_t sampleCount_ = 0;   // :893
+    bool temporal_ = false, temporalBegun_ = false, temporalReset_ = true;   // guarded by accumMutex_
     std::atomic<size_t> framesRendered_{0};
     std::atomic<bool> renderDone_{false};      // the reference uses a plain float here (:894), a data race
     std::thread thread_;

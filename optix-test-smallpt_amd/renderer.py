@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, load_library, load_multi_library
+from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, SptTemporalParams, load_library, load_multi_library
 from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
@@ -251,6 +251,47 @@ class DisplayParams:
 
 def _display_params(params):
     return params if params is not None else DisplayParams()
+
+
+class TemporalParams:
+    """Parameters of the temporal accumulation (spt_temporal_params): ``alpha`` in [0, 1], the lower bound of the current frame's weight
+    (0 = the running mean up to ``max_len``); ``max_len`` >= 1, the cap of the per-pixel history length; ``tau_normal`` and ``tau_plane``
+    >= 0, the largest squared normal difference and squared distance from the pixel's tangent plane -- in (scene length)^2 -- at which a
+    history tap still counts.  Anything left None takes the library's default (spt_temporal_params_default: 0.1, 32, 0.5, 10)."""
+    FIELDS = ("alpha", "max_len", "tau_normal", "tau_plane")
+
+    def __init__(self, alpha=None, max_len=None, tau_normal=None, tau_plane=None):
+        c = SptTemporalParams()
+        load_library().spt_temporal_params_default(C.byref(c))
+        for name, v in zip(self.FIELDS, (alpha, max_len, tau_normal, tau_plane)):
+            setattr(self, name, getattr(c, name) if v is None else float(v))
+
+    def as_c(self):
+        c = SptTemporalParams()
+        for name in self.FIELDS:
+            setattr(c, name, getattr(self, name))
+        return c
+
+    def __repr__(self):
+        return "TemporalParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.FIELDS) + ")"
+
+
+def _temporal_params(params):
+    return (params if params is not None else TemporalParams()).as_c()
+
+
+def temporal_history_bytes(w, h):
+    """Size of one history of the temporal accumulation: three float4 planes, 48 bytes per pixel (spt_temporal_history_bytes)."""
+    return int(load_library().spt_temporal_history_bytes(int(w), int(h)))
+
+
+def camera_inverse(camera):
+    """(3, 3) float32: the inverse of the matrix with columns cx, cy, dir of ``camera`` (spt_camera_inverse), computed in double and rounded
+    once; ValueError when the library rejects it (a singular or non-finite camera)."""
+    out = np.empty((3, 3), dtype=np.float32)
+    if load_library().spt_camera_inverse(C.byref(camera), out.ctypes.data_as(C.c_void_p)):
+        raise ValueError("camera_inverse: the camera's {cx | cy | dir} has no inverse")
+    return out
 
 
 class SptError(RuntimeError):
@@ -750,6 +791,54 @@ class Renderer:
                                                  C.c_void_p(stream) if stream else None))
         return out_t.view(h, w, dp.channels)
 
+    def temporal_accumulate(self, frame, normal, position, coverage, frame_samples, camera, prev_camera=None, history=None, params=None,
+                            want=("rgb", "var", "len")):
+        """One step of the temporal accumulation (spt_temporal_accumulate): ``frame`` the un-normalised beauty sum and ``normal``,
+        ``position``, ``coverage`` the feature sums of the same camera, samples and seed, (h, w, 3) float32 each; ``frame_samples`` = 4 *
+        samps; ``history`` the (3, h, w, 4) float32 array a previous step returned (None: no history) and ``prev_camera`` the camera of
+        that step.  Returns (history', {'rgb': (h, w, 3) mean, 'var': (h, w), 'len': (h, w)}) with the outputs named in ``want``."""
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (frame, normal, position, coverage)]
+        if imgs[0].ndim != 3 or imgs[0].shape[2] != 3 or any(a.shape != imgs[0].shape for a in imgs):
+            raise ValueError("temporal_accumulate: four (h, w, 3) images of one size")
+        h, w, _ = imgs[0].shape
+        if history is not None:
+            history = np.ascontiguousarray(history, dtype=np.float32)
+            if history.shape != (3, h, w, 4):
+                raise ValueError("temporal_accumulate: history is a (3, h, w, 4) float32 array")
+            if prev_camera is None:
+                raise ValueError("temporal_accumulate: a history needs the camera it was written with")
+        unknown = set(want) - {"rgb", "var", "len"}
+        if unknown:
+            raise ValueError(f"temporal_accumulate: unknown outputs {sorted(unknown)}")
+        nxt = np.empty((3, h, w, 4), dtype=np.float32)
+        outs = {k: np.empty((h, w, 3) if k == "rgb" else (h, w), dtype=np.float32) for k in ("rgb", "var", "len") if k in want}
+        ptr = lambda k: outs[k].ctypes.data_as(C.c_void_p) if k in outs else None       # noqa: E731
+        p = _temporal_params(params)
+        self._check(self._lib.spt_temporal_accumulate(
+            self._h, *[a.ctypes.data_as(C.c_void_p) for a in imgs], w, h, int(frame_samples), C.byref(camera),
+            C.byref(prev_camera) if prev_camera is not None else None, history.ctypes.data_as(C.c_void_p) if history is not None else None,
+            nxt.ctypes.data_as(C.c_void_p), C.byref(p), ptr("rgb"), ptr("var"), ptr("len")))
+        return nxt, outs
+
+    def temporal_accumulate_device(self, frame_t, normal_t, position_t, coverage_t, w, h, frame_samples, camera, hist_next_t, prev_camera=None,
+                                   hist_prev_t=None, params=None, out_rgb_t=None, out_var_t=None, out_len_t=None, stream=None):
+        """The same on float32 CUDA tensors (spt_temporal_accumulate_device): the four images w*h*3 elements, the histories w*h*12 elements
+        and 16-byte aligned, ``out_rgb_t`` w*h*3 and ``out_var_t`` / ``out_len_t`` w*h elements or None.  Asynchronous on ``stream`` (a raw
+        hipStream_t, None = the context's stream).  No output may overlap an input."""
+        sizes = [(frame_t, w * h * 3), (normal_t, w * h * 3), (position_t, w * h * 3), (coverage_t, w * h * 3), (hist_next_t, w * h * 12),
+                 (hist_prev_t, w * h * 12), (out_rgb_t, w * h * 3), (out_var_t, w * h), (out_len_t, w * h)]
+        for t, n in sizes:
+            if t is not None and (t.numel() != n or not t.is_contiguous() or str(t.dtype) != "torch.float32" or t.device.type != "cuda"):
+                raise ValueError("temporal_accumulate_device: contiguous float32 tensors on the GPU of w*h*3 (images), w*h*12 (histories) and w*h elements")
+        if hist_prev_t is not None and prev_camera is None:
+            raise ValueError("temporal_accumulate_device: a history needs the camera it was written with")
+        dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None            # noqa: E731
+        p = _temporal_params(params)
+        self._check(self._lib.spt_temporal_accumulate_device(
+            self._h, dp(frame_t), dp(normal_t), dp(position_t), dp(coverage_t), w, h, int(frame_samples), C.byref(camera),
+            C.byref(prev_camera) if prev_camera is not None else None, dp(hist_prev_t), dp(hist_next_t), C.byref(p), dp(out_rgb_t), dp(out_var_t),
+            dp(out_len_t), C.c_void_p(stream) if stream else None))
+
     def accumulate_moments_device(self, accum_t, m2_t, frame_t, clear=False, stream=None):
         """accum (``clear``: =, else +=) frame and m2 (=, +=) the squared luminance of frame, one kernel (spt_accumulate_moments_device):
         contiguous float32 CUDA tensors, ``accum_t`` and ``frame_t`` of npix*3 elements and 16-byte aligned, ``m2_t`` of npix elements.
@@ -848,6 +937,49 @@ class Renderer:
             raise ValueError("progressive_display_snapshot: source 'accum' takes no filter_params")
         self._check(self._lib.spt_progressive_display_snapshot(self._h, int(src), int(aov_samples), C.byref(fp) if fp is not None else None, C.byref(p),
                                                                out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def progressive_temporal_begin(self, params=None):
+        """spt_progressive_temporal_begin after ``progressive_begin``: a second loop over normalised means with a per-pixel history
+        length, which keeps its history across camera moves (``params`` a ``TemporalParams``)."""
+        self._prog_size("progressive_temporal_begin")
+        p = _temporal_params(params)
+        self._check(self._lib.spt_progressive_temporal_begin(self._h, C.byref(p)))
+
+    def progressive_temporal_frame(self, samps_per_cell, seed, reset=False, camera=None):
+        """One frame of the temporal loop (spt_progressive_temporal_frame): the radiance launch of ``progressive_frame`` and the feature
+        launch of the same camera, samples and seed, blended into the history reprojected from the previous frame's camera; ``reset``
+        drops the history.  Blocking; returns the radiance launch's stats.  The other accumulators are not touched."""
+        w, h, _ = self._prog_size("progressive_temporal_frame")
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        st = SptStats()
+        self._check(self._lib.spt_progressive_temporal_frame(self._h, C.byref(cam), samps_per_cell, seed, 1 if reset else 0, C.byref(st)))
+        return _stats_dict(st)
+
+    def progressive_temporal_snapshot(self, var=False, length=False):
+        """The temporal loop's picture: the (h, w, 3) float32 MEAN image (display weight 1); with ``var`` and / or ``length`` a tuple
+        (mean[, (h, w) variance][, (h, w) history length])."""
+        w, h, _ = self._prog_size("progressive_temporal_snapshot")
+        out = np.empty((h, w, 3), dtype=np.float32)
+        v = np.empty((h, w), dtype=np.float32) if var else None
+        n = np.empty((h, w), dtype=np.float32) if length else None
+        self._check(self._lib.spt_progressive_temporal_snapshot(self._h, out.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p) if var else None,
+                                                                n.ctypes.data_as(C.c_void_p) if length else None))
+        if not var and not length:
+            return out
+        return (out,) + ((v,) if var else ()) + ((n,) if length else ())
+
+    def progressive_temporal_display_snapshot(self, params=None, denoise=None):
+        """The temporal loop's picture as 8-bit colour straight from the device (spt_progressive_temporal_display_snapshot): the mean, or
+        with ``denoise`` (a ``DenoiseParams``, or True for the defaults) the mean filtered under the last frame's guides, through
+        ``display`` with ``params`` (weight 1 suits a mean).  Returns uint8 (h, w, 3|4)."""
+        w, h, _ = self._prog_size("progressive_temporal_display_snapshot")
+        dp = _display_params(params)
+        out = np.empty((h, w, dp.channels), dtype=np.uint8)
+        p = dp.as_c()
+        fp = None if denoise is None or denoise is False else _denoise_params(None if denoise is True else denoise)
+        self._check(self._lib.spt_progressive_temporal_display_snapshot(self._h, C.byref(fp) if fp is not None else None, C.byref(p),
+                                                                        out.ctypes.data_as(C.c_void_p)))
         return out
 
     def progressive_end(self):
