@@ -14,6 +14,7 @@
 #include "spt_display.h"
 #include "spt_temporal.h"
 #include "spt_temporal_host.h"
+#include "spt_devbuf.h"
 
 #include <chrono>
 #include <cmath>
@@ -52,20 +53,59 @@ inline bool is_grid_kernel(int k) { return k == kGrid || k == kGridPools; }
 
 // An instanced mesh scene (spt_set_instances): per model its host triangle records and its device descriptor (the MParams of a
 // spt_set_meshes scene holding that model alone), the device copies of the descriptors, instance records and per-instance material rows,
-// and every device buffer it owns.
+// and the models' device tables, whose raw addresses the descriptors hold (they are uploaded themselves).  Dropping a scene frees them all.
 struct InstScene {
     std::vector<std::vector<float4>> tris;
     std::vector<spt::MParams> models;
-    std::vector<void*> allocs;
-    spt::MParams* d_models = nullptr;
-    spt::InstRec* d_inst = nullptr;
-    float4* d_mats = nullptr;
+    std::vector<DevBuf<unsigned char>> tables;
+    DevBuf<spt::MParams> d_models;
+    DevBuf<spt::InstRec> d_inst;
+    DevBuf<float4> d_mats;
     uint32_t ninst = 0;
     uint64_t tri_sum = 0;            // sum over instances of the model's triangles (SPT_ACCEL_AUTO)
     bool specular = false;
     bool accel_built = false;        // every model's hierarchy is in its descriptor
     std::vector<uint32_t> thin;      // per model, once built: its thin triangles (spt_mesh_line_form)
     std::vector<uint8_t> line_tree;  // ... and whether they are a cone tree (1) or a table (0)
+
+    // Uploads one table of a model into a buffer of its own and hands its address to the descriptor.
+    template <typename T>
+    hipError_t add_table(T*& dptr, const void* src, size_t bytes)
+    {
+        tables.emplace_back();
+        const hipError_t e = tables.back().upload(src, bytes);
+        dptr = reinterpret_cast<T*>(tables.back().ptr);
+        return e;
+    }
+};
+
+// The groups of spt_ctx that end with the progressive loop: assigning a fresh value frees a group and resets its flags.
+// spt_progressive_aov_*: the selected kinds; per kind an accumulation buffer and a frame, w*h*3 floats each
+struct ProgressiveAov {
+    uint32_t mask = 0;
+    DevBuf<float> accum[6], frame[6];
+};
+// spt_progressive_moments_begin (owner): per-pixel sum of the frames' squared luminance (w*h floats), the frames summed into it and into
+// accumBuffer since the last clearing frame, and whether a clearing frame has been issued since the begin (the variance is defined)
+struct Moments {
+    DevBuf<float> sum;
+    uint32_t frames = 0;
+    bool valid = false;
+};
+// spt_denoise*: packed guides (3 planes of float4), two float4 colour images (ping-pong) and the float3 result of the progressive
+// snapshot, grown on demand; calls of one context run one after another, whatever their streams (they share these)
+struct DenoiseScratch {
+    DevBuf<float4> guides, ping, pong;
+    DevBuf<float> out;
+};
+// spt_progressive_temporal_*: the parameters of the begin, two histories (hist[cur] holds the last frame's), the loop's own radiance
+// frame, its NORMAL / ALBEDO / POSITION / COVERAGE frames (one allocation), the {mean rgb | var | len} image of the last frame, that
+// frame's camera and 4 * samps, and whether hist[cur] is a history yet
+struct Temporal {
+    bool on = false; spt_temporal_params params{};
+    DevBuf<float4> hist[2]; int cur = 0; bool have = false;
+    DevBuf<float> frame, guides, out;
+    spt_camera cam{}; uint32_t samples = 0;
 };
 
 struct spt_ctx {
@@ -75,25 +115,23 @@ struct spt_ctx {
     hipEvent_t ev_start = nullptr, ev_mid = nullptr, ev_stop = nullptr;
     // scene
     uint32_t n = 0;
-    float4* d_geom = nullptr;
-    float4* d_mat = nullptr;
-    uint32_t scene_cap = 0;
+    DevBuf<float4> d_geom;         // reused by capacity (in spheres; d_mat holds three rows per sphere)
+    DevBuf<float4> d_mat;
     bool needs_guard = false;      // r*r < 2^-60 or coordinates above 1e15: the hot-loop sqrt keeps its range guard
     bool pool_ok = false;          // scene qualifies for the material-sorted pool kernel (spt_pool.hip)
     int share = 0;                 // sharing pattern of the pool kernel's closest hit that every claim of holds on this table (spt_share.h)
     int last_share = 0;            // ... the one the last pool launch ran
-    float* d_stack = nullptr;      // pool kernel: global-memory stack of pending transmitted children
-    size_t stack_cap = 0;          // in floats
+    DevBuf<float> d_stack;         // pool kernel: global-memory stack of pending transmitted children
     int last_kernel = kMega;       // RenderKernel of the last render launch (spt_last_kernel)
     // triangle-mesh scene (spt_set_meshes); mesh_scene selects it for spt_render*
     bool mesh_scene = false;
     bool mesh_specular = false;            // a mesh material is SPEC or REFR: long mirror / glass chains are possible (task dealing of the hierarchy kernel)
-    float4* d_tris = nullptr; uint4* d_tri_index = nullptr; float4* d_verts = nullptr; uint32_t* d_inst_first = nullptr; float4* d_mesh_mats = nullptr;
-    float* d_trace_rays = nullptr; float* d_trace_hits = nullptr; uint64_t trace_cap = 0;   // spt_trace_rays staging (rays)
-    float* d_range_rays = nullptr; size_t range_cap = 0;     // spt_trace_*_range staging (32-byte rays, cap in floats; the hits go to d_trace_hits)
+    DevBuf<float4> d_tris; DevBuf<uint4> d_tri_index; DevBuf<float4> d_verts; DevBuf<uint32_t> d_inst_first; DevBuf<float4> d_mesh_mats;
+    DevBuf<float> d_trace_rays, d_trace_hits;   // spt_trace_rays staging (capacities in rays: 6 and 11 floats each)
+    DevBuf<float> d_range_rays;                 // spt_trace_*_range staging (32-byte rays; the hits go to d_trace_hits)
     // spt_trace_spheres*: the rays a walk hands to the exhaustive loop (one launch's worth), {count of the launch, pad, total of the query}, the
     // query's completion (a query waits for its predecessor: they share these), what the last query ran through (-1: none yet)
-    uint32_t* d_qlist = nullptr; size_t qlist_cap = 0; uint32_t* d_qcount = nullptr;
+    DevBuf<uint32_t> d_qlist, d_qcount;
     hipEvent_t ev_query = nullptr; bool query_pending = false; int query_path = -1;
     std::vector<float4> h_geom;      // host copy of the sphere table {centre, r*r} and the radii: its hierarchy is built on demand
     std::vector<float> h_radius;
@@ -103,55 +141,41 @@ struct spt_ctx {
     bool grid_ready = false;         // the tables below belong to the current sphere scene and the scene qualifies
     int grid_global = 0;             // ... 1: every table stays in global memory, 2: the sphere records do, the grid is staged in LDS (spt_grid.hip WHERE)
     spt::GridParams grid{};
-    uint32_t* d_grid_cells = nullptr; uint16_t* d_grid_refs = nullptr; uint32_t* d_grid_always = nullptr;
+    DevBuf<uint32_t> d_grid_cells; DevBuf<uint16_t> d_grid_refs; DevBuf<uint32_t> d_grid_always;
     std::string grid_why;            // why the current scene does not run on the grid kernel
     bool sbvh_ready = false;
-    float4* d_sbvh_nodes = nullptr; float4* d_sbvh_geom = nullptr; uint32_t* d_sbvh_index = nullptr; uint32_t* d_sbvh_always = nullptr;
+    DevBuf<float4> d_sbvh_nodes, d_sbvh_geom; DevBuf<uint32_t> d_sbvh_index, d_sbvh_always;
     uint32_t sbvh_nalways = 0, sbvh_depth = 0;
     std::vector<float4> h_tris;      // host copy of the triangle records: the hierarchy is built from it on demand
     int accel = SPT_ACCEL_AUTO;            // mesh scenes (spt_set_mesh_accel): one of the two modes that return the exhaustive loop's Hit for every ray (spt_tribvh.h)
     float mesh_ratio = -1.f;               // closest-hit queries per sample of the last synchronised launch of this mesh scene (-1: none yet): SPT_ACCEL_AUTO
     int last_mesh_mode = SPT_ACCEL_EXHAUSTIVE;   // what the last mesh launch / query ran through
     bool bvh_ready = false;          // the hierarchy below belongs to the current mesh scene
-    float4* d_bvh_nodes = nullptr; float4* d_bvh_tris = nullptr; uint32_t* d_bvh_index = nullptr;
-    float4* d_flat_lines = nullptr; uint32_t* d_flat_line_index = nullptr; uint32_t nline_slots = 0; bool bvh_flat = false;     // thin triangles as a table (spt_tribvh.h (3))
-    uint32_t* d_cam_planes = nullptr; uint32_t ncam = 0; size_t cam_cap = 0; float cam_key[4] = {0, 0, 0, 0}; bool cam_valid = false;   // spt_bvh.h camera_planes of the last pinhole origin
-    float4* d_bvh_cones = nullptr; float4* d_plane_nodes = nullptr; float4* d_line_nodes = nullptr; bool have_planes = false, have_lines = false;   // spt_tribvh.h
+    DevBuf<float4> d_bvh_nodes, d_bvh_tris; DevBuf<uint32_t> d_bvh_index;
+    DevBuf<float4> d_flat_lines; DevBuf<uint32_t> d_flat_line_index; uint32_t nline_slots = 0; bool bvh_flat = false;     // thin triangles as a table (spt_tribvh.h (3))
+    DevBuf<uint32_t> d_cam_planes; uint32_t ncam = 0; float cam_key[4] = {0, 0, 0, 0}; bool cam_valid = false;   // spt_bvh.h camera_planes of the last pinhole origin
+    DevBuf<float4> d_bvh_cones, d_plane_nodes, d_line_nodes; bool have_planes = false, have_lines = false;   // spt_tribvh.h
     uint32_t bvh_nodes = 0, bvh_depth = 0, bvh_leaves = 0;
     uint32_t bvh_thin = 0;           // thin triangles of the structures above (spt_mesh_line_form)
     int line_form = 0;               // spt_set_line_form: build_bvh's `form` for the structures built from now on (0 = by count)
     uint32_t ntris = 0, ninst = 0;
     bool inst_scene = false;         // the current mesh scene is instanced (spt_set_instances): ntris = min(tri_sum, 2^32 - 1), ninst = instances
     InstScene inst;
-    float* d_accum = nullptr;      // spt_progressive_*: accumBuffer (smallpt.cpp:881-883) and the current frame, w*h*3 floats each
-    float* d_frame = nullptr;
+    DevBuf<float> d_accum;         // spt_progressive_*: accumBuffer (smallpt.cpp:881-883) and the current frame, w*h*3 floats each
+    DevBuf<float> d_frame;
     uint32_t prog_w = 0, prog_h = 0;
-    uint32_t aov_mask = 0;         // spt_progressive_aov_*: the selected kinds; per kind an accumulation buffer and a frame, w*h*3 floats each
-    float* d_aov_accum[6] = {}; float* d_aov_frame[6] = {};
-    // spt_progressive_moments_begin (owner): per-pixel sum of the frames' squared luminance (w*h floats), the frames summed into it and into
-    // accumBuffer since the last clearing frame, and whether a clearing frame has been issued since the begin (the variance is defined)
-    float* d_m2 = nullptr; uint32_t m2_frames = 0; bool m2_valid = false;
-    // spt_denoise*: packed guides (3 planes of float4), two float4 colour images (ping-pong) and the float3 result of the progressive
-    // snapshot, grown on demand; calls of one context run one after another, whatever their streams (they share these)
-    float4* d_dn_guides = nullptr; size_t dn_guides_cap = 0;
-    float4* d_dn_ping = nullptr; size_t dn_ping_cap = 0;
-    float4* d_dn_pong = nullptr; size_t dn_pong_cap = 0;
-    float* d_dn_out = nullptr; size_t dn_out_cap = 0;
+    ProgressiveAov aov;
+    Moments m2;
+    DenoiseScratch dn;
     hipEvent_t ev_denoise = nullptr; bool denoise_recorded = false;
     int denoise_form = 0;          // spt_set_denoise_form (spt_internal.h): 1 = the direct-load pass at every step
     bool denoise_timed = false;    // spt_set_denoise_timing: events around every kernel of a filter call (spt_denoise_last_ms)
     hipEvent_t dn_ev[7] = {}; uint32_t dn_ev_count = 0;
     // spt_display*: the threshold table {T[1..255], +inf} on the device (uploaded by the first display call, kept until spt_destroy) and the
     // 8-bit image of the host forms and the snapshot, grown on demand (they run on the context's stream and block, so nothing else reads it)
-    float* d_disp_table = nullptr;
-    uint8_t* d_disp8 = nullptr; size_t disp8_cap = 0;
-    // spt_progressive_temporal_*: the parameters of the begin, two histories (hist[cur] holds the last frame's), the loop's own radiance
-    // frame, its NORMAL / ALBEDO / POSITION / COVERAGE frames (one allocation), the {mean rgb | var | len} image of the last frame, that
-    // frame's camera and 4 * samps, and whether hist[cur] is a history yet
-    bool tp_on = false; spt_temporal_params tp_params{};
-    float4* d_tp_hist[2] = {nullptr, nullptr}; int tp_cur = 0; bool tp_have = false;
-    float* d_tp_frame = nullptr; float* d_tp_guides = nullptr; float* d_tp_out = nullptr;
-    spt_camera tp_cam{}; uint32_t tp_samples = 0;
+    DevBuf<float> d_disp_table;
+    DevBuf<uint8_t> d_disp8;
+    Temporal tp;
     hipEvent_t ev_acc = nullptr;   // owner of an accumBuffer: completion of the most recent accumulation (any lane's stream)
     bool acc_recorded = false;
     bool frame_in_flight = false;  // a spt_progressive_frame_async of this lane has not been waited for
@@ -160,12 +184,10 @@ struct spt_ctx {
     uint32_t frames_in_flight_hint = 1;   // set by spt_progressive_frame_async for its launch: lanes of the loop (sizes a short launch's grid)
     unsigned long long pool_stats[24] = {};  // batches per class [3], lanes per class [3], watchdog hits, tail batches, tail lanes, full batches
     // scratch
-    float4* d_cells = nullptr;
-    size_t cells_cap = 0;          // in float4
-    float* d_out = nullptr;        // image buffer for spt_render
-    size_t out_cap = 0;            // in floats
-    uint32_t* d_queue = nullptr;   // 1 x u32 queue head + 2 x u64 counters (one 32-byte allocation)
-    unsigned long long* d_counters = nullptr;
+    DevBuf<float4> d_cells;
+    DevBuf<float> d_out;           // image buffer for spt_render
+    DevBuf<uint32_t> d_queue;      // 1 x u32 queue head + 2 x u64 counters (one allocation)
+    unsigned long long* d_counters = nullptr;   // ... the counters: an alias into d_queue, not an owner
     // tuning
     uint32_t blocks_per_cu = 0;
     uint32_t variant = 0;
@@ -175,8 +197,7 @@ struct spt_ctx {
     int grid_force_global = 0;
     uint32_t gq[5] = {192u, 96u, 24u, 32u, 4u};
     // pool kernel, cost-ordered dispatch (spt_kernel.h KParams::chunk_order): tables of the last pool launch and the view they belong to
-    uint32_t* d_chunk_tables = nullptr;   // order[cap] | clock[2 * cap] | 512 words of the sorting kernels
-    size_t chunk_cap = 0;
+    DevBuf<uint32_t> d_chunk_tables;      // order[cap] | clock[2 * cap] | 512 words of the sorting kernels (cap in chunks)
     bool order_valid = false;
     std::vector<unsigned char> order_key;  // camera, image, band, samples, scene generation, seed: an identical next launch reuses the order
     std::vector<unsigned char> last_pool_key;   // ... of the last pool launch, recorded or not: a launch records only when it repeats its predecessor
@@ -209,19 +230,6 @@ struct spt_ctx {
         hipError_t e__ = (call);                                                                 \
         if (e__ != hipSuccess) return (ctx)->fail("%s failed: %s", #call, hipGetErrorString(e__)); \
     } while (0)
-
-// Grows a device scratch buffer to room for `need` elements (nothing to do when it has it): frees, allocates `alloc` elements (by default
-// `need`) and sets the capacity only once the allocation stands.  The contents are not kept.
-template <typename T>
-static hipError_t grow(T*& ptr, size_t& cap, size_t need, size_t alloc = 0)
-{
-    if (need <= cap) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr; cap = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), (alloc ? alloc : need) * sizeof(T));
-    if (e == hipSuccess) cap = need;
-    return e;
-}
 
 extern "C" {
 
@@ -269,106 +277,21 @@ int spt_create(int device_id, spt_ctx** out)
     if ((e = hipEventCreate(&c->ev_mid)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreate(&c->ev_stop)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    void* p = nullptr;
-    if ((e = hipMalloc(&p, 256)) != hipSuccess) return bail("hipMalloc", e);
-    c->d_queue = static_cast<uint32_t*>(p);
-    c->d_counters = reinterpret_cast<unsigned long long*>(static_cast<char*>(p) + 16);
+    if ((e = c->d_queue.grow(64)) != hipSuccess) return bail("hipMalloc", e);
+    c->d_counters = reinterpret_cast<unsigned long long*>(c->d_queue.ptr + 4);
     *out = c;
     return 0;
 }
 
-static void denoise_free(spt_ctx* c)
-{
-    if (c->d_dn_guides) (void)hipFree(c->d_dn_guides);
-    if (c->d_dn_ping) (void)hipFree(c->d_dn_ping);
-    if (c->d_dn_pong) (void)hipFree(c->d_dn_pong);
-    if (c->d_dn_out) (void)hipFree(c->d_dn_out);
-    c->d_dn_guides = c->d_dn_ping = c->d_dn_pong = nullptr; c->d_dn_out = nullptr;
-    c->dn_guides_cap = c->dn_ping_cap = c->dn_pong_cap = c->dn_out_cap = 0;
-}
-
-static void display_free(spt_ctx* c)
-{
-    if (c->d_disp8) (void)hipFree(c->d_disp8);
-    c->d_disp8 = nullptr; c->disp8_cap = 0;
-}
-
-static void moments_free(spt_ctx* c)
-{
-    if (c->d_m2) (void)hipFree(c->d_m2);
-    c->d_m2 = nullptr; c->m2_frames = 0; c->m2_valid = false;
-}
-
-static void temporal_free(spt_ctx* c)
-{
-    for (float4*& hst : c->d_tp_hist) { if (hst) (void)hipFree(hst); hst = nullptr; }
-    if (c->d_tp_frame) (void)hipFree(c->d_tp_frame);
-    if (c->d_tp_guides) (void)hipFree(c->d_tp_guides);
-    if (c->d_tp_out) (void)hipFree(c->d_tp_out);
-    c->d_tp_frame = c->d_tp_guides = c->d_tp_out = nullptr;
-    c->tp_on = c->tp_have = false; c->tp_cur = 0; c->tp_samples = 0;
-}
-
-static void progressive_aov_free(spt_ctx* c)
-{
-    for (int k = 0; k < 6; ++k) {
-        if (c->d_aov_accum[k]) (void)hipFree(c->d_aov_accum[k]);
-        if (c->d_aov_frame[k]) (void)hipFree(c->d_aov_frame[k]);
-        c->d_aov_accum[k] = c->d_aov_frame[k] = nullptr;
-    }
-    c->aov_mask = 0;
-}
-
+// The context's device buffers go with `delete c` (DevBuf): with the device set and the stream drained.
 void spt_destroy(spt_ctx* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
-    if (c->d_geom) (void)hipFree(c->d_geom);
-    if (c->d_mat) (void)hipFree(c->d_mat);
-    if (c->d_cells) (void)hipFree(c->d_cells);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_stack) (void)hipFree(c->d_stack);
-    if (c->d_accum) (void)hipFree(c->d_accum);
-    if (c->d_frame) (void)hipFree(c->d_frame);
-    progressive_aov_free(c);
-    moments_free(c);
-    temporal_free(c);
-    denoise_free(c);
-    display_free(c);
-    if (c->d_disp_table) (void)hipFree(c->d_disp_table);
     if (c->ev_denoise) (void)hipEventDestroy(c->ev_denoise);
     for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
-    if (c->d_tris) (void)hipFree(c->d_tris);
-    if (c->d_tri_index) (void)hipFree(c->d_tri_index);
-    if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
-    if (c->d_trace_hits) (void)hipFree(c->d_trace_hits);
-    if (c->d_range_rays) (void)hipFree(c->d_range_rays);
-    if (c->d_qlist) (void)hipFree(c->d_qlist);
-    if (c->d_qcount) (void)hipFree(c->d_qcount);
     if (c->ev_query) (void)hipEventDestroy(c->ev_query);
-    if (c->d_grid_cells) (void)hipFree(c->d_grid_cells);
-    if (c->d_grid_refs) (void)hipFree(c->d_grid_refs);
-    if (c->d_grid_always) (void)hipFree(c->d_grid_always);
-    if (c->d_sbvh_nodes) (void)hipFree(c->d_sbvh_nodes);
-    if (c->d_sbvh_geom) (void)hipFree(c->d_sbvh_geom);
-    if (c->d_sbvh_index) (void)hipFree(c->d_sbvh_index);
-    if (c->d_sbvh_always) (void)hipFree(c->d_sbvh_always);
-    if (c->d_bvh_nodes) (void)hipFree(c->d_bvh_nodes);
-    if (c->d_bvh_tris) (void)hipFree(c->d_bvh_tris);
-    if (c->d_bvh_index) (void)hipFree(c->d_bvh_index);
-    if (c->d_bvh_cones) (void)hipFree(c->d_bvh_cones);
-    if (c->d_cam_planes) (void)hipFree(c->d_cam_planes);
-    if (c->d_flat_line_index) (void)hipFree(c->d_flat_line_index);
-    if (c->d_flat_lines) (void)hipFree(c->d_flat_lines);
-    if (c->d_plane_nodes) (void)hipFree(c->d_plane_nodes);
-    if (c->d_line_nodes) (void)hipFree(c->d_line_nodes);
-    if (c->d_verts) (void)hipFree(c->d_verts);
-    if (c->d_inst_first) (void)hipFree(c->d_inst_first);
-    if (c->d_mesh_mats) (void)hipFree(c->d_mesh_mats);
-    for (void* p : c->inst.allocs) (void)hipFree(p);
-    if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_mid) (void)hipEventDestroy(c->ev_mid);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
@@ -463,15 +386,6 @@ static int set_scene_impl(spt_ctx* c, const spt_sphere* s, uint32_t n)
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
     const uint32_t cap = n ? n : 1;
-    if (cap > c->scene_cap) {
-        if (c->d_geom) (void)hipFree(c->d_geom);
-        if (c->d_mat) (void)hipFree(c->d_mat);
-        c->d_geom = c->d_mat = nullptr;
-        c->scene_cap = 0;
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_geom), sizeof(float4) * cap));
-        SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_mat), sizeof(float4) * 3 * cap));
-        c->scene_cap = cap;
-    }
     std::vector<float4> geom(cap), mat(3 * (size_t)cap);
     for (uint32_t i = 0; i < n; ++i) {
         const spt_sphere& sp = s[i];
@@ -488,8 +402,17 @@ static int set_scene_impl(spt_ctx* c, const spt_sphere* s, uint32_t n)
         mat[3 * i + 1] = make_float4(sp.color[0], sp.color[1], sp.color[2], pmax);
         mat[3 * i + 2] = make_float4(sp.color[0] * inv, sp.color[1] * inv, sp.color[2] * inv, 0.0f);
     }
-    SPT_HIP(c, hipMemcpy(c->d_geom, geom.data(), sizeof(float4) * cap, hipMemcpyHostToDevice));
-    SPT_HIP(c, hipMemcpy(c->d_mat, mat.data(), sizeof(float4) * 3 * cap, hipMemcpyHostToDevice));
+    // The two tables are reused by capacity, so the previous table does not survive this point: a failure leaves no sphere table at all
+    // (d_geom == nullptr: every entry point refuses), and a mesh scene, if one is current, as it was.
+    hipError_t e = c->d_geom.grow(cap);
+    if (e == hipSuccess) e = c->d_mat.grow(cap, 3 * (size_t)cap);
+    if (e == hipSuccess) e = hipMemcpy(c->d_geom, geom.data(), sizeof(float4) * cap, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->d_mat, mat.data(), sizeof(float4) * 3 * cap, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        c->d_geom.reset(); c->d_mat.reset();
+        c->n = 0; c->grid_ready = c->sbvh_ready = false;
+        return c->fail("spt_set_scene: sphere tables: %s", hipGetErrorString(e));
+    }
     c->n = n;
     ++c->scene_gen;
     c->mesh_scene = false;
@@ -585,16 +508,10 @@ static int build_sphere_grid_tables(spt_ctx* c)
     const spt::SphereGrid& g = choice.g;
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
-    auto upload = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
-        if (dptr) (void)hipFree(dptr);
-        dptr = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), bytes ? bytes : 16);
-        if (e != hipSuccess || bytes == 0) return e;
-        return hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice);
-    };
-    SPT_HIP(c, upload(c->d_grid_cells, g.cells.data(), g.cells.size() * sizeof(uint32_t)));
-    SPT_HIP(c, upload(c->d_grid_refs, g.refs.data(), g.refs.size() * sizeof(uint16_t)));
-    SPT_HIP(c, upload(c->d_grid_always, g.always.data(), g.always.size() * sizeof(uint32_t)));
+    // (grid_ready is false from the first line on: a failure below leaves no grid, and the scene keeps the other kernels)
+    SPT_HIP(c, c->d_grid_cells.upload(g.cells.data(), g.cells.size() * sizeof(uint32_t)));
+    SPT_HIP(c, c->d_grid_refs.upload(g.refs.data(), g.refs.size() * sizeof(uint16_t)));
+    SPT_HIP(c, c->d_grid_always.upload(g.always.data(), g.always.size() * sizeof(uint32_t)));
     c->grid = g.P;
     c->grid_why.clear();
     c->grid_ready = true;
@@ -619,17 +536,11 @@ static int build_sphere_accel(spt_ctx* c)
     spt::build_sphere_bvh(c->h_geom.data(), c->h_radius.data(), c->n, bvh);
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
-    auto upload = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
-        if (dptr) (void)hipFree(dptr);
-        dptr = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), bytes ? bytes : 16);
-        if (e != hipSuccess || bytes == 0) return e;
-        return hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice);
-    };
-    SPT_HIP(c, upload(c->d_sbvh_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float4)));
-    SPT_HIP(c, upload(c->d_sbvh_geom, bvh.tris.data(), bvh.tris.size() * sizeof(float4)));
-    SPT_HIP(c, upload(c->d_sbvh_index, bvh.index.data(), bvh.index.size() * sizeof(uint32_t)));
-    SPT_HIP(c, upload(c->d_sbvh_always, bvh.always.data(), bvh.always.size() * sizeof(uint32_t)));
+    c->sbvh_ready = false;                          // a failure below leaves no hierarchy
+    SPT_HIP(c, c->d_sbvh_nodes.upload(bvh.nodes.data(), bvh.nodes.size() * sizeof(float4)));
+    SPT_HIP(c, c->d_sbvh_geom.upload(bvh.tris.data(), bvh.tris.size() * sizeof(float4)));
+    SPT_HIP(c, c->d_sbvh_index.upload(bvh.index.data(), bvh.index.size() * sizeof(uint32_t)));
+    SPT_HIP(c, c->d_sbvh_always.upload(bvh.always.data(), bvh.always.size() * sizeof(uint32_t)));
     c->sbvh_nalways = (uint32_t)bvh.always.size(); c->sbvh_depth = bvh.depth;
     c->sbvh_ready = true;
     return 0;
@@ -891,18 +802,17 @@ static int set_meshes_impl(spt_ctx* c, const spt_mesh* meshes, uint32_t nmesh, c
         specular = specular || materials[i].refl != SPT_DIFF;
     }
     first[nmesh] = (uint32_t)t;
-    auto upload = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
-        if (dptr) (void)hipFree(dptr);
-        dptr = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), bytes);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice);
-    };
-    SPT_HIP(c, upload(c->d_tris, tris.data(), tris.size() * sizeof(float4)));
-    SPT_HIP(c, upload(c->d_tri_index, tidx.data(), tidx.size() * sizeof(uint4)));
-    SPT_HIP(c, upload(c->d_verts, verts.data(), verts.size() * sizeof(float4)));
-    SPT_HIP(c, upload(c->d_inst_first, first.data(), first.size() * sizeof(uint32_t)));
-    SPT_HIP(c, upload(c->d_mesh_mats, mats.data(), mats.size() * sizeof(float4)));
+    DevBuf<float4> d_tris, d_verts, d_mats;
+    DevBuf<uint4> d_tidx;
+    DevBuf<uint32_t> d_first;
+    SPT_HIP(c, d_tris.upload(tris.data(), tris.size() * sizeof(float4)));
+    SPT_HIP(c, d_tidx.upload(tidx.data(), tidx.size() * sizeof(uint4)));
+    SPT_HIP(c, d_verts.upload(verts.data(), verts.size() * sizeof(float4)));
+    SPT_HIP(c, d_first.upload(first.data(), first.size() * sizeof(uint32_t)));
+    SPT_HIP(c, d_mats.upload(mats.data(), mats.size() * sizeof(float4)));
+    // commit: the mesh scene becomes current (a failure above has left the previous scene as it was)
+    c->d_tris = std::move(d_tris); c->d_tri_index = std::move(d_tidx); c->d_verts = std::move(d_verts);
+    c->d_inst_first = std::move(d_first); c->d_mesh_mats = std::move(d_mats);
     c->ntris = (uint32_t)ntris; c->ninst = nmesh;
     free_inst_scene(c);
     c->mesh_scene = true;
@@ -921,26 +831,20 @@ static int build_accel(spt_ctx* c)
     spt::build_bvh(c->h_tris.data(), c->ntris, bvh, c->line_form);
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
-    auto upload = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
-        if (dptr) (void)hipFree(dptr);
-        dptr = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), bytes);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice);
-    };
-    SPT_HIP(c, upload(c->d_bvh_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float4)));
-    SPT_HIP(c, upload(c->d_bvh_tris, bvh.tris.data(), bvh.tris.size() * sizeof(float4)));
-    SPT_HIP(c, upload(c->d_bvh_index, bvh.index.data(), bvh.index.size() * sizeof(uint32_t)));
+    c->bvh_ready = false;                           // a failure below leaves no hierarchy: the exhaustive loop keeps the scene
+    SPT_HIP(c, c->d_bvh_nodes.upload(bvh.nodes.data(), bvh.nodes.size() * sizeof(float4)));
+    SPT_HIP(c, c->d_bvh_tris.upload(bvh.tris.data(), bvh.tris.size() * sizeof(float4)));
+    SPT_HIP(c, c->d_bvh_index.upload(bvh.index.data(), bvh.index.size() * sizeof(uint32_t)));
     c->have_planes = !bvh.planes.empty(); c->have_lines = !bvh.lines.empty();
-    if (c->have_planes) SPT_HIP(c, upload(c->d_plane_nodes, bvh.planes.data(), bvh.planes.size() * sizeof(float4)));
-    if (c->have_lines) SPT_HIP(c, upload(c->d_line_nodes, bvh.lines.data(), bvh.lines.size() * sizeof(float4)));
+    if (c->have_planes) SPT_HIP(c, c->d_plane_nodes.upload(bvh.planes.data(), bvh.planes.size() * sizeof(float4)));
+    if (c->have_lines) SPT_HIP(c, c->d_line_nodes.upload(bvh.lines.data(), bvh.lines.size() * sizeof(float4)));
     c->bvh_flat = bvh.flat && bvh.thin_count; c->nline_slots = (uint32_t)bvh.flat_lines.size(); c->cam_valid = false;
     c->bvh_thin = bvh.thin_count;
     if (c->bvh_flat) {
-        SPT_HIP(c, upload(c->d_flat_lines, bvh.flat_lines.data(), bvh.flat_lines.size() * sizeof(float4)));
-        SPT_HIP(c, upload(c->d_flat_line_index, bvh.flat_line_index.data(), bvh.flat_line_index.size() * sizeof(uint32_t)));
+        SPT_HIP(c, c->d_flat_lines.upload(bvh.flat_lines.data(), bvh.flat_lines.size() * sizeof(float4)));
+        SPT_HIP(c, c->d_flat_line_index.upload(bvh.flat_line_index.data(), bvh.flat_line_index.size() * sizeof(uint32_t)));
     }
-    SPT_HIP(c, upload(c->d_bvh_cones, bvh.cones.data(), bvh.cones.size() * sizeof(float4)));
+    SPT_HIP(c, c->d_bvh_cones.upload(bvh.cones.data(), bvh.cones.size() * sizeof(float4)));
     c->bvh_nodes = (uint32_t)(bvh.nodes.size() / 4); c->bvh_depth = bvh.depth; c->bvh_leaves = bvh.leaves;
     c->bvh_ready = true;
     return 0;
@@ -949,23 +853,8 @@ static int build_accel(spt_ctx* c)
 // ---- mesh instances (spt_set_instances; spt_instance.h) ----
 static void free_inst_scene(spt_ctx* c)
 {
-    for (void* p : c->inst.allocs) (void)hipFree(p);
     c->inst = InstScene{};
     c->inst_scene = false;
-}
-
-extern "C++" {
-template <typename T>
-static hipError_t inst_upload(InstScene& s, T*& dptr, const void* src, size_t bytes)
-{
-    dptr = nullptr;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess) return e;
-    s.allocs.push_back(p);
-    dptr = static_cast<T*>(p);
-    return bytes ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-}
 }
 
 // Builds every model's structures (build_accel's products, over the model alone) into its descriptor and uploads the descriptors again.
@@ -980,15 +869,15 @@ static int build_inst_accel(spt_ctx* c, InstScene& s, const char* who)
         spt::MParams M = s.models[m];                                  // (stored only once complete)
         spt::Bvh bvh;
         spt::build_bvh(s.tris[m].data(), M.ntris, bvh, c->line_form);
-        hipError_t e = inst_upload(s, M.bvh_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float4));
-        if (e == hipSuccess) e = inst_upload(s, M.bvh_tris, bvh.tris.data(), bvh.tris.size() * sizeof(float4));
-        if (e == hipSuccess) e = inst_upload(s, M.bvh_index, bvh.index.data(), bvh.index.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = inst_upload(s, M.bvh_cones, bvh.cones.data(), bvh.cones.size() * sizeof(float4));
-        if (e == hipSuccess && !bvh.planes.empty()) e = inst_upload(s, M.plane_nodes, bvh.planes.data(), bvh.planes.size() * sizeof(float4));
-        if (e == hipSuccess && !bvh.lines.empty()) e = inst_upload(s, M.line_nodes, bvh.lines.data(), bvh.lines.size() * sizeof(float4));
+        hipError_t e = s.add_table(M.bvh_nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float4));
+        if (e == hipSuccess) e = s.add_table(M.bvh_tris, bvh.tris.data(), bvh.tris.size() * sizeof(float4));
+        if (e == hipSuccess) e = s.add_table(M.bvh_index, bvh.index.data(), bvh.index.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = s.add_table(M.bvh_cones, bvh.cones.data(), bvh.cones.size() * sizeof(float4));
+        if (e == hipSuccess && !bvh.planes.empty()) e = s.add_table(M.plane_nodes, bvh.planes.data(), bvh.planes.size() * sizeof(float4));
+        if (e == hipSuccess && !bvh.lines.empty()) e = s.add_table(M.line_nodes, bvh.lines.data(), bvh.lines.size() * sizeof(float4));
         if (e == hipSuccess && bvh.flat && bvh.thin_count) {
-            e = inst_upload(s, M.flat_lines, bvh.flat_lines.data(), bvh.flat_lines.size() * sizeof(float4));
-            if (e == hipSuccess) e = inst_upload(s, M.flat_line_index, bvh.flat_line_index.data(), bvh.flat_line_index.size() * sizeof(uint32_t));
+            e = s.add_table(M.flat_lines, bvh.flat_lines.data(), bvh.flat_lines.size() * sizeof(float4));
+            if (e == hipSuccess) e = s.add_table(M.flat_line_index, bvh.flat_line_index.data(), bvh.flat_line_index.size() * sizeof(uint32_t));
             M.nline_slots = (uint32_t)bvh.flat_lines.size();
         }
         if (e != hipSuccess) return c->fail("%s: %s", who, hipGetErrorString(e));
@@ -1034,7 +923,6 @@ static int set_instances_impl(spt_ctx* c, const spt_mesh* models, uint32_t nmode
     // per model: the tables of a spt_set_meshes scene holding that model alone (instance field 0)
     s.tris.resize(nmodels);
     s.models.resize(nmodels);
-    auto fail_free = [&](hipError_t e) { for (void* p : s.allocs) (void)hipFree(p); return c->fail("%s: %s", who, hipGetErrorString(e)); };
     for (uint32_t m = 0; m < nmodels; ++m) {
         const spt_mesh& mesh = models[m];
         std::vector<float4>& tris = s.tris[m];
@@ -1046,28 +934,21 @@ static int set_instances_impl(spt_ctx* c, const spt_mesh* models, uint32_t nmode
         const uint32_t first[2] = {0u, mesh.ntris};
         spt::MParams& M = s.models[m];
         M = spt::MParams{};
-        hipError_t e = inst_upload(s, M.tris, tris.data(), tris.size() * sizeof(float4));
-        if (e == hipSuccess) e = inst_upload(s, M.tri_index, tidx.data(), tidx.size() * sizeof(uint4));
-        if (e == hipSuccess) e = inst_upload(s, M.verts, verts.data(), verts.size() * sizeof(float4));
-        if (e == hipSuccess) e = inst_upload(s, M.inst_first_tri, first, sizeof first);
-        if (e != hipSuccess) return fail_free(e);
+        hipError_t e = s.add_table(M.tris, tris.data(), tris.size() * sizeof(float4));
+        if (e == hipSuccess) e = s.add_table(M.tri_index, tidx.data(), tidx.size() * sizeof(uint4));
+        if (e == hipSuccess) e = s.add_table(M.verts, verts.data(), verts.size() * sizeof(float4));
+        if (e == hipSuccess) e = s.add_table(M.inst_first_tri, first, sizeof first);
+        if (e != hipSuccess) return c->fail("%s: %s", who, hipGetErrorString(e));
         M.ntris = mesh.ntris; M.ninst = 1;
         tris.resize(3 * (size_t)mesh.ntris);
     }
-    hipError_t e = inst_upload(s, s.d_models, s.models.data(), s.models.size() * sizeof(spt::MParams));
-    if (e == hipSuccess) e = inst_upload(s, s.d_inst, recs.data(), recs.size() * sizeof(spt::InstRec));
-    if (e == hipSuccess) e = inst_upload(s, s.d_mats, mats.data(), mats.size() * sizeof(float4));
-    if (e != hipSuccess) return fail_free(e);
+    hipError_t e = s.d_models.upload(s.models.data(), s.models.size() * sizeof(spt::MParams));
+    if (e == hipSuccess) e = s.d_inst.upload(recs.data(), recs.size() * sizeof(spt::InstRec));
+    if (e == hipSuccess) e = s.d_mats.upload(mats.data(), mats.size() * sizeof(float4));
+    if (e != hipSuccess) return c->fail("%s: %s", who, hipGetErrorString(e));
     s.ninst = ninst;
-    if (c->accel != SPT_ACCEL_EXHAUSTIVE) {
-        try {
-            if (build_inst_accel(c, s, who)) { for (void* p : s.allocs) (void)hipFree(p); return 1; }
-        } catch (...) {
-            for (void* p : s.allocs) (void)hipFree(p);
-            throw;
-        }
-    }
-    // commit: the instanced scene becomes current
+    if (c->accel != SPT_ACCEL_EXHAUSTIVE && build_inst_accel(c, s, who)) return 1;
+    // commit: the instanced scene becomes current (a failure above has dropped s and left the previous scene as it was)
     free_inst_scene(c);
     c->inst = std::move(s);
     c->inst_scene = true;
@@ -1264,16 +1145,8 @@ int spt_trace_rays_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hi
 // hits buffer), kept between calls (traceRays is called once per bounce by the reference's render loop)
 static hipError_t ensure_trace_staging(spt_ctx* c, uint64_t n)
 {
-    hipError_t e = hipSuccess;
-    if (n > c->trace_cap) {
-        if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
-        if (c->d_trace_hits) (void)hipFree(c->d_trace_hits);
-        c->d_trace_rays = c->d_trace_hits = nullptr; c->trace_cap = 0;
-        e = hipMalloc(reinterpret_cast<void**>(&c->d_trace_rays), n * sizeof(spt_ray));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_trace_hits), n * sizeof(spt_hit));
-        if (e == hipSuccess) c->trace_cap = n;
-    }
-    return e;
+    const hipError_t e = c->d_trace_rays.grow(n, n * (sizeof(spt_ray) / sizeof(float)));
+    return e == hipSuccess ? c->d_trace_hits.grow(n, n * (sizeof(spt_hit) / sizeof(float))) : e;
 }
 
 int spt_trace_rays(spt_ctx* c, const spt_ray* rays, uint64_t n, spt_hit* hits)
@@ -1325,9 +1198,9 @@ static int sphere_query_enqueue(spt_ctx* c, const float* d_rays, uint64_t n, flo
     if (c->sphere_accel == SPT_ACCEL_GRID && c->grid_ready) path = spt::kQueryGrid;
     else if (c->sphere_accel != SPT_ACCEL_EXHAUSTIVE && c->sbvh_ready && !c->needs_guard) path = spt::kQueryBvh;
     if (!c->ev_query) SPT_HIP(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
-    if (!c->d_qcount) SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_qcount), 16));
+    SPT_HIP(c, c->d_qcount.grow(4));
     const uint64_t slice_cap = n < spt::kQuerySlice ? n : spt::kQuerySlice;
-    if (path != spt::kQueryExhaustive) SPT_HIP(c, grow(c->d_qlist, c->qlist_cap, slice_cap));   // (hipFree waits for the device: no launch still reads the old list)
+    if (path != spt::kQueryExhaustive) SPT_HIP(c, c->d_qlist.grow(slice_cap));   // (hipFree waits for the device: no launch still reads the old list)
     if (c->query_pending) SPT_HIP(c, hipStreamWaitEvent(st, c->ev_query, 0));   // the previous query (any stream) has released the list
     SPT_HIP(c, hipMemsetAsync(c->d_qcount, 0, 16, st));
     const int guard_all = c->needs_guard ? 1 : 0;
@@ -1519,9 +1392,8 @@ int spt_occluded_rays(spt_ctx* c, const spt_ray* rays, const float* tmax, uint64
 static hipError_t ensure_range_staging(spt_ctx* c, uint64_t n)
 {
     static_assert(sizeof(spt_ray_range) == 32, "OptixRay layout (RTP_BUFFER_FORMAT_RAY_ORIGIN_TMIN_DIRECTION_TMAX)");
-    hipError_t e = ensure_trace_staging(c, n);
-    if (e == hipSuccess) e = grow(c->d_range_rays, c->range_cap, (size_t)n * (sizeof(spt_ray_range) / sizeof(float)));
-    return e;
+    const hipError_t e = ensure_trace_staging(c, n);
+    return e == hipSuccess ? c->d_range_rays.grow((size_t)n * (sizeof(spt_ray_range) / sizeof(float))) : e;
 }
 
 int spt_trace_spheres_range_device(spt_ctx* c, const void* d_rays, uint64_t n, void* d_hits, void* hip_stream)
@@ -1726,7 +1598,7 @@ static int camera_plane_list(spt_ctx* c, const spt_camera* cam, hipStream_t st, 
     if (!c->cam_valid || std::memcmp(c->cam_key, key, sizeof c->cam_key) != 0) {
         std::vector<uint32_t> list;
         spt::camera_planes(c->h_tris.data(), c->ntris, cam->origin, extra, list);
-        SPT_HIP(c, grow(c->d_cam_planes, c->cam_cap, list.size()));
+        SPT_HIP(c, c->d_cam_planes.grow(list.size()));
         if (!list.empty()) SPT_HIP(c, hipMemcpyAsync(c->d_cam_planes, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         if (!list.empty()) SPT_HIP(c, hipStreamSynchronize(st));           // (the list is a local)
         c->ncam = (uint32_t)list.size();
@@ -1819,7 +1691,7 @@ static int finish_launch(spt_ctx* c, hipStream_t st, const spt::KParams& P, Rend
 static int launch_grid(spt_ctx* c, spt::KParams& P, hipStream_t st, const float* radiance, uint32_t flags, float* d_out)
 {
     const uint32_t threads = grid_render_threads(c), blocks = grid_render_blocks(c);
-    SPT_HIP(c, grow(c->d_stack, c->stack_cap, spt_grid_stack_floats(blocks, threads)));
+    SPT_HIP(c, c->d_stack.grow(spt_grid_stack_floats(blocks, threads)));
     P.stack = c->d_stack;
     P.watchdog_ticks = c->watchdog_ticks;
     const uint32_t lsel = (c->variant >> kTuneGridLeaveShift) & kTuneGridLeaveMask;
@@ -1835,7 +1707,7 @@ static int launch_gpool(spt_ctx* c, spt::KParams& P, spt::QParams& Q, hipStream_
     const uint32_t threads = grid_render_threads(c), blocks = grid_render_blocks(c), waves = threads / 64u;
     // one allocation: the children stack followed by the slots
     const size_t stack_floats = spt_gpool_stack_floats(blocks, waves, Q.S);
-    SPT_HIP(c, grow(c->d_stack, c->stack_cap, stack_floats + spt_gpool_slot_floats(blocks, waves, Q.S)));
+    SPT_HIP(c, c->d_stack.grow(stack_floats + spt_gpool_slot_floats(blocks, waves, Q.S)));
     P.stack = c->d_stack;
     P.watchdog_ticks = c->watchdog_ticks;
     Q.slots = reinterpret_cast<float4*>(c->d_stack + stack_floats);
@@ -1857,7 +1729,7 @@ static int launch_mesh(spt_ctx* c, spt::KParams& P, RenderKernel kernel, int mod
     const uint64_t needed = ((uint64_t)P.ntasks + 255) / 256;
     if (blocks > needed) blocks = needed;
     if (blocks < 1) blocks = 1;
-    SPT_HIP(c, grow(c->d_stack, c->stack_cap, spt_mesh_stack_floats((uint32_t)blocks)));
+    SPT_HIP(c, c->d_stack.grow(spt_mesh_stack_floats((uint32_t)blocks)));
     P.stack = c->d_stack;
     spt::MParams M{};
     if (kernel == kSphereBvh) {
@@ -1906,7 +1778,7 @@ static int launch_pool(spt_ctx* c, spt::KParams& P, const spt_camera* cam, uint6
     if (blocks < 1) blocks = 1;
     // one allocation: the children stack followed by the {task, next sample} words of every slot
     const size_t stack_floats = spt_pool_stack_floats((uint32_t)blocks, pool);
-    SPT_HIP(c, grow(c->d_stack, c->stack_cap, stack_floats + spt_pool_state_bytes((uint32_t)blocks, pool) / sizeof(float)));
+    SPT_HIP(c, c->d_stack.grow(stack_floats + spt_pool_state_bytes((uint32_t)blocks, pool) / sizeof(float)));
     P.stack = c->d_stack;
     P.slot_state = reinterpret_cast<uint2*>(c->d_stack + stack_floats);
     P.watchdog_ticks = c->watchdog_ticks;
@@ -1941,10 +1813,10 @@ static int launch_pool(spt_ctx* c, spt::KParams& P, const spt_camera* cam, uint6
     const bool repeats = key == c->last_pool_key;
     if (!(c->variant & kTuneStaticOrder) && !(flags & SPT_FLAG_ONE_SHOT) && P.samps >= 16u && nchunks <= (4u << 20) && (have_order || repeats)) {
         // order[cap] | clock[2 * cap] | 512 words of the sorting kernels; new tables hold no order
-        if (nchunks > c->chunk_cap) c->order_valid = false;
-        SPT_HIP(c, grow(c->d_chunk_tables, c->chunk_cap, nchunks, (size_t)nchunks * 3 + 512));
+        if (nchunks > c->d_chunk_tables.cap) c->order_valid = false;
+        SPT_HIP(c, c->d_chunk_tables.grow(nchunks, (size_t)nchunks * 3 + 512));
         uint32_t* const d_order = c->d_chunk_tables;
-        uint32_t* const d_clock = c->d_chunk_tables + c->chunk_cap;
+        uint32_t* const d_clock = c->d_chunk_tables + c->d_chunk_tables.cap;
         P.chunk_order = (have_order && c->order_valid) ? d_order : nullptr;     // (order_valid: the tables may just have been re-allocated)
         P.chunk_clock = d_clock;
         P.nchunks = nchunks;
@@ -1958,7 +1830,7 @@ static int launch_pool(spt_ctx* c, spt::KParams& P, const spt_camera* cam, uint6
     c->last_share = share;
     if (finish_launch(c, st, P, kPool, (uint32_t)blocks, 256, flags, d_out)) return 1;
     if (P.chunk_clock) {                                         // (after ev_stop: not part of the frame's device time, overlaps the caller's next step)
-        SPT_HIP(c, spt_pool_chunk_order(P.chunk_clock, nchunks, P.ntasks, c->d_chunk_tables, c->d_chunk_tables + 3 * c->chunk_cap, st));
+        SPT_HIP(c, spt_pool_chunk_order(P.chunk_clock, nchunks, P.ntasks, c->d_chunk_tables, c->d_chunk_tables + 3 * c->d_chunk_tables.cap, st));
         SPT_HIP(c, hipEventRecord(c->ev_order, st));
         c->order_pending = true;
         c->order_key = key;
@@ -1988,7 +1860,7 @@ static int launch_mega(spt_ctx* c, spt::KParams& P, float cam_big, hipStream_t s
     const uint64_t needed = ((uint64_t)P.ntasks + threads - 1) / threads;
     if (blocks > needed) blocks = needed;
     if (blocks < 1) blocks = 1;
-    SPT_HIP(c, grow(c->d_stack, c->stack_cap, spt_k_stack_floats((uint32_t)blocks, threads)));
+    SPT_HIP(c, c->d_stack.grow(spt_k_stack_floats((uint32_t)blocks, threads)));
     P.stack = c->d_stack;
     if (begin_launch(c, st)) return 1;
     SPT_HIP(c, spt_k_launch(&P, (uint32_t)blocks, mat_lds, (c->needs_guard || !(cam_big <= 1e15f)) ? 1 : 0, (c->variant & kTuneStats) ? 1 : 0, 1, big_block, st, radiance));
@@ -2010,7 +1882,7 @@ static int render_rows_impl(spt_ctx* c, const spt_camera* cam, uint32_t w, uint3
     SPT_HIP(c, hipSetDevice(c->device));
     if (c->pending) { SPT_HIP(c, hipEventSynchronize(c->ev_stop)); }
     c->last_aov = false;
-    SPT_HIP(c, grow(c->d_cells, c->cells_cap, (size_t)npix * 4 * nb));
+    SPT_HIP(c, c->d_cells.grow((size_t)npix * 4 * nb));
     if (cam->sampler > SPT_SAMPLER_PINHOLE) return c->fail("spt_render_rows_device: unknown camera sampler %u", cam->sampler);
 
     spt::KParams P{};
@@ -2083,8 +1955,8 @@ int spt_sync(spt_ctx* c, spt_stats* stats)
 // The staging image of the host-buffer renders; a pending launch may still write the old one.
 static int grow_out(spt_ctx* c, size_t nfl)
 {
-    if (nfl > c->out_cap && c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
-    SPT_HIP(c, grow(c->d_out, c->out_cap, nfl));
+    if (nfl > c->d_out.cap && c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+    SPT_HIP(c, c->d_out.grow(nfl));
     return 0;
 }
 
@@ -2140,7 +2012,7 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
         else SPT_HIP(c, hipEventSynchronize(c->ev_stop));
     }
     const size_t ntasks = (size_t)npix * 4 * nb;
-    SPT_HIP(c, grow(c->d_cells, c->cells_cap, ntasks * nplanes));
+    SPT_HIP(c, c->d_cells.grow(ntasks * nplanes));
     if (set) aov |= spt_aov_set;
     spt::KParams P{};
     fill_kparams(c, cam, w, h, row_begin, row_count, samps, seed, P);
@@ -2280,16 +2152,14 @@ int spt_progressive_end(spt_ctx* c)
     if (c->stream) SPT_HIP(c, hipStreamSynchronize(c->stream));
     if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
     if (c->acc_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_acc));   // accumulations other lanes still have in flight
-    if (c->d_accum) (void)hipFree(c->d_accum);
-    if (c->d_frame) (void)hipFree(c->d_frame);
-    c->d_accum = c->d_frame = nullptr;
-    progressive_aov_free(c);
-    moments_free(c);
-    temporal_free(c);
+    c->d_accum.reset(); c->d_frame.reset();
+    c->aov = ProgressiveAov{};
+    c->m2 = Moments{};
+    c->tp = Temporal{};
     if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));   // a filter a caller's stream still runs
     c->denoise_recorded = false;
-    denoise_free(c);
-    display_free(c);
+    c->dn = DenoiseScratch{};
+    c->d_disp8.reset();
     c->prog_w = c->prog_h = 0;
     c->acc_recorded = false;
     c->frame_in_flight = false;
@@ -2306,12 +2176,14 @@ int spt_progressive_begin(spt_ctx* c, uint32_t w, uint32_t h)
     if (!c) return 1;
     if (w == 0 || h == 0) return c->fail("spt_progressive_begin: empty image");
     if (int rc = spt_progressive_end(c)) return rc;
-    const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-    SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_accum), bytes));
-    SPT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_frame), bytes));
-    SPT_HIP(c, hipMemsetAsync(c->d_accum, 0, bytes, c->stream));       // accumBuffer.resize(w*h, make_float3(0,0,0)), :882
+    const size_t nfl = (size_t)w * h * 3;
+    DevBuf<float> accum, frame;                                        // (a failure below leaves the loop ended: d_accum == nullptr)
+    SPT_HIP(c, accum.grow(nfl));
+    SPT_HIP(c, frame.grow(nfl));
+    SPT_HIP(c, hipMemsetAsync(accum, 0, nfl * sizeof(float), c->stream));   // accumBuffer.resize(w*h, make_float3(0,0,0)), :882
     if (!c->ev_acc) SPT_HIP(c, hipEventCreateWithFlags(&c->ev_acc, hipEventDisableTiming));
     SPT_HIP(c, hipEventRecord(c->ev_acc, c->stream));                  // later accumulations (any lane) run behind the clearing
+    c->d_accum = std::move(accum); c->d_frame = std::move(frame);
     c->acc_recorded = true;
     c->prog_w = w; c->prog_h = h;
     return 0;
@@ -2337,7 +2209,7 @@ int spt_progressive_attach(spt_ctx* lane, spt_ctx* owner)
     const int prio = levels[owner->lanes_attached++ % levels.size()];
     if (lane->stream) { (void)hipStreamSynchronize(lane->stream); (void)hipStreamDestroy(lane->stream); lane->stream = nullptr; }
     SPT_HIP(lane, hipStreamCreateWithPriority(&lane->stream, hipStreamNonBlocking, prio));
-    SPT_HIP(lane, hipMalloc(reinterpret_cast<void**>(&lane->d_frame), (size_t)owner->prog_w * owner->prog_h * 3 * sizeof(float)));
+    SPT_HIP(lane, lane->d_frame.grow((size_t)owner->prog_w * owner->prog_h * 3));   // (a failure leaves the lane unattached: d_frame == nullptr)
     lane->prog_w = owner->prog_w; lane->prog_h = owner->prog_h;
     lane->attached_to = owner;
     return 0;
@@ -2363,10 +2235,10 @@ int spt_progressive_frame_async(spt_ctx* c, spt_ctx* owner, const spt_camera* ca
     if (rrc) return rrc;
     // :927-937 accumBuffer (clear ? = : +=) outImage, behind the previous accumulation whichever lane issued it
     if (owner->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, owner->ev_acc, 0));
-    if (owner->d_m2) {          // moments on: the same adds and the squared luminance from one read of the frame (spt_denoise_var.hip)
-        SPT_HIP(c, spt_moments_accumulate_launch(owner->d_accum, owner->d_m2, c->d_frame, (size_t)c->prog_w * c->prog_h, clear, c->stream));
-        owner->m2_frames = clear ? 1u : owner->m2_frames + 1u;
-        if (clear) owner->m2_valid = true;
+    if (owner->m2.sum) {          // moments on: the same adds and the squared luminance from one read of the frame (spt_denoise_var.hip)
+        SPT_HIP(c, spt_moments_accumulate_launch(owner->d_accum, owner->m2.sum, c->d_frame, (size_t)c->prog_w * c->prog_h, clear, c->stream));
+        owner->m2.frames = clear ? 1u : owner->m2.frames + 1u;
+        if (clear) owner->m2.valid = true;
     } else {
         SPT_HIP(c, spt_k_accumulate(owner->d_accum, c->d_frame, (size_t)c->prog_w * c->prog_h * 3, clear, c->stream));
     }
@@ -2412,12 +2284,12 @@ int spt_progressive_moments_begin(spt_ctx* c)
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     if (c->acc_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_acc));   // accumulations other lanes still have in flight
-    moments_free(c);
-    const size_t bytes = (size_t)c->prog_w * c->prog_h * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_m2), bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_m2, 0, bytes, c->stream);
+    c->m2 = Moments{};
+    const size_t npix = (size_t)c->prog_w * c->prog_h;
+    hipError_t e = c->m2.sum.grow(npix);
+    if (e == hipSuccess) e = hipMemsetAsync(c->m2.sum, 0, npix * sizeof(float), c->stream);
     if (e == hipSuccess) e = hipEventRecord(c->ev_acc, c->stream);     // later accumulations (any lane) run behind the clearing
-    if (e != hipSuccess) { (void)hipGetLastError(); moments_free(c); return c->fail("spt_progressive_moments_begin: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipGetLastError(); c->m2 = Moments{}; return c->fail("spt_progressive_moments_begin: %s", hipGetErrorString(e)); }
     c->acc_recorded = true;
     return 0;
 }
@@ -2425,8 +2297,8 @@ int spt_progressive_moments_begin(spt_ctx* c)
 // Moments on and a clearing frame issued since: what every variance entry point needs
 static int moments_check(spt_ctx* c, const char* who)
 {
-    if (!c->d_m2) return c->fail("%s: call spt_progressive_moments_begin first", who);
-    if (!c->m2_valid) return c->fail("%s: no frame with clear != 0 has been issued since spt_progressive_moments_begin", who);
+    if (!c->m2.sum) return c->fail("%s: call spt_progressive_moments_begin first", who);
+    if (!c->m2.valid) return c->fail("%s: no frame with clear != 0 has been issued since spt_progressive_moments_begin", who);
     return 0;
 }
 
@@ -2439,10 +2311,10 @@ int spt_progressive_variance_snapshot(spt_ctx* c, float* out_var, uint32_t* fram
     const size_t npix = (size_t)c->prog_w * c->prog_h;
     if (grow_out(c, npix)) return 1;
     if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
-    SPT_HIP(c, spt_moments_variance_launch(c->d_accum, c->d_m2, npix, (float)c->m2_frames, c->d_out, c->stream));
+    SPT_HIP(c, spt_moments_variance_launch(c->d_accum, c->m2.sum, npix, (float)c->m2.frames, c->d_out, c->stream));
     SPT_HIP(c, hipMemcpyAsync(out_var, c->d_out, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
-    if (frames) *frames = c->m2_frames;
+    if (frames) *frames = c->m2.frames;
     return 0;
 }
 
@@ -2456,31 +2328,31 @@ int spt_progressive_aov_begin(spt_ctx* c, uint32_t mask)
     if (mask == 0 || mask > SPT_AOVSET_ALL) return c->fail("spt_progressive_aov_begin: bad mask 0x%x (one or more of SPT_AOVSET_NORMAL .. SPT_AOVSET_COVERAGE)", mask);
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
-    progressive_aov_free(c);
-    const size_t bytes = (size_t)c->prog_w * c->prog_h * 3 * sizeof(float);
+    c->aov = ProgressiveAov{};
+    const size_t nfl = (size_t)c->prog_w * c->prog_h * 3;
     for (uint32_t k = 0; k < 6; ++k) {
         if (!((mask >> k) & 1u)) continue;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_aov_accum[k]), bytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_aov_frame[k]), bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_aov_accum[k], 0, bytes, c->stream);
-        if (e != hipSuccess) { progressive_aov_free(c); return c->fail("spt_progressive_aov_begin: %s", hipGetErrorString(e)); }
+        hipError_t e = c->aov.accum[k].grow(nfl);
+        if (e == hipSuccess) e = c->aov.frame[k].grow(nfl);
+        if (e == hipSuccess) e = hipMemsetAsync(c->aov.accum[k], 0, nfl * sizeof(float), c->stream);
+        if (e != hipSuccess) { c->aov = ProgressiveAov{}; return c->fail("spt_progressive_aov_begin: %s", hipGetErrorString(e)); }
     }
-    c->aov_mask = mask;
+    c->aov.mask = mask;
     return 0;
 }
 
 int spt_progressive_aov_frame(spt_ctx* c, const spt_camera* cam, uint32_t samps, uint64_t seed, int clear, spt_stats* stats)
 {
     if (!c) return 1;
-    if (!c->aov_mask) return c->fail("spt_progressive_aov_frame: call spt_progressive_aov_begin first");
+    if (!c->aov.mask) return c->fail("spt_progressive_aov_frame: call spt_progressive_aov_begin first");
     if (c->frame_in_flight) return c->fail("spt_progressive_aov_frame: a radiance frame of this context has not been waited for");
     void* frames[6];
     uint32_t n = 0;
-    for (uint32_t k = 0; k < 6; ++k) if ((c->aov_mask >> k) & 1u) frames[n++] = c->d_aov_frame[k];
-    if (int rc = render_aov_impl(c, "spt_progressive_aov_frame", cam, c->prog_w, c->prog_h, 0, c->prog_h, samps, seed, true, c->aov_mask, 0u, frames, nullptr)) return rc;
+    for (uint32_t k = 0; k < 6; ++k) if ((c->aov.mask >> k) & 1u) frames[n++] = c->aov.frame[k];
+    if (int rc = render_aov_impl(c, "spt_progressive_aov_frame", cam, c->prog_w, c->prog_h, 0, c->prog_h, samps, seed, true, c->aov.mask, 0u, frames, nullptr)) return rc;
     for (uint32_t k = 0; k < 6; ++k)
-        if ((c->aov_mask >> k) & 1u)
-            SPT_HIP(c, spt_k_accumulate(c->d_aov_accum[k], c->d_aov_frame[k], (size_t)c->prog_w * c->prog_h * 3, clear, c->stream));
+        if ((c->aov.mask >> k) & 1u)
+            SPT_HIP(c, spt_k_accumulate(c->aov.accum[k], c->aov.frame[k], (size_t)c->prog_w * c->prog_h * 3, clear, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return spt_sync(c, stats);
 }
@@ -2489,11 +2361,11 @@ int spt_progressive_aov_snapshot(spt_ctx* c, uint32_t kind_bit, float* out_rgb)
 {
     if (!c) return 1;
     if (!out_rgb) return c->fail("spt_progressive_aov_snapshot: out_rgb is NULL");
-    if (kind_bit == 0 || (kind_bit & (kind_bit - 1u)) || !(kind_bit & c->aov_mask))
-        return c->fail("spt_progressive_aov_snapshot: 0x%x is not one kind of the mask 0x%x given to spt_progressive_aov_begin", kind_bit, c->aov_mask);
+    if (kind_bit == 0 || (kind_bit & (kind_bit - 1u)) || !(kind_bit & c->aov.mask))
+        return c->fail("spt_progressive_aov_snapshot: 0x%x is not one kind of the mask 0x%x given to spt_progressive_aov_begin", kind_bit, c->aov.mask);
     SPT_HIP(c, hipSetDevice(c->device));
     const int k = __builtin_ctz(kind_bit);
-    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_aov_accum[k], (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->aov.accum[k], (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2552,11 +2424,11 @@ static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, con
                            hipStream_t st, const float* m2 = nullptr, uint32_t frames = 0, float sigma_colour = 0.f)
 {
     const size_t npix = (size_t)w * h;
-    if (npix > c->dn_guides_cap || npix > c->dn_ping_cap || npix > c->dn_pong_cap) {
+    if (npix > c->dn.guides.cap || npix > c->dn.ping.cap || npix > c->dn.pong.cap) {
         if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));   // the previous filter may still read the old scratch
-        hipError_t e = grow(c->d_dn_guides, c->dn_guides_cap, npix, 3 * npix);
-        if (e == hipSuccess) e = grow(c->d_dn_ping, c->dn_ping_cap, npix);
-        if (e == hipSuccess) e = grow(c->d_dn_pong, c->dn_pong_cap, npix);
+        hipError_t e = c->dn.guides.grow(npix, 3 * npix);
+        if (e == hipSuccess) e = c->dn.ping.grow(npix);
+        if (e == hipSuccess) e = c->dn.pong.grow(npix);
         if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: scratch for %u x %u pixels: %s", who, w, h, hipGetErrorString(e)); }
     }
     if (!c->ev_denoise) SPT_HIP(c, hipEventCreateWithFlags(&c->ev_denoise, hipEventDisableTiming));
@@ -2567,16 +2439,16 @@ static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, con
         for (hipEvent_t& e : c->dn_ev) if (!e) SPT_HIP(c, hipEventCreate(&e));
         SPT_HIP(c, hipEventRecord(c->dn_ev[0], st));
     }
-    if (m2) SPT_HIP(c, spt_denoise_var_pack_launch(beauty, normal, albedo, position, coverage, m2, (uint32_t)npix, (float)aov_samples, (float)frames, c->d_dn_ping, c->d_dn_guides, st));
-    else SPT_HIP(c, spt_denoise_pack_launch(beauty, normal, albedo, position, coverage, (uint32_t)npix, (float)aov_samples, c->d_dn_ping, c->d_dn_guides, st));
+    if (m2) SPT_HIP(c, spt_denoise_var_pack_launch(beauty, normal, albedo, position, coverage, m2, (uint32_t)npix, (float)aov_samples, (float)frames, c->dn.ping, c->dn.guides, st));
+    else SPT_HIP(c, spt_denoise_pack_launch(beauty, normal, albedo, position, coverage, (uint32_t)npix, (float)aov_samples, c->dn.ping, c->dn.guides, st));
     const float sigma[5] = {p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage, sigma_colour};
     if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[1], st));
-    float4* src = c->d_dn_ping;
-    float4* dst = c->d_dn_pong;
+    float4* src = c->dn.ping;
+    float4* dst = c->dn.pong;
     for (uint32_t i = 0; i < p->levels; ++i) {
         const bool last = i + 1 == p->levels;
-        if (m2) SPT_HIP(c, spt_denoise_var_pass_launch(src, c->d_dn_guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
-        else SPT_HIP(c, spt_denoise_pass_launch(src, c->d_dn_guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
+        if (m2) SPT_HIP(c, spt_denoise_var_pass_launch(src, c->dn.guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
+        else SPT_HIP(c, spt_denoise_pass_launch(src, c->dn.guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
         if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[2 + i], st));
         std::swap(src, dst);
     }
@@ -2626,26 +2498,26 @@ int spt_denoise(spt_ctx* c, const float* beauty, const float* normal, const floa
 // so far: vp == nullptr is the guide-only filter under *p
 static int progressive_denoised_enqueue(spt_ctx* c, const char* who, uint32_t aov_samples, const spt_denoise_params* p, const spt_denoise_var_params* vp)
 {
-    const uint32_t need = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE, missing = need & ~c->aov_mask;
+    const uint32_t need = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE, missing = need & ~c->aov.mask;
     if (missing)
         return c->fail("%s: spt_progressive_aov_begin has not selected%s%s%s%s", who, (missing & SPT_AOVSET_NORMAL) ? " NORMAL" : "",
                        (missing & SPT_AOVSET_ALBEDO) ? " ALBEDO" : "", (missing & SPT_AOVSET_POSITION) ? " POSITION" : "", (missing & SPT_AOVSET_COVERAGE) ? " COVERAGE" : "");
     spt_denoise_params four;
     if (vp) {
         if (int rc = moments_check(c, who)) return rc;
-        if (int rc = denoise_var_check(c, who, c->prog_w, c->prog_h, aov_samples, c->m2_frames, vp, &four)) return rc;
+        if (int rc = denoise_var_check(c, who, c->prog_w, c->prog_h, aov_samples, c->m2.frames, vp, &four)) return rc;
         p = &four;
     } else if (int rc = denoise_check(c, who, c->prog_w, c->prog_h, aov_samples, p)) return rc;
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t nfl = (size_t)c->prog_w * c->prog_h * 3;
-    if (nfl > c->dn_out_cap) {
+    if (nfl > c->dn.out.cap) {
         if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));
-        const hipError_t e = grow(c->d_dn_out, c->dn_out_cap, nfl);
+        const hipError_t e = c->dn.out.grow(nfl);
         if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: scratch: %s", who, hipGetErrorString(e)); }
     }
     if (c->acc_recorded) SPT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_acc, 0));   // every accumulation issued so far, any lane
-    if (int rc = denoise_enqueue(c, who, c->d_accum, c->d_aov_accum[SPT_AOV_NORMAL], c->d_aov_accum[SPT_AOV_ALBEDO], c->d_aov_accum[4], c->d_aov_accum[5],
-                                 c->prog_w, c->prog_h, aov_samples, p, c->d_dn_out, c->stream, vp ? c->d_m2 : nullptr, c->m2_frames, vp ? vp->sigma_colour : 0.f)) return rc;
+    if (int rc = denoise_enqueue(c, who, c->d_accum, c->aov.accum[SPT_AOV_NORMAL], c->aov.accum[SPT_AOV_ALBEDO], c->aov.accum[4], c->aov.accum[5],
+                                 c->prog_w, c->prog_h, aov_samples, p, c->dn.out, c->stream, vp ? c->m2.sum : nullptr, c->m2.frames, vp ? vp->sigma_colour : 0.f)) return rc;
     return 0;
 }
 
@@ -2655,7 +2527,7 @@ static int progressive_denoised(spt_ctx* c, const char* who, uint32_t aov_sample
 {
     if (!c->d_accum || !out_rgb) return c->fail("%s: no accumulation buffer or out_rgb is NULL", who);
     if (int rc = progressive_denoised_enqueue(c, who, aov_samples, p, vp)) return rc;
-    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_dn_out, (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->dn.out, (size_t)c->prog_w * c->prog_h * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2736,11 +2608,8 @@ static int display_table(spt_ctx* c, const char* who)
     char msg[256];
     const float* t = spt_display_table(msg, sizeof msg);
     if (!t) return c->fail("%s: %s", who, msg);
-    float* d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), SPT_DISPLAY_TABLE * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d, t, SPT_DISPLAY_TABLE * sizeof(float), hipMemcpyHostToDevice);   // blocking: in place before any stream reads it
-    if (e != hipSuccess) { (void)hipGetLastError(); if (d) (void)hipFree(d); return c->fail("%s: threshold table: %s", who, hipGetErrorString(e)); }
-    c->d_disp_table = d;
+    const hipError_t e = c->d_disp_table.upload(t, SPT_DISPLAY_TABLE * sizeof(float));   // blocking: in place before any stream reads it
+    if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: threshold table: %s", who, hipGetErrorString(e)); }
     return 0;
 }
 
@@ -2750,7 +2619,7 @@ static size_t display_bytes(uint32_t w, uint32_t h, const spt_display_params* p)
 static int display_to_host(spt_ctx* c, const char* who, const float* d_sum, uint32_t w, uint32_t h, const spt_display_params* p, uint8_t* out8)
 {
     const size_t bytes = display_bytes(w, h, p);
-    const hipError_t e = grow(c->d_disp8, c->disp8_cap, bytes);
+    const hipError_t e = c->d_disp8.grow(bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: 8-bit image of %u x %u pixels: %s", who, w, h, hipGetErrorString(e)); }
     SPT_HIP(c, spt_display_launch(d_sum, c->d_disp_table, w, h, p->weight, p->format == SPT_DISPLAY_RGBA8 ? 4 : 3, (p->flags & SPT_DISPLAY_FLIP_Y) != 0, c->d_disp8, c->stream));
     SPT_HIP(c, hipMemcpyAsync(out8, c->d_disp8, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2803,7 +2672,7 @@ int spt_progressive_display_snapshot(spt_ctx* c, uint32_t filter, uint32_t aov_s
         const bool var = filter == SPT_DISPLAY_SRC_DENOISED_VAR;
         if (int rc = progressive_denoised_enqueue(c, who, aov_samples, var ? nullptr : static_cast<const spt_denoise_params*>(filter_params),
                                                   var ? static_cast<const spt_denoise_var_params*>(filter_params) : nullptr)) return rc;
-        src = c->d_dn_out;
+        src = c->dn.out;
     }
     return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);
 }
@@ -2918,16 +2787,16 @@ int spt_progressive_temporal_begin(spt_ctx* c, const spt_temporal_params* p)
     if ((uint64_t)c->prog_w * c->prog_h > 0x7FFFFFFFull) return c->fail("%s: w*h exceeds 2^31-1 pixels", who);
     SPT_HIP(c, hipSetDevice(c->device));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
-    temporal_free(c);
-    const size_t hist = (size_t)spt_temporal_history_bytes(c->prog_w, c->prog_h), pitch = temporal_pitch(c), plane = temporal_plane(c);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_hist[0]), hist);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_hist[1]), hist);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_frame), pitch * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_guides), 4 * pitch * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_tp_out), (pitch + 2 * plane) * sizeof(float));
-    if (e != hipSuccess) { (void)hipGetLastError(); temporal_free(c); return c->fail("%s: %s", who, hipGetErrorString(e)); }
-    c->tp_params = *p;
-    c->tp_on = true;
+    c->tp = Temporal{};
+    const size_t hist = (size_t)spt_temporal_history_bytes(c->prog_w, c->prog_h) / sizeof(float4), pitch = temporal_pitch(c), plane = temporal_plane(c);
+    hipError_t e = c->tp.hist[0].grow(hist);
+    if (e == hipSuccess) e = c->tp.hist[1].grow(hist);
+    if (e == hipSuccess) e = c->tp.frame.grow(pitch);
+    if (e == hipSuccess) e = c->tp.guides.grow(4 * pitch);
+    if (e == hipSuccess) e = c->tp.out.grow(pitch + 2 * plane);
+    if (e != hipSuccess) { (void)hipGetLastError(); c->tp = Temporal{}; return c->fail("%s: %s", who, hipGetErrorString(e)); }
+    c->tp.params = *p;
+    c->tp.on = true;
     return 0;
 }
 
@@ -2935,7 +2804,7 @@ int spt_progressive_temporal_frame(spt_ctx* c, const spt_camera* cam, uint32_t s
 {
     if (!c) return 1;
     const char* const who = "spt_progressive_temporal_frame";
-    if (!c->tp_on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (!c->tp.on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
     if (!cam) return c->fail("%s: NULL argument", who);
     if (c->frame_in_flight) return c->fail("%s: a radiance frame of this context has not been waited for", who);
     // everything the step would refuse is refused here, before a launch overwrites the loop's frames: the remembered camera passed this
@@ -2947,24 +2816,24 @@ int spt_progressive_temporal_frame(spt_ctx* c, const spt_camera* cam, uint32_t s
     const uint32_t w = c->prog_w, h = c->prog_h;
     const size_t pitch = temporal_pitch(c), plane = temporal_plane(c);
     // :922 the frame is the UN-NORMALISED sum of Renderer::render -- the launch of spt_progressive_frame, into the loop's own frame
-    if (int rc = spt_render_rows_device(c, cam, w, h, 0, h, samps, seed, 0u, c->d_tp_frame, nullptr)) return rc;
+    if (int rc = spt_render_rows_device(c, cam, w, h, 0, h, samps, seed, 0u, c->tp.frame, nullptr)) return rc;
     if (int rc = spt_sync(c, stats)) return rc;
-    float* const g = c->d_tp_guides;
+    float* const g = c->tp.guides;
     void* const guides[4] = {g, g + pitch, g + 2 * pitch, g + 3 * pitch};       // NORMAL, ALBEDO, POSITION, COVERAGE: ascending bit order
     const uint32_t mask = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE;
     if (int rc = render_aov_impl(c, who, cam, w, h, 0, h, samps, seed, true, mask, 0u, guides, nullptr)) return rc;
-    const bool have = c->tp_have && !reset;
-    const int next = c->tp_cur ^ 1;
-    const spt::TemporalCall k{c->d_tp_frame, g, g + 2 * pitch, g + 3 * pitch, have ? c->d_tp_hist[c->tp_cur] : nullptr, c->d_tp_hist[next], c->d_tp_out,
-                              c->d_tp_out + pitch, c->d_tp_out + pitch + plane, w, h, 4u * samps, cam, have ? &c->tp_cam : nullptr, &c->tp_params, true};
+    const bool have = c->tp.have && !reset;
+    const int next = c->tp.cur ^ 1;
+    const spt::TemporalCall k{c->tp.frame, g, g + 2 * pitch, g + 3 * pitch, have ? c->tp.hist[c->tp.cur] : nullptr, c->tp.hist[next], c->tp.out,
+                              c->tp.out + pitch, c->tp.out + pitch + plane, w, h, 4u * samps, cam, have ? &c->tp.cam : nullptr, &c->tp.params, true};
     const int rc = temporal_enqueue(c, who, k, c->stream);
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     if (int src = spt_sync(c, nullptr)) return src;                             // the feature launch's completion
     if (rc) return rc;
-    c->tp_cur = next;
-    c->tp_have = true;
-    c->tp_cam = *cam;
-    c->tp_samples = 4u * samps;
+    c->tp.cur = next;
+    c->tp.have = true;
+    c->tp.cam = *cam;
+    c->tp.samples = 4u * samps;
     return 0;
 }
 
@@ -2972,14 +2841,14 @@ int spt_progressive_temporal_snapshot(spt_ctx* c, float* out_rgb, float* out_var
 {
     if (!c) return 1;
     const char* const who = "spt_progressive_temporal_snapshot";
-    if (!c->tp_on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (!c->tp.on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
     if (!out_rgb) return c->fail("%s: NULL argument (out_rgb)", who);
-    if (!c->tp_have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
+    if (!c->tp.have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t npix = (size_t)c->prog_w * c->prog_h, pitch = temporal_pitch(c), plane = temporal_plane(c);
-    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->d_tp_out, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (out_var) SPT_HIP(c, hipMemcpyAsync(out_var, c->d_tp_out + pitch, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (out_len) SPT_HIP(c, hipMemcpyAsync(out_len, c->d_tp_out + pitch + plane, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->tp.out, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_var) SPT_HIP(c, hipMemcpyAsync(out_var, c->tp.out + pitch, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_len) SPT_HIP(c, hipMemcpyAsync(out_len, c->tp.out + pitch + plane, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2988,24 +2857,24 @@ int spt_progressive_temporal_display_snapshot(spt_ctx* c, const spt_denoise_para
 {
     if (!c) return 1;
     const char* const who = "spt_progressive_temporal_display_snapshot";
-    if (!c->tp_on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (!c->tp.on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
     if (!out8) return c->fail("%s: NULL argument (out8)", who);
-    if (!c->tp_have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
+    if (!c->tp.have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
     if (int rc = display_check(c, who, c->prog_w, c->prog_h, p)) return rc;
-    if (dp) if (int rc = denoise_check(c, who, c->prog_w, c->prog_h, c->tp_samples, dp)) return rc;
+    if (dp) if (int rc = denoise_check(c, who, c->prog_w, c->prog_h, c->tp.samples, dp)) return rc;
     SPT_HIP(c, hipSetDevice(c->device));
     if (int rc = display_table(c, who)) return rc;
-    const float* src = c->d_tp_out;
+    const float* src = c->tp.out;
     if (dp) {
         const size_t nfl = (size_t)c->prog_w * c->prog_h * 3, pitch = temporal_pitch(c);
-        if (nfl > c->dn_out_cap) {
+        if (nfl > c->dn.out.cap) {
             if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));
-            const hipError_t e = grow(c->d_dn_out, c->dn_out_cap, nfl);
+            const hipError_t e = c->dn.out.grow(nfl);
             if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: scratch: %s", who, hipGetErrorString(e)); }
         }
-        const float* const g = c->d_tp_guides;
-        if (int rc = denoise_enqueue(c, who, c->d_tp_out, g, g + pitch, g + 2 * pitch, g + 3 * pitch, c->prog_w, c->prog_h, c->tp_samples, dp, c->d_dn_out, c->stream)) return rc;
-        src = c->d_dn_out;
+        const float* const g = c->tp.guides;
+        if (int rc = denoise_enqueue(c, who, c->tp.out, g, g + pitch, g + 2 * pitch, g + 3 * pitch, c->prog_w, c->prog_h, c->tp.samples, dp, c->dn.out, c->stream)) return rc;
+        src = c->dn.out;
     }
     return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);
 }
@@ -3125,14 +2994,12 @@ int spt_selftest_math(spt_ctx* c, int op, const float* in, float* out, uint32_t 
     if (!c) return 1;
     if (!in || !out || !n || !w) return c->fail("spt_selftest_math: bad argument");
     SPT_HIP(c, hipSetDevice(c->device));
-    float *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_in), (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), (size_t)n * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice);
+    DevBuf<float> d_in, d_out;
+    hipError_t e = d_in.upload(in, (size_t)n * 4);
+    if (e == hipSuccess) e = d_out.grow(n);
     if (e == hipSuccess) e = spt_k_selftest(op, d_in, d_out, n, w, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in); (void)hipFree(d_out);
     if (e != hipSuccess) return c->fail("spt_selftest_math: %s", hipGetErrorString(e));
     return 0;
 }
@@ -3143,15 +3010,13 @@ int spt_selftest_range(spt_ctx* c, int op, uint32_t first, uint32_t count, uint6
     if (!c) return 1;
     if (!mismatches || !first_bad) return c->fail("spt_selftest_range: NULL argument");
     SPT_HIP(c, hipSetDevice(c->device));
-    unsigned long long* d_m = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_m), 16);
+    DevBuf<unsigned long long> d_m;
     const unsigned long long init[2] = {0ull, 0xFFFFFFFFull};
-    if (e == hipSuccess) e = hipMemcpy(d_m, init, 16, hipMemcpyHostToDevice);
+    hipError_t e = d_m.upload(init, 16);
     if (e == hipSuccess) e = spt_k_selftest_range(op, first, count, d_m, reinterpret_cast<uint32_t*>(d_m + 1), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     unsigned long long out[2] = {0, 0};
     if (e == hipSuccess) e = hipMemcpy(out, d_m, 16, hipMemcpyDeviceToHost);
-    (void)hipFree(d_m);
     if (e != hipSuccess) return c->fail("spt_selftest_range: %s", hipGetErrorString(e));
     *mismatches = out[0];
     *first_bad = (uint32_t)out[1];
