@@ -31,6 +31,7 @@
 #include "spt_device.h"
 #include "spt_kernel.h"
 #include "spt_share.h"
+#include "spt_lanes.h"
 
 namespace spt {
 
@@ -56,6 +57,13 @@ __device__ __forceinline__ uint32_t rank_in(unsigned long long m)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 __device__ __forceinline__ unsigned long long lanes_where(bool p) { return __builtin_amdgcn_ballot_w64(p); }   // the compare's own lane mask
+// the per-lane condition back from a lane mask held in a scalar register pair: a branch on it narrows EXEC by the mask itself, a select reads it
+__device__ __forceinline__ bool lane_in(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// Code that must stay a branch under its lanes: the compiler turns a short body into selects on the mask (slow issue class) where the
+// branch costs two scalar instructions; an instruction it cannot speculate keeps the branch.
+__device__ __forceinline__ void bump(uint32_t& c) { asm volatile("v_add_u32 %0, 1, %0" : "+v"(c)); }
+__device__ __forceinline__ void pin(f3& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z)); }
+__device__ __forceinline__ unsigned long long lanes_zero(const f3& v) { return lanes_where(v.x == 0.f) & lanes_where(v.y == 0.f) & lanes_where(v.z == 0.f); }
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
@@ -70,12 +78,18 @@ __device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c)
     return r;
 }
 
-// packed word of a slot: [11:0] depth, [14:12] branch bits (D7), [15] weight-may-be-non-finite flag,
+// packed word of a slot (the untrimmed loop's; the trimmed loop's layout follows): [11:0] depth, [14:12] branch bits (D7), [15] weight-may-be-non-finite flag,
 // [27:16] sphere index, [29:28] Refl_t, [31:30] pending transmitted children of the slot's current sample
 __device__ __forceinline__ uint32_t pack_path(uint32_t depth, uint32_t branchf, uint32_t inst, uint32_t refl, uint32_t sp)
 {
     return depth | (branchf << 12) | (inst << 16) | (refl << 28) | (sp << 30);
 }
+
+// The trimmed loop's word holds the same fields where their consumers take them with one full-rate instruction each: [3:0] branch bits
+// and flag (one AND), [12:4] sphere index * 16 = the byte offset of its s_geom record (one AND; times three the offset of its s_mat rows),
+// [14:13] Refl_t, [16:15] pending children -- carried through a bounce in place: a slot on the GEN list holds this field alone, the glass
+// split adds kSpOne, only the record's address shifts it down --, [31:20] depth (one shift).  The word never leaves the kernel.
+constexpr uint32_t kSpShift = 15, kSpOne = 1u << kSpShift, kSpMask = 3u << kSpShift, kReflMask2 = 3u << 13, kGeomMask = 0x1FF0u;
 
 enum { C_GEN = 0, C_DIFF = 1, C_REFR = 2 };
 
@@ -89,6 +103,10 @@ template <int P, int NG, int SH, bool OLD, typename... EP>
 __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
 {
     constexpr bool ENV = kHasEnv<EP...>;
+    // MASKS: the trimmed loop's predicates as 64-bit lane masks in scalar registers from the class code to the push.  The environment variants
+    // keep them as per-lane predicates (their miss code shares its blocks with the closest hit's); the batch's lanes from
+    // the batch size, the counters and the slot word are the trimmed loop's in both.
+    constexpr bool MASKS = !OLD && !ENV;
     static_assert(P % 16 == 0 && P <= 256, "pool size");
     extern __shared__ float4 lds[];
     constexpr int kWaveF4 = (kSlotBytes * P) / 16;               // float4 per wave region
@@ -200,7 +218,11 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
         if ((++it_total & 255u) == 0u && K.watchdog_ticks != 0ull &&
             __builtin_amdgcn_s_memtime() - t_start > K.watchdog_ticks) { timed_out = true; break; }
 
-        const bool valid = lane < b;
+        // trimmed loop: the batch's lanes and every predicate that reaches the push are 64-bit lane masks in scalar registers, built by
+        // the compare's own ballot where its operands are known and combined with scalar arithmetic (b is wave-uniform)
+        const unsigned long long vmask = low_lanes(b);
+        unsigned long long mh = 0ull, mret = 0ull;                // lanes with a ray for the closest hit / GEN lanes whose slot retires
+        const bool valid = OLD ? lane < b : lane_in(vmask);
         const uint32_t slot = valid ? (uint32_t)LG[lbase + lane] : 0u;    // LDR follows LG: index P.. = LDR[0..]
 
         // per-lane path registers handed from the class code to the closest-hit query
@@ -212,10 +234,9 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
         PH_STAMP(0)
         if (c == C_GEN) {
             // ================= GEN: continue the slot's task (smallpt.cpp:304-340, :252 pop) =================
-            if constexpr (!OLD) cntG += valid ? 1u : 0u;
             const uint2 ts = gtask[slot];
             uint32_t task = ts.x, snext = ts.y;
-            sp = __float_as_uint(A1[slot].w) >> 30;
+            sp = OLD ? __float_as_uint(A1[slot].w) >> 30 : __float_as_uint(A1[slot].w);      // (trimmed loop: sp is the word's field in place)
             // task = ((pixel * 4 + cell) << nb_log2) | block (D9); a task-less slot has snext == send == 0
             uint32_t send = 0;
             if (task != kNoTask) {
@@ -224,25 +245,49 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
             }
             bool gen = false;
             bool need_task = false;
-            if (valid) {
-                if (sp > 0u) {                                   // pending transmitted child (reflected subtree is done)
-                    --sp;
-                    const float4* rec = stack_rec(sp, slot);
-                    const float4 s0 = rec[0], s1 = rec[1], s2 = rec[2];
-                    o = mk(s0.x, s0.y, s0.z); d = mk(s1.x, s1.y, s1.z); w = mk(s2.x, s2.y, s2.z);
-                    const uint32_t db = __float_as_uint(s0.w);
-                    depth = db & 0xFFFu; branchf = db >> 16;
-                    const uint32_t k0 = __float_as_uint(s1.w);
-                    k1 = __float_as_uint(s2.w);
-                    rbase = rng_base(k0, branchf & 7u, depth);
-                    has_ray = true;
-                } else if (snext == send) {
-                    need_task = true;                            // sample block finished (or the slot never had a task)
-                } else {
-                    gen = true;
+            unsigned long long mneed = 0ull, mgen = 0ull;        // trimmed loop: the same two as lane masks
+            auto pop_child = [&]() {                             // pending transmitted child (reflected subtree is done)
+                sp -= kSpOne;
+                const float4* rec = stack_rec(sp >> kSpShift, slot);
+                const float4 s0 = rec[0], s1 = rec[1], s2 = rec[2];
+                o = mk(s0.x, s0.y, s0.z); d = mk(s1.x, s1.y, s1.z); w = mk(s2.x, s2.y, s2.z);
+                const uint32_t db = __float_as_uint(s0.w);
+                depth = db & 0xFFFu; branchf = db >> 16;
+                const uint32_t k0 = __float_as_uint(s1.w);
+                k1 = __float_as_uint(s2.w);
+                rbase = rng_base(k0, branchf & 7u, depth);
+            };
+            if constexpr (!MASKS) {
+                if constexpr (!OLD) { if (valid) bump(cntG); }
+                if (valid) {
+                    if (sp > 0u) {                               // pending transmitted child (reflected subtree is done)
+                        sp -= OLD ? 1u : kSpOne;
+                        const float4* rec = stack_rec(OLD ? sp : sp >> kSpShift, slot);
+                        const float4 s0 = rec[0], s1 = rec[1], s2 = rec[2];
+                        o = mk(s0.x, s0.y, s0.z); d = mk(s1.x, s1.y, s1.z); w = mk(s2.x, s2.y, s2.z);
+                        const uint32_t db = __float_as_uint(s0.w);
+                        depth = db & 0xFFFu; branchf = db >> 16;
+                        const uint32_t k0 = __float_as_uint(s1.w);
+                        k1 = __float_as_uint(s2.w);
+                        rbase = rng_base(k0, branchf & 7u, depth);
+                        has_ray = true;
+                    } else if (snext == send) {
+                        need_task = true;                        // sample block finished (or the slot never had a task)
+                    } else {
+                        gen = true;
+                    }
                 }
+            } else {
+                // (idle lanes read slot 0: whatever they compare, vmask drops it)
+                const unsigned long long mpop = vmask & lanes_where(sp != 0u);
+                mneed = vmask & ~mpop & lanes_where(snext == send);
+                mgen = vmask & ~(mpop | mneed);
+                mh = mpop;
+                if (valid) bump(cntG);
+                if (lane_in(mpop)) pop_child();
+                need_task = lane_in(mneed);
             }
-            const unsigned long long need_mask = OLD ? __ballot(need_task) : lanes_where(need_task);
+            const unsigned long long need_mask = OLD ? __ballot(need_task) : (MASKS ? mneed : lanes_where(need_task));
             if (need_mask != 0ull) {
                 // cost-ordered dispatch (see chunk_order_kernel): completion times go to the chunk's clock word, fetch times below
                 // (pointers rebuilt from integers are generic to the compiler: said to be global, or it emits FLAT operations, which count
@@ -291,18 +336,31 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
                 } else {
                     chunk_next += cntn;
                 }
-                if (need_task) {
+                if constexpr (!MASKS) {
+                    if (need_task) {
+                        const uint32_t nt = rk < avail ? base_old + rk : base_new + (rk - avail);
+                        if (nt < K.ntasks) {
+                            task = nt; gen = true;
+                            snext = (task & ((1u << K.nb_log2) - 1u)) * K.sb;
+                            ACX[slot] = 0.f; ACY[slot] = 0.f; ACZ[slot] = 0.f;
+                        } else {
+                            retired = true;                      // the slot is pushed onto no list
+                        }
+                    }
+                } else {
                     const uint32_t nt = rk < avail ? base_old + rk : base_new + (rk - avail);
-                    if (nt < K.ntasks) {
-                        task = nt; gen = true;
+                    const unsigned long long mnew = need_mask & lanes_where(nt < K.ntasks);
+                    if (lane_in(mnew)) {
+                        task = nt;
                         snext = (task & ((1u << K.nb_log2) - 1u)) * K.sb;
                         ACX[slot] = 0.f; ACY[slot] = 0.f; ACZ[slot] = 0.f;
-                    } else {
-                        retired = true;                          // the slot is pushed onto no list
                     }
+                    mgen |= mnew;
+                    mret = need_mask & ~mnew;                    // these slots are pushed onto no list
                 }
             }
-            if (gen) {
+            if constexpr (MASKS) mh |= mgen;
+            if (MASKS ? lane_in(mgen) : gen) {
                 // ---- camera ray of sample `snext` of the cell (smallpt.cpp:325-340 / :745-760) ----
                 const uint32_t cellid = task >> K.nb_log2;
                 const uint32_t pix_local = cellid >> 2, cell = cellid & 3u;
@@ -348,7 +406,7 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
                 d = dd * inv;                                                                   // normalize(d)
                 w = mk(1, 1, 1); depth = 0; branchf = 0; rbase = k0;                             // :338-339
                 gtask[slot] = make_uint2(task, snext + 1u);
-                has_ray = true;
+                if constexpr (!MASKS) has_ray = true;
             }
         } else {
             // ================= DIFF / REFR: shade the waiting hit (smallpt.cpp:170-263) =================
@@ -356,17 +414,19 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
             const f3 hx = mk(a0.x, a0.y, a0.z);
             rbase = __float_as_uint(a0.w);
             const f3 din = mk(a1.x, a1.y, a1.z);
-            const uint32_t pk = valid ? __float_as_uint(a1.w) : 0u;       // idle lanes: sphere 0, never stored
+            // idle lanes: sphere 0, never stored (trimmed loop: slot 0's word as it is -- every word names a staged sphere --, never stored)
+            const uint32_t pk = OLD ? (valid ? __float_as_uint(a1.w) : 0u) : __float_as_uint(a1.w);
             w = mk(a2.x, a2.y, a2.z);
             k1 = __float_as_uint(a2.w);
-            depth = pk & 0xFFFu; branchf = (pk >> 12) & 0xFu; sp = pk >> 30;
-            const uint32_t inst = (pk >> 16) & 0xFFFu;
-            const float4 gh = s_geom[inst];
+            if constexpr (OLD) { depth = pk & 0xFFFu; branchf = (pk >> 12) & 0xFu; sp = pk >> 30; }
+            else { depth = pk >> 20; branchf = pk & 0xFu; sp = pk & kSpMask; }
+            const uint32_t inst = OLD ? (pk >> 16) & 0xFFFu : pk & kGeomMask;       // (trimmed loop: times 16)
+            const float4 gh = OLD ? s_geom[inst] : *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_geom) + inst);
             const f3 n = normalize<false>(mk(hx.x - gh.x, hx.y - gh.y, hx.z - gh.z));       // scene.cpp:124
             const f3 nl = dot(n, din) < 0 ? n : neg(n);                                     // :174 (D2)
             if (c == C_DIFF) {
-                if constexpr (!OLD) cntD += valid ? 1u : 0u;
-                const bool is_diff = valid && ((pk >> 28) & 3u) == 0u;   // idle lanes (pk = 0) must not drag a mirror-only batch through the diffuse code
+                if constexpr (!OLD) { if (valid) bump(cntD); }
+                const bool is_diff = valid && (OLD ? (pk >> 28) & 3u : pk & kReflMask2) == 0u;   // idle lanes (pk = 0) must not drag a mirror-only batch through the diffuse code
                 o = hx + nl * 0.02f;                                                        // :172 (D3)
                 if (is_diff) {                                                              // DIFF :208-215
                     const uint32_t u1bits = rng_draw_bits(rbase + kGolden, k1);
@@ -388,11 +448,12 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
                 // the weight was multiplied, the depth cap and the zero-weight cut applied before the slot was queued
                 ++depth;
                 rbase += 4u * kGolden;
-                has_ray = valid;
+                if constexpr (!MASKS) has_ray = valid;
+                else mh = vmask;
             } else {
                 // ---- glass, smallpt.cpp:225-263 ----
-                if constexpr (!OLD) cntR += valid ? 1u : 0u;
-                const float4 mfc = s_mat[3 * inst + (depth > 5u ? 2 : 1)];                  // f after the roulette (:192)
+                const float4 mfc = OLD ? s_mat[3 * inst + (depth > 5u ? 2 : 1)]             // f after the roulette (:192)
+                                       : *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_mat) + (3u * inst + (depth > 5u ? 32u : 16u)));
                 const f3 f = mk(mfc.x, mfc.y, mfc.z);
                 const f3 off = nl * 0.02f;                                                  // :172 (D3)
                 f3 no = hx + off, nf = f;
@@ -414,12 +475,12 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
                         if (!(tw.x == 0.f && tw.y == 0.f && tw.z == 0.f)) {
                             const uint32_t br = branchf & 7u;
                             const bool nonfin = !(__builtin_fabsf(tw.x) < __builtin_inff() && __builtin_fabsf(tw.y) < __builtin_inff() && __builtin_fabsf(tw.z) < __builtin_inff());
-                            float4* rec = stack_rec(sp, slot);
+                            float4* rec = stack_rec(OLD ? sp : sp >> kSpShift, slot);
                             rec[0] = make_float4(xin.x, xin.y, xin.z, __uint_as_float((depth + 1u) | ((br | (1u << depth) | ((branchf & 8u) | (nonfin ? 8u : 0u))) << 16)));
                             rec[1] = make_float4(tdir.x, tdir.y, tdir.z, __uint_as_float(rbase - ((br << 29) | (depth << 2)) * kGolden));   // k0
                             rec[2] = make_float4(tw.x, tw.y, tw.z, __uint_as_float(k1));
                             rec[3] = make_float4(0.f, 0.f, 0.f, 0.f);              // completes the line: no partial-line write
-                            ++sp;
+                            sp += OLD ? 1u : kSpOne;
                             ++nrec;
                         }
                         nf = f * Re;
@@ -436,10 +497,21 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
                 o = no; d = nd;
                 ++depth;
                 rbase += 4u * kGolden;
-                if (valid) {
-                    if (depth >= SPT_K_MAX_DEPTH) ++nkill;
-                    else if (!(w.x == 0.f && w.y == 0.f && w.z == 0.f)) has_ray = true;
-                    if (!(__builtin_fabsf(w.x) < __builtin_inff() && __builtin_fabsf(w.y) < __builtin_inff() && __builtin_fabsf(w.z) < __builtin_inff())) branchf |= 8u;
+                if constexpr (!MASKS) {
+                    if (valid) {
+                        if constexpr (!OLD) bump(cntR);
+                        if (depth >= SPT_K_MAX_DEPTH) ++nkill;
+                        else if (!(w.x == 0.f && w.y == 0.f && w.z == 0.f)) has_ray = true;
+                        if (!(__builtin_fabsf(w.x) < __builtin_inff() && __builtin_fabsf(w.y) < __builtin_inff() && __builtin_fabsf(w.z) < __builtin_inff())) branchf |= 8u;
+                    }
+                } else {
+                    const unsigned long long mcap = vmask & lanes_where(depth >= SPT_K_MAX_DEPTH);
+                    mh = vmask & ~mcap & ~lanes_zero(w);
+                    if (lane_in(mcap)) bump(nkill);
+                    if (valid) {
+                        bump(cntR);
+                        if (!(__builtin_fabsf(w.x) < __builtin_inff() && __builtin_fabsf(w.y) < __builtin_inff() && __builtin_fabsf(w.z) < __builtin_inff())) branchf |= 8u;
+                    }
                 }
             }
         }
@@ -450,12 +522,23 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
         // to 3 * NG spheres with never-hit entries (r*r = -inf: det = -inf, NaN keys), so the loop is fully unrolled
         // without bounds tests; ascending index with strict '<' = lowest index wins ties.
         PH_STAMP(1)
-        nbounce += (unsigned long long)__popcll(OLD ? __ballot(has_ray) : lanes_where(has_ray));
+        if constexpr (MASKS) has_ray = lane_in(mh);
+        // trimmed loop: what the class code contributes to the slot word -- depth, branch bits, pending children -- is packed in front of the
+        // sphere tests, in whichever form they run (the compiler would sink it into the store behind them; kept here, the block of the
+        // wide closest hit holds the same number of vector instructions as before the has-ray ballot in front of it went: DESIGN 4.1);
+        // sphere and material join the word behind the closest hit
+        uint32_t pre = 0u;
+        auto pack_class_part = [&]() {
+            if constexpr (MASKS) asm volatile("v_lshlrev_b32 %0, 20, %1\n\tv_or3_b32 %0, %0, %2, %3" : "=&v"(pre) : "v"(depth), "v"(branchf), "v"(sp));   // (depth << 20) | branchf | sp
+        };
+        nbounce += (unsigned long long)__popcll(OLD ? __ballot(has_ray) : (MASKS ? mh : lanes_where(has_ray)));
         uint32_t next = C_GEN;                                   // slots without a continuing path go back to GEN
-        bool to_diff = false, to_refr = false;                   // (trimmed loop: the same as two predicates, whose lane masks the branches below already hold)
-        const bool queued = valid && !retired;
+        bool to_diff = false, to_refr = false;                   // (trimmed loop, environment variants: the same as two predicates)
+        const bool queued = valid && !retired;                   // (the mask form pushes by vmask & ~mret)
+        unsigned long long md = 0ull, mr = 0ull;                 // trimmed loop: the lanes whose slot goes to DIFF / to REFR
         uint32_t near_key = kInfKeyP, inst = 0;
-        if (SPT_POOL_NARROW && 3 * NG <= 16 && b <= 4u) {
+        pack_class_part();
+        if (SPT_POOL_NARROW && 3 * NG <= 16 && (MASKS ? __builtin_expect(b <= 4u, 0) : b <= 4u)) {
             // ---- narrow closest hit: a batch of <= 4 rays (the end of a launch: its duration is set by the last, longest
             // paths) spreads the sphere tests over the wave -- lane 16 r + i tests sphere i for ray r -- instead of
             // running all of them in <= 4 lanes: ~60 instead of ~340 instructions on the critical path.  Same keys, same
@@ -555,7 +638,45 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
                 if (nk[i + 1] != nk[i]) inst = (uint32_t)i;
         }
         PH_STAMP(2)
-        if (has_ray) {
+        if constexpr (MASKS) {
+            // ---- class-independent part of shadePaths (smallpt.cpp:168-198), every decision a lane mask: the compares run where their
+            // operands are known, with every lane (a lane outside the mask that is ANDed in compares leftovers), the branches narrow
+            // EXEC by the mask itself ----
+            const unsigned long long mhit = lanes_where(near_key != kInfKeyP);                  // else :168 miss (D13); a lane without a ray kept kInfKeyP
+            if (mhit != 0ull) {
+                const float4 me = s_mat[3 * inst + 0];                                      // emission.xyz, refl | emissive << 2 (row 0 where nothing was hit)
+                const float4 mc = s_mat[3 * inst + 1];                                      // color.xyz, pmax
+                const float4 mf = s_mat[3 * inst + 2];                                      // color * (1/pmax), :192: read with the others (one LDS round trip)
+                const uint32_t rb = __float_as_uint(me.w);
+                const uint32_t refl = rb & 3u;
+                if (lane_in(mhit) && ((rb & 4u) != 0u || (branchf & 8u) != 0u)) {           // :179 (D4); + w*0 is skipped, exact for finite w
+                    ACX[slot] = ACX[slot] + w.x * me.x; ACY[slot] = ACY[slot] + w.y * me.y; ACZ[slot] = ACZ[slot] + w.z * me.z;
+                }
+                f3 f = mk(mc.x, mc.y, mc.z);                                                // :175
+                unsigned long long mcont = mhit;
+                const unsigned long long mdeep = mhit & lanes_where(depth > 5u);            // :188 (D5)
+                if (mdeep != 0ull) {
+                    mcont &= ~mdeep | lanes_where(rng_draw(rbase, k1) < mc.w);              // :196
+                    if (lane_in(mdeep)) { f = mk(mf.x, mf.y, mf.z); pin(f); }
+                }
+                // extend() of the DIFF / SPEC child (:214,:221): weight, D18 depth cap, D19 zero-weight cut
+                const unsigned long long mrefr = lanes_where(refl == 2u);
+                const unsigned long long mext = mcont & ~mrefr;
+                if (lane_in(mext)) { w = w * f; pin(w); }
+                const unsigned long long mcap = mext & lanes_where(depth + 1u >= SPT_K_MAX_DEPTH);
+                if (lane_in(mcap)) bump(nkill);
+                mcont &= ~(mcap | (mext & lanes_zero(w)));
+                if (lane_in(mcont)) {
+                    const float t = __uint_as_float(near_key + kEpsBias);
+                    const f3 hx = o + d * t;                                                // scene.cpp:137
+                    A0[slot] = make_float4(hx.x, hx.y, hx.z, __uint_as_float(rbase));
+                    A1[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(pre | (inst << 4) | (refl << 13)));
+                    A2[slot] = make_float4(w.x, w.y, w.z, __uint_as_float(k1));
+                }
+                md = mcont & ~mrefr;
+                mr = mcont & mrefr;
+            }
+        } else if (has_ray) {
             // ---- class-independent part of shadePaths (smallpt.cpp:168-198) ----
             if (near_key != kInfKeyP) {                                                     // else :168 miss (D13)
                 const float t = __uint_as_float(near_key + kEpsBias);
@@ -586,7 +707,8 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
                     if (cont) {
                         const f3 hx = o + d * t;                                            // scene.cpp:137
                         A0[slot] = make_float4(hx.x, hx.y, hx.z, __uint_as_float(rbase));
-                        A1[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(pack_path(depth, branchf, inst, refl, sp)));
+                        A1[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(OLD ? pack_path(depth, branchf, inst, refl, sp)
+                                                                                      : (depth << 20) | branchf | (inst << 4) | (refl << 13) | sp));
                         A2[slot] = make_float4(w.x, w.y, w.z, __uint_as_float(k1));
                         if constexpr (OLD) next = refl == 2u ? C_REFR : C_DIFF;
                         else { to_refr = refl == 2u; to_diff = !to_refr; }
@@ -599,19 +721,32 @@ __device__ __forceinline__ void pool_body(const KParams& K, const EP&... env)
         }
         PH_STAMP(3)
         // ================= push every slot onto the list of its next class =================
-        if constexpr (!OLD) {
-            // a continuing path is a queued slot (has_ray implies valid and not retired), so the GEN mask is what the other two leave
-            const unsigned long long mq = lanes_where(queued), md = lanes_where(to_diff), mr = lanes_where(to_refr);
+        if constexpr (MASKS) {
+            // a continuing path is a queued slot (a ray implies a batch lane that did not retire), so the GEN mask is what the other two leave
+            const unsigned long long mq = vmask & ~mret;
             const unsigned long long mg = mq & ~(md | mr);
-            const bool to_gen = queued && !to_diff && !to_refr;
             uint32_t pos = nG + rank_in(mg);
-            if (to_diff) pos = (uint32_t)P + nD + rank_in(md);
-            if (to_refr) pos = 2u * (uint32_t)P - 1u - nR - rank_in(mr);
-            if (queued) LG[pos] = (uint8_t)slot;
-            if (to_gen) A1[slot].w = __uint_as_float(sp << 30);
+            if (lane_in(md)) pos = (uint32_t)P + nD + rank_in(md);
+            if (lane_in(mr)) pos = 2u * (uint32_t)P - 1u - nR - rank_in(mr);
+            if (lane_in(mq)) LG[pos] = (uint8_t)slot;
+            if (lane_in(mg)) A1[slot].w = __uint_as_float(sp);
             nG += (uint32_t)__popcll(mg);
             nD += (uint32_t)__popcll(md);
             nR += (uint32_t)__popcll(mr);
+        } else if constexpr (!OLD) {
+            // the same push from per-lane predicates (environment variants): each ballot of a predicate that comes out of control flow
+            // costs a select and a compare
+            const unsigned long long mq = lanes_where(queued), mdp = lanes_where(to_diff), mrp = lanes_where(to_refr);
+            const unsigned long long mg = mq & ~(mdp | mrp);
+            const bool to_gen = queued && !to_diff && !to_refr;
+            uint32_t pos = nG + rank_in(mg);
+            if (to_diff) pos = (uint32_t)P + nD + rank_in(mdp);
+            if (to_refr) pos = 2u * (uint32_t)P - 1u - nR - rank_in(mrp);
+            if (queued) LG[pos] = (uint8_t)slot;
+            if (to_gen) A1[slot].w = __uint_as_float(sp);
+            nG += (uint32_t)__popcll(mg);
+            nD += (uint32_t)__popcll(mdp);
+            nR += (uint32_t)__popcll(mrp);
         } else {
             const bool to_gen = queued && next == C_GEN;
             const unsigned long long mg = __ballot(to_gen);
