@@ -40,7 +40,10 @@
  *     glutils.cpp:230-256) and toInt per channel before the      bit-exact to toInt), spt_write_ppm_rgb8
  *     PPM (smallpt.cpp:52,136-142)
  *   needClearBuffer on a camera update (smallpt.cpp:903-915,    spt_temporal_accumulate* / spt_progressive_temporal_*: history
- *     931-933): the accumulation restarts                        reprojected across the move instead of a restart
+ *     931-933): the accumulation restarts                        reprojected across the move instead of a restart;
+ *                                                                spt_temporal_variance* + spt_denoise_pvar* /
+ *                                                                spt_progressive_temporal_*_var_snapshot: its picture filtered
+ *                                                                under the history's own per-pixel variance
  *   "Elapsed time" stderr line (smallpt.cpp:371-373,809-811)    spt_stats
  *   CHK_PRIME / rtpContextGetLastErrorString                    int status + spt_last_error()
  *     (smallpt.cpp:381-393)
@@ -777,7 +780,8 @@ int  spt_write_ppm_rgb8(const char* path, const uint8_t* rgb8_top_first, uint32_
  *     before the first frame).
  *   Known limits: only the camera may move -- after spt_set_scene / spt_set_meshes / spt_set_instances / spt_set_environment the caller
  *     resets.  The first hit's motion stands for the whole path: reflections and refractions lag until alpha fades them.  The async lanes
- *     and the multi-GPU front are not covered.  The per-pixel variance is not fed into spt_denoise_var: that entry takes one frame count. */
+ *     and the multi-GPU front are not covered.  spt_denoise_var takes one frame count and so cannot take this per-pixel variance: it reaches
+ *     the filter through spt_temporal_variance* and spt_denoise_pvar* below. */
 typedef struct spt_temporal_params {
     float alpha;       /* in [0, 1]: lower bound of the weight of the current frame */
     float max_len;     /* >= 1: cap of the history length */
@@ -808,6 +812,74 @@ int  spt_progressive_temporal_frame(spt_ctx* ctx, const spt_camera* cam, uint32_
 int  spt_progressive_temporal_snapshot(spt_ctx* ctx, float* out_rgb, float* out_var, float* out_len);
 int  spt_progressive_temporal_display_snapshot(spt_ctx* ctx, const spt_denoise_params* denoise_params, const spt_display_params* display_params,
                                                uint8_t* out8);
+
+/* The seam between the temporal stage above and the variance-guided filter (csrc/spt_temporal_var.hip): SVGF's variance estimate from a
+ * temporal history and the filter of spt_denoise_var* with a caller-supplied per-pixel variance.
+ *
+ *   Arithmetic: float32, one rounding per operation, no contraction, correctly rounded division; lum is the expression of
+ *     spt_accumulate_moments_device.  Restated bit for bit by tests/temporal_var_expected.py (numpy) and tests/test_gpu_temporal_var.py.
+ *   spt_temporal_variance*: `hist` is a history as spt_temporal_accumulate* writes it (three float4 planes {mean rgb, len}, {n, c},
+ *     {x, m2}; 48 bytes per pixel, 16-byte aligned); the outputs are w*h floats each, row 0 at the bottom, 4-byte aligned.  Per pixel p with
+ *     {r, g, b, len}, {n_p, c_p}, {x_p, m2_p} and L_p = lum(r, g, b):
+ *       len >= min_len (the temporal branch):  v = m2_p - L_p*L_p;  v = v > 0 ? v : 0  -- out_var of spt_temporal_accumulate.
+ *       otherwise (the spatial branch):  s1 = s2 = sw = 0; for dy = -3..3 (outer), dx = -3..3 (inner), q = p + (dx, dy), skipping taps
+ *         outside the image and taps with (c_q > 0) != (c_p > 0):
+ *           dn = n_p - n_q;  en = (dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z
+ *           d = x_q - x_p;   pl = (n_p.x*d.x + n_p.y*d.y) + n_p.z*d.z;  ep = pl*pl
+ *           D = 1 + (sigma_normal*en + sigma_plane*ep);  wt = 1 / D
+ *           s1 += wt * L_q;  s2 += wt * m2_q;  sw += wt          (in that order; the centre is tap 25 with wt = 1, so sw >= 1)
+ *         m = s1 / sw;  s = s2 / sw;  v = s - m*m;  v = v > 0 ? v : 0;  boost = min_len / len;  v = v * boost
+ *       out_var[p] = v (the estimate of one frame's luminance variance; skipped when NULL); out_var_mean[p] = v / len (the variance of
+ *       the pixel's mean: what spt_denoise_pvar* takes).  A history with non-finite len, m2 or means is outside the contract.
+ *     spt_temporal_variance_device: DEVICE buffers; asynchronous on hip_stream (NULL = the context's).  It uses no scratch and no state of
+ *       the context, so calls are ordered by their streams alone.  spt_temporal_variance: host buffers, blocking; staged through the
+ *       context's scratch as spt_temporal_accumulate does.
+ *     Parameters: min_len >= 1 and finite; sigma_normal, sigma_plane >= 0 and finite.  Defaults (spt_temporal_var_params_default): 4, 32,
+ *       0.2 -- SVGF's history threshold and the filter's own normal and plane strengths.
+ *     Failures (message in spt_last_error, nothing launched, nothing written): a NULL hist, params or out_var_mean; w or h of 0, or w*h
+ *       above 2^31 - 1; a parameter out of range or not finite; a history pointer that is not 16-byte aligned; an output that is not 4-byte
+ *       aligned; an output that overlaps the history or the other output.
+ *   spt_denoise_pvar*: the contract of spt_denoise_var* word for word -- guides, passes, weights, validation, scratch, serialisation
+ *     of a context's filter calls, "changes no render state" -- except that the colour image's fourth float starts as variance[p]: there is
+ *     no `frames` and no `m2`.  `variance` is w*h floats, >= 0 and finite: the variance of the luminance of `beauty` as given, whether
+ *     `beauty` is a sum or a mean.  It is an input like the others: 4-byte aligned, and d_out may not equal it.
+ *   The loop (preconditions of spt_progressive_temporal_display_snapshot: begun, and at least one frame made):
+ *     spt_progressive_temporal_denoised_var_snapshot(ctx, var_params, denoise_params, out_rgb, out_var_mean)   on the context's stream:
+ *       spt_temporal_variance of the current history into scratch of the loop, then spt_denoise_pvar with beauty = the loop's mean image,
+ *       the last frame's four guide sums and aov_samples = its 4 * samps; out_rgb receives the w*h*3 floats and, where not NULL,
+ *       out_var_mean the w*h floats of the estimate.  Bit for bit spt_denoise_pvar of the float snapshot, those guides and
+ *       spt_temporal_variance of the history.
+ *     spt_progressive_temporal_display_var_snapshot(ctx, var_params, denoise_params, display_params, out8)   the same followed by the
+ *       display kernel, so that only the bytes cross the host link: byte for byte spt_display of the float form.
+ *     Both leave the history, the frames and every other accumulator unchanged.  Their scratch (4 bytes per pixel) is grown on demand and
+ *     freed by spt_progressive_end, the next begin and spt_destroy; a failed allocation fails the call and leaves the context usable. */
+typedef struct spt_temporal_var_params {
+    float min_len;       /* >= 1: histories shorter than this take the spatial estimate */
+    float sigma_normal;  /* >= 0: strength of the squared normal difference in a spatial tap's weight */
+    float sigma_plane;   /* >= 0: strength of the squared distance from the pixel's tangent plane, 1 / (scene length)^2 */
+} spt_temporal_var_params;
+#if defined(__cplusplus)
+static_assert(sizeof(spt_temporal_var_params) == 12, "spt_temporal_var_params: 12 bytes");
+#else
+_Static_assert(sizeof(spt_temporal_var_params) == 12, "spt_temporal_var_params: 12 bytes");
+#endif
+/* Host-only: min_len = 4, sigma_normal = 32, sigma_plane = 0.2. */
+void spt_temporal_var_params_default(spt_temporal_var_params* params);
+int  spt_temporal_variance_device(spt_ctx* ctx, const void* d_hist, uint32_t w, uint32_t h, const spt_temporal_var_params* params,
+                                  void* d_out_var_mean, void* d_out_var, void* hip_stream);
+int  spt_temporal_variance(spt_ctx* ctx, const void* hist, uint32_t w, uint32_t h, const spt_temporal_var_params* params,
+                           float* out_var_mean, float* out_var);
+int  spt_denoise_pvar_device(spt_ctx* ctx, const void* d_beauty, const void* d_normal, const void* d_albedo, const void* d_position,
+                             const void* d_coverage, const void* d_variance, uint32_t w, uint32_t h, uint32_t aov_samples,
+                             const spt_denoise_var_params* params, void* d_out, void* hip_stream);
+int  spt_denoise_pvar(spt_ctx* ctx, const float* beauty, const float* normal, const float* albedo, const float* position,
+                      const float* coverage, const float* variance, uint32_t w, uint32_t h, uint32_t aov_samples,
+                      const spt_denoise_var_params* params, float* out);
+int  spt_progressive_temporal_denoised_var_snapshot(spt_ctx* ctx, const spt_temporal_var_params* var_params,
+                                                    const spt_denoise_var_params* denoise_params, float* out_rgb, float* out_var_mean);
+int  spt_progressive_temporal_display_var_snapshot(spt_ctx* ctx, const spt_temporal_var_params* var_params,
+                                                   const spt_denoise_var_params* denoise_params, const spt_display_params* display_params,
+                                                   uint8_t* out8);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,10 @@ class SptTemporalParams(C.Structure):  # spt_temporal_params: 16 bytes
     _fields_ = [("alpha", C.c_float), ("max_len", C.c_float), ("tau_normal", C.c_float), ("tau_plane", C.c_float)]
 
 
+class SptTemporalVarParams(C.Structure):  # spt_temporal_var_params: 12 bytes
+    _fields_ = [("min_len", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
+
 class SptInstance(C.Structure):      # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
     _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
 
@@ -147,6 +151,14 @@ SYMBOLS = {
     "spt_progressive_temporal_frame": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint64, C.c_int, C.POINTER(SptStats)]),
     "spt_progressive_temporal_snapshot": (C.c_int, [_P, _P, _P, _P]),
     "spt_progressive_temporal_display_snapshot": (C.c_int, [_P, C.POINTER(SptDenoiseParams), C.POINTER(SptDisplayParams), _P]),
+    "spt_temporal_var_params_default": (None, [C.POINTER(SptTemporalVarParams)]),
+    "spt_temporal_variance_device": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(SptTemporalVarParams), _P, _P, _P]),
+    "spt_temporal_variance": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(SptTemporalVarParams), _P, _P]),
+    "spt_denoise_pvar_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseVarParams), _P, _P]),
+    "spt_denoise_pvar": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDenoiseVarParams), _P]),
+    "spt_progressive_temporal_denoised_var_snapshot": (C.c_int, [_P, C.POINTER(SptTemporalVarParams), C.POINTER(SptDenoiseVarParams), _P, _P]),
+    "spt_progressive_temporal_display_var_snapshot": (C.c_int, [_P, C.POINTER(SptTemporalVarParams), C.POINTER(SptDenoiseVarParams),
+                                                                C.POINTER(SptDisplayParams), _P]),
 }
 
 # test / tuning hooks declared in csrc/spt_internal.h (not part of the drop-in boundary)

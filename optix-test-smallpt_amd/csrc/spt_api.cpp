@@ -14,6 +14,8 @@
 #include "spt_display.h"
 #include "spt_temporal.h"
 #include "spt_temporal_host.h"
+#include "spt_temporal_var.h"
+#include "spt_temporal_var_host.h"
 #include "spt_devbuf.h"
 
 #include <chrono>
@@ -100,11 +102,12 @@ struct DenoiseScratch {
 };
 // spt_progressive_temporal_*: the parameters of the begin, two histories (hist[cur] holds the last frame's), the loop's own radiance
 // frame, its NORMAL / ALBEDO / POSITION / COVERAGE frames (one allocation), the {mean rgb | var | len} image of the last frame, that
-// frame's camera and 4 * samps, and whether hist[cur] is a history yet
+// frame's camera and 4 * samps, and whether hist[cur] is a history yet; var = the w*h floats of the variance estimate the *_var_snapshot
+// entries filter under (spt_temporal_var.hip), grown by their first call
 struct Temporal {
     bool on = false; spt_temporal_params params{};
     DevBuf<float4> hist[2]; int cur = 0; bool have = false;
-    DevBuf<float> frame, guides, out;
+    DevBuf<float> frame, guides, out, var;
     spt_camera cam{}; uint32_t samples = 0;
 };
 
@@ -2405,23 +2408,32 @@ void spt_denoise_var_params_default(spt_denoise_var_params* p)
     p->sigma_colour = 0.5f;
 }
 
-// denoise_check of the four old fields (copied to *four) plus the two conditions of the variance-guided filter
-static int denoise_var_check(spt_ctx* c, const char* who, uint32_t w, uint32_t h, uint32_t aov_samples, uint32_t frames, const spt_denoise_var_params* p,
-                             spt_denoise_params* four)
+// denoise_check of the four old fields (copied to *four) plus the condition on sigma_colour: the filter with a caller's variance
+static int denoise_pvar_check(spt_ctx* c, const char* who, uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_var_params* p,
+                              spt_denoise_params* four)
 {
     if (!p) return c->fail("%s: NULL argument", who);
     *four = spt_denoise_params{p->levels, p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage};
     if (int rc = denoise_check(c, who, w, h, aov_samples, four)) return rc;
     if (!std::isfinite(p->sigma_colour) || p->sigma_colour < 0.f) return c->fail("%s: sigma_colour = %g is negative or not finite", who, (double)p->sigma_colour);
+    return 0;
+}
+
+// ... plus the condition on the frame count: the filter with the second moments of `frames` frames
+static int denoise_var_check(spt_ctx* c, const char* who, uint32_t w, uint32_t h, uint32_t aov_samples, uint32_t frames, const spt_denoise_var_params* p,
+                             spt_denoise_params* four)
+{
+    if (int rc = denoise_pvar_check(c, who, w, h, aov_samples, p, four)) return rc;
     if (frames < 2) return c->fail("%s: frames = %u: the variance of the frames needs at least 2", who, frames);
     return 0;
 }
 
 // Validated arguments, device set.  Enqueues the guide pack and the passes on st behind the context's previous filter.  m2 != nullptr
-// selects the variance-guided kernels (spt_denoise_var.hip) with the second moments of `frames` frames and sigma_colour.
+// selects the variance-guided kernels (spt_denoise_var.hip) with the second moments of `frames` frames and sigma_colour; pvar != nullptr
+// selects them with that per-pixel variance as given (the pack of spt_temporal_var.hip) and sigma_colour.
 static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, const float* normal, const float* albedo, const float* position,
                            const float* coverage, uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_params* p, float* out,
-                           hipStream_t st, const float* m2 = nullptr, uint32_t frames = 0, float sigma_colour = 0.f)
+                           hipStream_t st, const float* m2 = nullptr, uint32_t frames = 0, float sigma_colour = 0.f, const float* pvar = nullptr)
 {
     const size_t npix = (size_t)w * h;
     if (npix > c->dn.guides.cap || npix > c->dn.ping.cap || npix > c->dn.pong.cap) {
@@ -2439,7 +2451,8 @@ static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, con
         for (hipEvent_t& e : c->dn_ev) if (!e) SPT_HIP(c, hipEventCreate(&e));
         SPT_HIP(c, hipEventRecord(c->dn_ev[0], st));
     }
-    if (m2) SPT_HIP(c, spt_denoise_var_pack_launch(beauty, normal, albedo, position, coverage, m2, (uint32_t)npix, (float)aov_samples, (float)frames, c->dn.ping, c->dn.guides, st));
+    if (pvar) SPT_HIP(c, spt_denoise_pvar_pack_launch(beauty, normal, albedo, position, coverage, pvar, (uint32_t)npix, (float)aov_samples, c->dn.ping, c->dn.guides, st));
+    else if (m2) SPT_HIP(c, spt_denoise_var_pack_launch(beauty, normal, albedo, position, coverage, m2, (uint32_t)npix, (float)aov_samples, (float)frames, c->dn.ping, c->dn.guides, st));
     else SPT_HIP(c, spt_denoise_pack_launch(beauty, normal, albedo, position, coverage, (uint32_t)npix, (float)aov_samples, c->dn.ping, c->dn.guides, st));
     const float sigma[5] = {p->sigma_normal, p->sigma_plane, p->sigma_albedo, p->sigma_coverage, sigma_colour};
     if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[1], st));
@@ -2447,7 +2460,7 @@ static int denoise_enqueue(spt_ctx* c, const char* who, const float* beauty, con
     float4* dst = c->dn.pong;
     for (uint32_t i = 0; i < p->levels; ++i) {
         const bool last = i + 1 == p->levels;
-        if (m2) SPT_HIP(c, spt_denoise_var_pass_launch(src, c->dn.guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
+        if (m2 || pvar) SPT_HIP(c, spt_denoise_var_pass_launch(src, c->dn.guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
         else SPT_HIP(c, spt_denoise_pass_launch(src, c->dn.guides, w, h, 1u << i, sigma, c->denoise_form == 0, dst, last ? out : nullptr, st));
         if (timed) SPT_HIP(c, hipEventRecord(c->dn_ev[2 + i], st));
         std::swap(src, dst);
@@ -2583,6 +2596,48 @@ int spt_denoise_var(spt_ctx* c, const float* beauty, const float* normal, const 
     SPT_HIP(c, hipMemcpyAsync(d + 6 * pitch, m2, (size_t)w * h * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (int rc = denoise_enqueue(c, "spt_denoise_var", d, d + pitch, d + 2 * pitch, d + 3 * pitch, d + 4 * pitch, w, h, aov_samples, &four, d + 5 * pitch, c->stream,
                                  d + 6 * pitch, frames, p->sigma_colour)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out, d + 5 * pitch, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the variance-guided filter with a caller-supplied per-pixel variance (the pack of spt_temporal_var.hip) ----
+int spt_denoise_pvar_device(spt_ctx* c, const void* d_beauty, const void* d_normal, const void* d_albedo, const void* d_position, const void* d_coverage,
+                            const void* d_variance, uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_var_params* p, void* d_out, void* hip_stream)
+{
+    if (!c) return 1;
+    if (!d_beauty || !d_normal || !d_albedo || !d_position || !d_coverage || !d_variance || !d_out) return c->fail("spt_denoise_pvar_device: NULL argument");
+    spt_denoise_params four;
+    if (int rc = denoise_pvar_check(c, "spt_denoise_pvar_device", w, h, aov_samples, p, &four)) return rc;
+    const void* const ptrs[7] = {d_beauty, d_normal, d_albedo, d_position, d_coverage, d_variance, d_out};
+    for (const void* q : ptrs)
+        if (reinterpret_cast<uintptr_t>(q) & 3u) return c->fail("spt_denoise_pvar_device: buffers must be 4-byte aligned");
+    for (int i = 0; i < 6; ++i)
+        if (ptrs[i] == d_out) return c->fail("spt_denoise_pvar_device: d_out aliases an input");
+    SPT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return denoise_enqueue(c, "spt_denoise_pvar_device", static_cast<const float*>(d_beauty), static_cast<const float*>(d_normal), static_cast<const float*>(d_albedo),
+                           static_cast<const float*>(d_position), static_cast<const float*>(d_coverage), w, h, aov_samples, &four, static_cast<float*>(d_out), st,
+                           nullptr, 0, p->sigma_colour, static_cast<const float*>(d_variance));
+}
+
+int spt_denoise_pvar(spt_ctx* c, const float* beauty, const float* normal, const float* albedo, const float* position, const float* coverage,
+                     const float* variance, uint32_t w, uint32_t h, uint32_t aov_samples, const spt_denoise_var_params* p, float* out)
+{
+    if (!c) return 1;
+    if (!beauty || !normal || !albedo || !position || !coverage || !variance || !out) return c->fail("spt_denoise_pvar: NULL argument");
+    spt_denoise_params four;
+    if (int rc = denoise_pvar_check(c, "spt_denoise_pvar", w, h, aov_samples, p, &four)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    const size_t nfl = (size_t)w * h * 3, pitch = (nfl + 3) & ~(size_t)3;
+    if (grow_out(c, pitch * 7)) return 1;
+    const float* const host[5] = {beauty, normal, albedo, position, coverage};
+    for (int j = 0; j < 5; ++j)
+        SPT_HIP(c, hipMemcpyAsync(c->d_out + j * pitch, host[j], nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float* const d = c->d_out;
+    SPT_HIP(c, hipMemcpyAsync(d + 6 * pitch, variance, (size_t)w * h * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int rc = denoise_enqueue(c, "spt_denoise_pvar", d, d + pitch, d + 2 * pitch, d + 3 * pitch, d + 4 * pitch, w, h, aov_samples, &four, d + 5 * pitch, c->stream,
+                                 nullptr, 0, p->sigma_colour, d + 6 * pitch)) return rc;
     SPT_HIP(c, hipMemcpyAsync(out, d + 5 * pitch, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -2877,6 +2932,109 @@ int spt_progressive_temporal_display_snapshot(spt_ctx* c, const spt_denoise_para
         src = c->dn.out;
     }
     return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);
+}
+
+// ---- variance estimate from a temporal history (spt_temporal_var.hip; the contract is stated in include/smallpt_mi355x.h) ----
+void spt_temporal_var_params_default(spt_temporal_var_params* p)
+{
+    if (!p) return;
+    p->min_len = 4.0f;
+    p->sigma_normal = 32.0f;
+    p->sigma_plane = 0.2f;
+}
+
+int spt_temporal_variance_device(spt_ctx* c, const void* d_hist, uint32_t w, uint32_t h, const spt_temporal_var_params* p, void* d_out_var_mean,
+                                 void* d_out_var, void* hip_stream)
+{
+    if (!c) return 1;
+    const spt::TemporalVarCall k{d_hist, d_out_var_mean, d_out_var, w, h, p, true};
+    char msg[256];
+    if (spt::temporal_var_validate(k, "spt_temporal_variance_device", msg, sizeof msg)) return c->fail("%s", msg);
+    SPT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    SPT_HIP(c, spt_temporal_variance_launch(static_cast<const float4*>(d_hist), w, h, p->min_len, p->sigma_normal, p->sigma_plane,
+                                            static_cast<float*>(d_out_var_mean), static_cast<float*>(d_out_var), st));
+    return 0;
+}
+
+int spt_temporal_variance(spt_ctx* c, const void* hist, uint32_t w, uint32_t h, const spt_temporal_var_params* p, float* out_var_mean, float* out_var)
+{
+    if (!c) return 1;
+    const spt::TemporalVarCall k{hist, out_var_mean, out_var, w, h, p, false};
+    char msg[256];
+    if (spt::temporal_var_validate(k, "spt_temporal_variance", msg, sizeof msg)) return c->fail("%s", msg);
+    SPT_HIP(c, hipSetDevice(c->device));
+    // staging, in floats, every piece 16-byte aligned: the history | var of the mean | var
+    const size_t npix = (size_t)w * h, plane = (npix + 3) & ~(size_t)3, nh = npix * 12;
+    if (grow_out(c, nh + 2 * plane)) return 1;
+    float* const d = c->d_out;
+    SPT_HIP(c, hipMemcpyAsync(d, hist, nh * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, spt_temporal_variance_launch(reinterpret_cast<const float4*>(d), w, h, p->min_len, p->sigma_normal, p->sigma_plane, d + nh,
+                                            out_var ? d + nh + plane : nullptr, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(out_var_mean, d + nh, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_var) SPT_HIP(c, hipMemcpyAsync(out_var, d + nh + plane, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Validated loop state and parameters, device set.  Enqueues on the context's stream: the variance estimate of the current history into
+// tp.var, then the filter of the mean under it and the last frame's guides into dn.out.
+static int temporal_denoised_var_enqueue(spt_ctx* c, const char* who, const spt_temporal_var_params* vp, const spt_denoise_params* four, float sigma_colour)
+{
+    const uint32_t w = c->prog_w, h = c->prog_h;
+    const size_t npix = (size_t)w * h, nfl = npix * 3, pitch = temporal_pitch(c);
+    if (npix > c->tp.var.cap || nfl > c->dn.out.cap) {
+        if (c->denoise_recorded) SPT_HIP(c, hipEventSynchronize(c->ev_denoise));
+        hipError_t e = c->tp.var.grow(npix);
+        if (e == hipSuccess) e = c->dn.out.grow(nfl);
+        if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: scratch: %s", who, hipGetErrorString(e)); }
+    }
+    SPT_HIP(c, spt_temporal_variance_launch(c->tp.hist[c->tp.cur], w, h, vp->min_len, vp->sigma_normal, vp->sigma_plane, c->tp.var, nullptr, c->stream));
+    const float* const g = c->tp.guides;
+    return denoise_enqueue(c, who, c->tp.out, g, g + pitch, g + 2 * pitch, g + 3 * pitch, w, h, c->tp.samples, four, c->dn.out, c->stream, nullptr, 0,
+                           sigma_colour, c->tp.var);
+}
+
+// The checks the two *_var_snapshot entries share; *four receives the filter's four old fields
+static int temporal_denoised_var_check(spt_ctx* c, const char* who, const void* out, const spt_temporal_var_params* vp, const spt_denoise_var_params* dp,
+                                       spt_denoise_params* four)
+{
+    if (!c->tp.on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (!out) return c->fail("%s: NULL argument (the output)", who);
+    if (!c->tp.have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
+    char msg[256];
+    if (spt::temporal_var_params_check(vp, who, msg, sizeof msg)) return c->fail("%s", msg);
+    return denoise_pvar_check(c, who, c->prog_w, c->prog_h, c->tp.samples, dp, four);
+}
+
+int spt_progressive_temporal_denoised_var_snapshot(spt_ctx* c, const spt_temporal_var_params* vp, const spt_denoise_var_params* dp, float* out_rgb,
+                                                   float* out_var_mean)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_temporal_denoised_var_snapshot";
+    spt_denoise_params four;
+    if (int rc = temporal_denoised_var_check(c, who, out_rgb, vp, dp, &four)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (int rc = temporal_denoised_var_enqueue(c, who, vp, &four, dp->sigma_colour)) return rc;
+    const size_t npix = (size_t)c->prog_w * c->prog_h;
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->dn.out, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (out_var_mean) SPT_HIP(c, hipMemcpyAsync(out_var_mean, c->tp.var, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int spt_progressive_temporal_display_var_snapshot(spt_ctx* c, const spt_temporal_var_params* vp, const spt_denoise_var_params* dp,
+                                                  const spt_display_params* p, uint8_t* out8)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_temporal_display_var_snapshot";
+    spt_denoise_params four;
+    if (int rc = temporal_denoised_var_check(c, who, out8, vp, dp, &four)) return rc;
+    if (int rc = display_check(c, who, c->prog_w, c->prog_h, p)) return rc;
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (int rc = display_table(c, who)) return rc;
+    if (int rc = temporal_denoised_var_enqueue(c, who, vp, &four, dp->sigma_colour)) return rc;
+    return display_to_host(c, who, c->dn.out, c->prog_w, c->prog_h, p, out8);
 }
 
 // Test / measurement hook (spt_internal.h)

@@ -217,6 +217,52 @@ public:
     {
         check(spt_progressive_temporal_display_snapshot(ctx_, denoiseParams, &params, image.data()));
     }
+    // The loop's mean under the variance-guided filter with the variance estimated from its own history (spt_temporal_variance +
+    // spt_denoise_pvar on the device); nullptr = the defaults.  varianceOfMean receives the estimate the filter ran under.
+    void progressiveTemporalDenoisedVarSnapshot(std::vector<float3>& image, const spt_temporal_var_params* varParams = nullptr,
+                                                const spt_denoise_var_params* denoiseParams = nullptr, std::vector<float>* varianceOfMean = nullptr)
+    {
+        spt_temporal_var_params vp;
+        spt_denoise_var_params dp;
+        if (varParams) vp = *varParams; else spt_temporal_var_params_default(&vp);
+        if (denoiseParams) dp = *denoiseParams; else spt_denoise_var_params_default(&dp);
+        if (varianceOfMean) varianceOfMean->resize(image.size());
+        check(spt_progressive_temporal_denoised_var_snapshot(ctx_, &vp, &dp, reinterpret_cast<float*>(image.data()),
+                                                             varianceOfMean ? varianceOfMean->data() : nullptr));
+    }
+    void progressiveTemporalDisplayVarSnapshot(std::vector<uint8_t>& image, const spt_display_params& params,
+                                               const spt_temporal_var_params* varParams = nullptr, const spt_denoise_var_params* denoiseParams = nullptr)
+    {
+        spt_temporal_var_params vp;
+        spt_denoise_var_params dp;
+        if (varParams) vp = *varParams; else spt_temporal_var_params_default(&vp);
+        if (denoiseParams) dp = *denoiseParams; else spt_denoise_var_params_default(&dp);
+        check(spt_progressive_temporal_display_var_snapshot(ctx_, &vp, &dp, &params, image.data()));
+    }
+    // The pieces on a caller's buffers: the variance estimate of a 12 * w * h float history (host), and the filter under a per-pixel variance
+    std::vector<float> temporalVariance(const std::vector<float>& history, size_t imageWidth, size_t imageHeight, std::vector<float>* variance = nullptr,
+                                        const spt_temporal_var_params* params = nullptr)
+    {
+        const size_t n = imageWidth * imageHeight;
+        if (history.size() != 12 * n) throw std::runtime_error("temporalVariance: a history of 12 floats per pixel");
+        spt_temporal_var_params p;
+        if (params) p = *params; else spt_temporal_var_params_default(&p);
+        std::vector<float> ofMean(n);
+        if (variance) variance->resize(n);
+        check(spt_temporal_variance(ctx_, history.data(), (uint32_t)imageWidth, (uint32_t)imageHeight, &p, ofMean.data(), variance ? variance->data() : nullptr));
+        return ofMean;
+    }
+    void temporalVarianceDevice(const void* dHist, size_t imageWidth, size_t imageHeight, const spt_temporal_var_params& params, void* dOutVarMean,
+                                void* dOutVar = nullptr, void* hipStream = nullptr)
+    {
+        check(spt_temporal_variance_device(ctx_, dHist, (uint32_t)imageWidth, (uint32_t)imageHeight, &params, dOutVarMean, dOutVar, hipStream));
+    }
+    void denoisePvarDevice(const void* dBeauty, const void* dNormal, const void* dAlbedo, const void* dPosition, const void* dCoverage, const void* dVariance,
+                           size_t imageWidth, size_t imageHeight, size_t aovSamples, const spt_denoise_var_params& params, void* dOut, void* hipStream = nullptr)
+    {
+        check(spt_denoise_pvar_device(ctx_, dBeauty, dNormal, dAlbedo, dPosition, dCoverage, dVariance, (uint32_t)imageWidth, (uint32_t)imageHeight,
+                                      (uint32_t)aovSamples, &params, dOut, hipStream));
+    }
 
     // accumBuffer of the viewer loop in HBM (spt_progressive_*, smallpt.cpp:881-883,922-937,955-959)
     void progressiveBegin(size_t w, size_t h) { check(spt_progressive_begin(ctx_, (uint32_t)w, (uint32_t)h)); }

@@ -304,17 +304,22 @@ bool parse_update_camera_request(const std::string& text, float3* org)
     return true;
 }
 
-bool parse_request_temporal(const std::string& text, bool* temporal)
+// An optional boolean field of a render request: true and *value filled when it is present
+static bool request_flag(const std::string& text, const char* name, bool* value)
 {
     Parser p(text);
     JPtr root = p.parse();
     if (root->kind != JValue::Object) throw std::runtime_error("render request: expected a JSON object");
-    auto t = root->obj.find("temporal");
+    auto t = root->obj.find(name);
     if (t == root->obj.end()) return false;
-    if (t->second->kind != JValue::Bool) throw std::runtime_error("render request: \"temporal\" must be true or false");
-    *temporal = t->second->b;
+    if (t->second->kind != JValue::Bool) throw std::runtime_error(std::string("render request: \"") + name + "\" must be true or false");
+    *value = t->second->b;
     return true;
 }
+
+bool parse_request_temporal(const std::string& text, bool* temporal) { return request_flag(text, "temporal", temporal); }
+
+bool parse_request_temporal_denoise(const std::string& text, bool* denoise) { return request_flag(text, "temporal_denoise", denoise); }
 
 Scene load_scene_file(const std::string& path)
 {

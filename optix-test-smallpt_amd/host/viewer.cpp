@@ -87,6 +87,7 @@ void ProgressiveRenderer::postRequest(const std::string& json)
     bool ignoredFlag;
     (void)parseUpdateCamera(json, &ignored);         // malformed text is refused HERE, on the caller's thread, not in the render thread
     (void)parse_request_temporal(json, &ignoredFlag);
+    (void)parse_request_temporal_denoise(json, &ignoredFlag);
     std::unique_lock<std::mutex> l{requestsMutex_};  // :980
     requests_.emplace_back(json);
 }
@@ -102,7 +103,7 @@ void ProgressiveRenderer::moveCamera(float dy)
 void ProgressiveRenderer::stepOnce()
 {
     bool needClearBuffer = false;                    // :903
-    bool temporal = false, temporalGiven = false;
+    bool temporal = false, temporalGiven = false, denoise = false, denoiseGiven = false;
     {
         std::unique_lock<std::mutex> l{requestsMutex_};   // :906
         for (const std::string& request : requests_) {    // :909
@@ -113,6 +114,7 @@ void ProgressiveRenderer::stepOnce()
             }
             bool t;
             if (parse_request_temporal(request, &t)) { temporal = t; temporalGiven = true; }
+            if (parse_request_temporal_denoise(request, &t)) { denoise = t; denoiseGiven = true; }
         }
         requests_.clear();                           // :918
     }
@@ -123,6 +125,7 @@ void ProgressiveRenderer::stepOnce()
     }
     // :922 render + :927-937 accumulate, both on the device; the lock keeps a snapshot from reading a half-added frame
     std::unique_lock<std::mutex> l{accumMutex_};     // :925
+    if (denoiseGiven) temporalDenoise_ = denoise;    // changes the snapshots only
     if (temporalGiven && temporal != temporal_) {
         for (size_t i = 0; i < lanes_.size(); ++i)   // the two loops take turns on this context: drain what is in flight
             if (inFlight_[i]) { inFlight_[i] = 0; lanes_[i]->progressiveWait(); }
@@ -156,7 +159,8 @@ bool ProgressiveRenderer::snapshotLocked(std::vector<float3>& image, float weigh
 {
     image.resize(w_ * h_);
     if (temporal_ && !temporalReset_) {              // the temporal loop's picture is a mean already
-        renderer_.progressiveTemporalSnapshot(image);
+        if (temporalDenoise_) renderer_.progressiveTemporalDenoisedVarSnapshot(image);
+        else renderer_.progressiveTemporalSnapshot(image);
         weight3[0] = weight3[1] = weight3[2] = 1.f;
         return true;
     }
@@ -186,7 +190,8 @@ void ProgressiveRenderer::snapshotDisplay(std::vector<uint8_t>& image, uint32_t 
     image.resize(w_ * h_ * (format == SPT_DISPLAY_RGBA8 ? 4 : 3));
     if (temporal_ && !temporalReset_) {
         p.weight[0] = p.weight[1] = p.weight[2] = 1.f;
-        renderer_.progressiveTemporalDisplaySnapshot(image, p);
+        if (temporalDenoise_) renderer_.progressiveTemporalDisplayVarSnapshot(image, p);
+        else renderer_.progressiveTemporalDisplaySnapshot(image, p);
         return;
     }
     renderer_.progressiveDisplaySnapshot(image, p);
@@ -208,6 +213,12 @@ bool ProgressiveRenderer::temporal()
 {
     std::unique_lock<std::mutex> l{accumMutex_};
     return temporal_;
+}
+
+bool ProgressiveRenderer::temporalDenoise()
+{
+    std::unique_lock<std::mutex> l{accumMutex_};
+    return temporalDenoise_;
 }
 
 size_t ProgressiveRenderer::sampleCount()

@@ -11,7 +11,9 @@
 //   keys UP/DOWN move org.y by 0.01 and post a request (:968-985)     moveCamera(dy)
 //   needClearBuffer on a camera change (:915, :931-933)               a request may carry "temporal": true (opt-in, default off): from
 //                                                                       then on a frame goes through spt_progressive_temporal_frame and a
-//                                                                       camera change keeps the reprojected history instead of clearing
+//                                                                       camera change keeps the reprojected history instead of clearing;
+//                                                                       "temporal_denoise": true (opt-in, default off) shows that loop's
+//                                                                       mean under the variance-guided filter, default parameters
 //   exit: accumBuffer /= sampleCount*spp, flipY, writeImage (:995-1004)  finalImage()
 //
 // accumBuffer lives in HBM (spt_progressive_*); the mutex guards the frame counter and the request queue like the
@@ -73,7 +75,10 @@ public:
     size_t sampleCount();                           // frames accumulated since the last clear
     // whether the render thread currently runs the temporal loop (the last "temporal" field a request carried; off until one does).
     // While it is on, snapshot() returns the loop's MEAN image with weight 1 and snapshotDisplay() its 8-bit form; extra lanes idle.
+    // With the last "temporal_denoise" field on as well, both return that mean under the variance-guided filter
+    // (spt_progressive_temporal_denoised_var_snapshot / _display_var_snapshot with the default parameters).
     bool temporal();
+    bool temporalDenoise();
     size_t framesRendered() const { return framesRendered_; }
 
 private:
@@ -90,6 +95,7 @@ private:
     std::vector<std::string> requests_;
     size_t sampleCount_ = 0;   // :893
     bool temporal_ = false, temporalBegun_ = false, temporalReset_ = true;   // guarded by accumMutex_
+    bool temporalDenoise_ = false;                                           // guarded by accumMutex_
     std::atomic<size_t> framesRendered_{0};
     std::atomic<bool> renderDone_{false};      // the reference uses a plain float here (:894), a data race
     std::thread thread_;

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, SptTemporalParams, load_library, load_multi_library
+from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, SptTemporalParams, SptTemporalVarParams, load_library, load_multi_library
 from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
@@ -278,6 +278,33 @@ class TemporalParams:
 
 def _temporal_params(params):
     return (params if params is not None else TemporalParams()).as_c()
+
+
+class TemporalVarParams:
+    """Parameters of the variance estimate from a temporal history (spt_temporal_var_params): ``min_len`` >= 1, the history length below
+    which a pixel takes the 7 x 7 spatial estimate instead of its own temporal variance; ``sigma_normal`` and ``sigma_plane`` >= 0, the
+    strengths of the squared normal difference and of the squared distance from the pixel's tangent plane in a spatial tap's weight.
+    Anything left None takes the library's default (spt_temporal_var_params_default: 4, 32, 0.2)."""
+    FIELDS = ("min_len", "sigma_normal", "sigma_plane")
+
+    def __init__(self, min_len=None, sigma_normal=None, sigma_plane=None):
+        c = SptTemporalVarParams()
+        load_library().spt_temporal_var_params_default(C.byref(c))
+        for name, v in zip(self.FIELDS, (min_len, sigma_normal, sigma_plane)):
+            setattr(self, name, getattr(c, name) if v is None else float(v))
+
+    def as_c(self):
+        c = SptTemporalVarParams()
+        for name in self.FIELDS:
+            setattr(c, name, getattr(self, name))
+        return c
+
+    def __repr__(self):
+        return "TemporalVarParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.FIELDS) + ")"
+
+
+def _temporal_var_params(params):
+    return (params if params is not None else TemporalVarParams()).as_c()
 
 
 def temporal_history_bytes(w, h):
@@ -839,6 +866,60 @@ class Renderer:
             C.byref(prev_camera) if prev_camera is not None else None, dp(hist_prev_t), dp(hist_next_t), C.byref(p), dp(out_rgb_t), dp(out_var_t),
             dp(out_len_t), C.c_void_p(stream) if stream else None))
 
+    def temporal_variance(self, history, params=None, var=False):
+        """SVGF's variance estimate from a temporal history (spt_temporal_variance): ``history`` the (3, h, w, 4) float32 array
+        ``temporal_accumulate`` returns.  A pixel whose history length is at least ``params.min_len`` takes its temporal variance, a
+        younger one the boosted 7 x 7 spatial estimate.  Returns the (h, w) float32 variance of the pixel's MEAN (what ``denoise_pvar``
+        takes); with ``var`` a tuple (that, the (h, w) estimate of one frame's variance)."""
+        history = np.ascontiguousarray(history, dtype=np.float32)
+        if history.ndim != 4 or history.shape[0] != 3 or history.shape[3] != 4:
+            raise ValueError("temporal_variance: history is a (3, h, w, 4) float32 array")
+        _, h, w, _ = history.shape
+        vm = np.empty((h, w), dtype=np.float32)
+        v = np.empty((h, w), dtype=np.float32) if var else None
+        p = _temporal_var_params(params)
+        self._check(self._lib.spt_temporal_variance(self._h, history.ctypes.data_as(C.c_void_p), w, h, C.byref(p), vm.ctypes.data_as(C.c_void_p),
+                                                    v.ctypes.data_as(C.c_void_p) if var else None))
+        return (vm, v) if var else vm
+
+    def temporal_variance_device(self, hist_t, w, h, out_var_mean_t, out_var_t=None, params=None, stream=None):
+        """The same on float32 CUDA tensors (spt_temporal_variance_device): ``hist_t`` w*h*12 elements and 16-byte aligned, the outputs w*h
+        elements (``out_var_t`` or None).  Asynchronous on ``stream`` (a raw hipStream_t, None = the context's stream).  No output may
+        overlap the history or the other output."""
+        for t, n in ((hist_t, w * h * 12), (out_var_mean_t, w * h), (out_var_t, w * h)):
+            if t is not None and (t.numel() != n or not t.is_contiguous() or str(t.dtype) != "torch.float32" or t.device.type != "cuda"):
+                raise ValueError("temporal_variance_device: contiguous float32 tensors on the GPU of w*h*12 (history) and w*h elements")
+        p = _temporal_var_params(params)
+        self._check(self._lib.spt_temporal_variance_device(self._h, C.c_void_p(hist_t.data_ptr()), w, h, C.byref(p), C.c_void_p(out_var_mean_t.data_ptr()),
+                                                           C.c_void_p(out_var_t.data_ptr()) if out_var_t is not None else None,
+                                                           C.c_void_p(stream) if stream else None))
+
+    def denoise_pvar(self, beauty, normal, albedo, position, coverage, variance, aov_samples, params=None):
+        """Variance-guided filter with a caller's per-pixel variance (spt_denoise_pvar): ``denoise_var`` with ``variance`` = (h, w)
+        float32, >= 0, the variance of the luminance of ``beauty`` as given (a sum or a mean) in place of ``m2`` and ``frames``.
+        Returns the filtered image, (h, w, 3) float32."""
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (beauty, normal, albedo, position, coverage)]
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+        if imgs[0].ndim != 3 or imgs[0].shape[2] != 3 or any(a.shape != imgs[0].shape for a in imgs) or variance.shape != imgs[0].shape[:2]:
+            raise ValueError("denoise_pvar: five (h, w, 3) images and one (h, w) image of one size")
+        h, w, _ = imgs[0].shape
+        out = np.empty((h, w, 3), dtype=np.float32)
+        p = _denoise_var_params(params)
+        self._check(self._lib.spt_denoise_pvar(self._h, *[a.ctypes.data_as(C.c_void_p) for a in imgs], variance.ctypes.data_as(C.c_void_p), w, h,
+                                               int(aov_samples), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoise_pvar_device(self, beauty_t, normal_t, albedo_t, position_t, coverage_t, variance_t, out_t, w, h, aov_samples, params=None, stream=None):
+        """The same on contiguous float32 CUDA tensors (spt_denoise_pvar_device): w*h*3 elements each, ``variance_t`` w*h; asynchronous on
+        ``stream`` (a raw hipStream_t, None = the context's stream).  ``out_t`` may not alias an input."""
+        ts = (beauty_t, normal_t, albedo_t, position_t, coverage_t, out_t, variance_t)
+        for t, n in zip(ts, (w * h * 3,) * 6 + (w * h,)):
+            if t.numel() != n or not t.is_contiguous() or str(t.dtype) != "torch.float32" or t.device.type != "cuda":
+                raise ValueError("denoise_pvar_device: contiguous float32 tensors of w*h*3 (variance_t: w*h) elements on the GPU")
+        p = _denoise_var_params(params)
+        self._check(self._lib.spt_denoise_pvar_device(self._h, *[C.c_void_p(t.data_ptr()) for t in ts[:5]], C.c_void_p(variance_t.data_ptr()), w, h,
+                                                      int(aov_samples), C.byref(p), C.c_void_p(out_t.data_ptr()), C.c_void_p(stream) if stream else None))
+
     def accumulate_moments_device(self, accum_t, m2_t, frame_t, clear=False, stream=None):
         """accum (``clear``: =, else +=) frame and m2 (=, +=) the squared luminance of frame, one kernel (spt_accumulate_moments_device):
         contiguous float32 CUDA tensors, ``accum_t`` and ``frame_t`` of npix*3 elements and 16-byte aligned, ``m2_t`` of npix elements.
@@ -980,6 +1061,30 @@ class Renderer:
         fp = None if denoise is None or denoise is False else _denoise_params(None if denoise is True else denoise)
         self._check(self._lib.spt_progressive_temporal_display_snapshot(self._h, C.byref(fp) if fp is not None else None, C.byref(p),
                                                                         out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def progressive_temporal_denoised_var_snapshot(self, var_params=None, params=None, var_mean=False):
+        """The temporal loop's mean under the variance-guided filter (spt_progressive_temporal_denoised_var_snapshot): the variance
+        estimate of the current history (``var_params`` a ``TemporalVarParams``), then ``denoise_pvar`` of the mean under it and the last
+        frame's guides (``params`` a ``DenoiseVarParams``).  Returns the (h, w, 3) float32 picture (display weight 1); with ``var_mean``
+        a tuple (picture, the (h, w) variance of the mean it was filtered under).  Nothing of the loop changes."""
+        w, h, _ = self._prog_size("progressive_temporal_denoised_var_snapshot")
+        out = np.empty((h, w, 3), dtype=np.float32)
+        vm = np.empty((h, w), dtype=np.float32) if var_mean else None
+        vp, p = _temporal_var_params(var_params), _denoise_var_params(params)
+        self._check(self._lib.spt_progressive_temporal_denoised_var_snapshot(self._h, C.byref(vp), C.byref(p), out.ctypes.data_as(C.c_void_p),
+                                                                             vm.ctypes.data_as(C.c_void_p) if var_mean else None))
+        return (out, vm) if var_mean else out
+
+    def progressive_temporal_display_var_snapshot(self, params=None, var_params=None, denoise=None):
+        """The same picture as 8-bit colour straight from the device (spt_progressive_temporal_display_var_snapshot): ``display`` with
+        ``params`` (a ``DisplayParams``; weight 1 suits a mean) of the filtered mean; ``denoise`` a ``DenoiseVarParams`` or None for the
+        defaults.  Returns uint8 (h, w, 3|4)."""
+        w, h, _ = self._prog_size("progressive_temporal_display_var_snapshot")
+        dp = _display_params(params)
+        out = np.empty((h, w, dp.channels), dtype=np.uint8)
+        p, vp, fp = dp.as_c(), _temporal_var_params(var_params), _denoise_var_params(denoise)
+        self._check(self._lib.spt_progressive_temporal_display_var_snapshot(self._h, C.byref(vp), C.byref(fp), C.byref(p), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def progressive_end(self):

@@ -5,9 +5,14 @@
            camera (reprojection) and of a camera at rest (identity rule), alternating call by call with spt_accumulate_moments_device
            on the same pixel count as the yardstick: medians of N (default 50) after 10 warm-up calls each; bytes per pixel the
            algorithm needs at the least (every input and output once, one history read) and the rate that gives.
+  estimate at the same size, HIP events around spt_temporal_variance_device (the variance estimate the variance-guided filter runs under)
+           on a history at rest (every workgroup skips its window), on the history after one camera move (the workgroups with
+           disoccluded pixels stage their tile) and with min_len out of reach (the 7 x 7 window at every pixel), against the same yardstick.
   loop     host wall time of spt_progressive_temporal_frame against spt_progressive_frame + spt_progressive_aov_frame of the same
            camera, samples and seed (medians over the frames of a moving sequence), and the share of pixels whose history is
-           invalidated per frame on that sequence.
+           invalidated per frame on that sequence; then, on the last frame, the blocking snapshots: the 8-bit picture of the mean, of
+           the guide-only filter (spt_progressive_temporal_display_snapshot with spt_denoise_params) and of the variance-guided filter
+           under the estimate (spt_progressive_temporal_display_var_snapshot), medians of N alternating calls.
 
 Prints a text report (and writes it to --out)."""
 import argparse
@@ -104,12 +109,39 @@ def main():
             none = name.startswith("no history")
             bytes_px = 4 * 12 + (0 if none else 48) + 48 + 12 + 4 + 4        # F, N, P, C | one history read | history written | mean, var, len
             lines.append(f"  {name:34s} {tm:8.1f} us  (min {min(t):.1f}, max {max(t):.1f})   {bytes_px} B/pixel at the least -> "
-                         f"{bytes_px * npix / tm * 1e-6:7.1f} GB/s")
+                         f"{bytes_px * npix / tm * 1e-6:7.1f} TB/s")
             lines.append(f"  {'  spt_accumulate_moments_device':34s} {ym:8.1f} us  (min {min(y):.1f}, max {max(y):.1f})   44 B/pixel -> "
-                         f"{44 * npix / ym * 1e-6:7.1f} GB/s")
+                         f"{44 * npix / ym * 1e-6:7.1f} TB/s")
         temporal(1, cams[1], cams[0], hist[0], hist[1])
         stream.synchronize()
         lines.append(f"  pixels without history after one move of {step}: {100 * float((length.cpu().numpy() == 1).mean()):.2f} %")
+        # the variance estimate: five frames at rest (len = 5 everywhere), then the move
+        temporal(0, cams[0], None, None, hist[0])
+        for k in range(4):
+            temporal(0, cams[0], cams[0], hist[k % 2], hist[(k + 1) % 2])
+        rest_hist = hist[0].clone()
+        temporal(1, cams[1], cams[0], hist[0], hist[1])
+        stream.synchronize()
+        moved_hist = hist[1]
+        young = 100 * float((length.cpu().numpy() < 4).mean())
+        vm = new(npix)
+        vp, vp_all = pkg.TemporalVarParams(), pkg.TemporalVarParams(min_len=1e9)
+        est = {"history at rest (no window staged)": lambda: r.temporal_variance_device(rest_hist, w, h, vm, None, vp, stream=sp),
+               f"after one move ({young:.2f} % below min_len)": lambda: r.temporal_variance_device(moved_hist, w, h, vm, None, vp, stream=sp),
+               "min_len out of reach (every window)": lambda: r.temporal_variance_device(moved_hist, w, h, vm, None, vp_all, stream=sp)}
+        lines.append(f"variance estimate (spt_temporal_variance_device), HIP events, median of {a.reps} after {a.warmup} warm-up calls:")
+        for name, fn in est.items():
+            for _ in range(a.warmup):
+                fn()
+                moments()
+            stream.synchronize()
+            t, y = [], []
+            for _ in range(a.reps):
+                t.append(timed(fn))
+                y.append(timed(moments))
+            tm, ym = statistics.median(t), statistics.median(y)
+            lines.append(f"  {name:44s} {tm:8.1f} us  (min {min(t):.1f}, max {max(t):.1f})   52 B/pixel at the least -> {52 * npix / tm * 1e-6:7.1f} TB/s"
+                         f"   yardstick {ym:.1f} us")
         # the loop against the two loops it stands beside
         r.progressive_begin(w, h, aov_kinds=KINDS)
         r.progressive_temporal_begin(p)
@@ -126,11 +158,24 @@ def main():
                 t_temporal.append((t1 - t0) * 1e3)
                 t_plain.append((t2 - t1) * 1e3)
                 lost.append(float((r.progressive_temporal_snapshot(length=True)[1] == 1).mean()))
+        snaps = {"mean (no filter)": lambda: r.progressive_temporal_display_snapshot(),
+                 "guide-only filter, spt_denoise_params": lambda: r.progressive_temporal_display_snapshot(denoise=True),
+                 "variance-guided filter under the estimate": lambda: r.progressive_temporal_display_var_snapshot()}
+        t_snap = {k: [] for k in snaps}
+        for i in range(a.warmup + a.reps):
+            for k, fn in snaps.items():
+                t0 = time.perf_counter()
+                fn()
+                if i >= a.warmup:
+                    t_snap[k].append((time.perf_counter() - t0) * 1e3)
         r.progressive_end()
         lines.append(f"loop, host wall time per frame, median of {len(t_temporal)} frames of a moving camera:")
         lines.append(f"  spt_progressive_temporal_frame                         {statistics.median(t_temporal):7.3f} ms  (min {min(t_temporal):.3f}, max {max(t_temporal):.3f})")
         lines.append(f"  spt_progressive_frame + spt_progressive_aov_frame      {statistics.median(t_plain):7.3f} ms  (min {min(t_plain):.3f}, max {max(t_plain):.3f})")
         lines.append(f"  pixels whose history is invalidated per frame: mean {100 * float(np.mean(lost)):.2f} %, max {100 * max(lost):.2f} %")
+        lines.append(f"display snapshots of the temporal loop (blocking, 5 levels), host wall time, median of {a.reps} alternating calls:")
+        for k, t in t_snap.items():
+            lines.append(f"  {k:54s} {statistics.median(t):7.3f} ms  (min {min(t):.3f}, max {max(t):.3f})")
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if a.out:
