@@ -393,7 +393,10 @@ int  spt_render_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uin
  *                     for meshes;
  *     SPT_AOV_ALBEDO  the material colour of hit.instId (:175);
  *     SPT_AOV_UV      (hit.uv.x, hit.uv.y, 0) (:182): (0, 0, 0) for spheres;
- *     SPT_AOV_DIST    (dist, dist, dist).
+ *     SPT_AOV_DIST    (dist, dist, dist);
+ *     SPT_AOV_EMISSION  the emission of hit.instId's material, everything else as SPT_AOV_ALBEDO: what spt_demodulate* takes off a
+ *                     pixel that sees a light.  A single kind only: the set entry points below do not know it (bit 1u << 6 of their
+ *                     masks stays reserved for it), and kinds 4 and 5 stay unknown here.
  *   Accumulation: the D9 order of spt_render bit for bit (float32, samples ascending within a block, blocks of a cell in order, pixel =
  *     ((c0 + c1) + c2) + c3); SPT_FLAG_NORMALISE multiplies by 1.f / spp.  Stats: samples = rows * w * spp, bounces = samples,
  *     max_depth_kills = 0.
@@ -404,6 +407,7 @@ int  spt_render_rows_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uin
  *   into 1e-3 of colour, so it cannot be bit-exact --; the multi-GPU front.  Several buffers of the same samples from one launch, and the
  *   progressive loop over them: spt_render_aov_set* and spt_progressive_aov_* below. */
 enum { SPT_AOV_NORMAL = 0, SPT_AOV_ALBEDO = 1, SPT_AOV_UV = 2, SPT_AOV_DIST = 3 };
+#define SPT_AOV_EMISSION 6u
 /* Full w x h buffer to out_rgb (host, w*h*3 floats, row 0 = bottom).  Blocking. */
 int  spt_render_aov(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps_per_cell, uint64_t seed,
                     uint32_t aov, uint32_t flags, float* out_rgb, spt_stats* stats);
@@ -534,7 +538,8 @@ int  spt_progressive_aov_snapshot(spt_ctx* ctx, uint32_t kind_bit, float* out_rg
  *   Scratch (the packed guides and two colour images, 80 bytes per pixel) belongs to the context, is grown on demand and freed by
  *     spt_destroy and spt_progressive_end; a failed allocation fails the call and leaves the context usable.  Calls of one context run
  *     one after another, whatever their streams (they share the scratch).  A call changes no render state.
- *   Out of scope: albedo demodulation; the multi-GPU front; the async lanes (they stay radiance-only). */
+ *   Albedo demodulation around the filter: spt_demodulate* / spt_remodulate* below (the filters are linear in the colour, so they take
+ *   the illumination as their `beauty`).  Out of scope: the multi-GPU front; the async lanes (they stay radiance-only). */
 typedef struct spt_denoise_params {
     uint32_t levels;      /* 1..5 passes; pass i uses step 2^i pixels */
     float sigma_normal, sigma_plane, sigma_albedo, sigma_coverage;  /* each finite and >= 0 */
@@ -880,6 +885,71 @@ int  spt_progressive_temporal_denoised_var_snapshot(spt_ctx* ctx, const spt_temp
 int  spt_progressive_temporal_display_var_snapshot(spt_ctx* ctx, const spt_temporal_var_params* var_params,
                                                    const spt_denoise_var_params* denoise_params, const spt_display_params* display_params,
                                                    uint8_t* out8);
+
+/* Albedo demodulation around the filters (csrc/spt_demod.hip): SVGF filters ILLUMINATION -- colour with the directly seen emission and
+ * the escaped share removed, divided by the first-hit albedo -- and multiplies the albedo back afterwards, so that a filter neither
+ * stops at a material seam nor bleeds one material's colour into the next.
+ *
+ *   Images: w*h packed float3, row 0 at the bottom.  `beauty` is the un-normalised sum over beauty_samples samples per pixel; `albedo`,
+ *     `coverage` and `emission` are the un-normalised sums over aov_samples as spt_render_aov* / spt_render_aov_set* write them
+ *     (SPT_AOV_ALBEDO, SPT_AOVSET_COVERAGE, SPT_AOV_EMISSION; emission NULL = the scene shows no light).  `illum` and `out_rgb` are MEANS:
+ *     the filters take `illum` as their `beauty` (they are linear in the colour), spt_display* takes `out_rgb` with weight 1.
+ *   Arithmetic: float32, one rounding per operation, no contraction, correctly rounded division.  Restated bit for bit by
+ *     tests/demod_expected.py (numpy) and tests/test_gpu_demod.py.
+ *       host, once:   wb = 1.0f / (float)beauty_samples;   wg = 1.0f / (float)aov_samples
+ *       per pixel:    k = C[0] * wg;   t = 1.0f - k
+ *       per channel:  a = A_j * wg;    e = E ? E_j * wg : 0.0f;    u = e + background_j * t
+ *       demodulate:   m = B_j * wb;    d = m - u;    illum_j = a > albedo_floor ? d / a : d
+ *       remodulate:   out_j = u + (a > albedo_floor ? a * f_j : f_j)                           (f = the filtered illumination)
+ *     a is the mean albedo over ALL samples (misses count as 0): the factor sum(a_i L_i) / N carries.  u is the unmodulated part: the
+ *     seen emission and the escaped share of `background`, the environment radiance (pass spt_get_environment's value).  Nothing is
+ *     clamped: tiny negatives pass through.  A channel at or below the floor (the compare is strict) passes through in colour units --
+ *     light sources of colour 0 and pixels without hits do.
+ *   Aliasing and alignment: the kernels are elementwise; d_out_illum may equal d_beauty and d_out_rgb may equal d_illum (exactly, not
+ *     shifted); every other overlap of an output with an input is refused.  Pointers need 4-byte alignment only (host buffers none: they
+ *     are staged through the context's scratch as spt_temporal_variance does, blocking).  The device forms are asynchronous on hip_stream
+ *     (NULL = the context's); they use no scratch and no state of the context, so calls are ordered by their streams alone.
+ *   Parameters: albedo_floor and background >= 0 and finite.  Defaults (spt_demod_params_default): albedo_floor = 1/64, background = 0.
+ *   Failures (message in spt_last_error, nothing launched, nothing written): a required pointer that is NULL; w or h of 0, or w*h above
+ *     2^31 - 1; a sample count of 0; a floor or background that is negative or not finite; a device pointer that is not 4-byte aligned; a
+ *     forbidden overlap.
+ *   Known limits: the first hit stands for the path -- mirror and glass pixels have albedo .999 and are effectively not demodulated --;
+ *     a channel at or below the floor is filtered in colour units.
+ *   The temporal loop over illumination: spt_progressive_temporal_demodulate(ctx, params) after spt_progressive_temporal_begin (which
+ *     leaves the mode off); params = NULL switches it off again.  The call may be made at any time; either way it drops the history (it
+ *     holds moments of the other quantity), so the next frame runs with "no history" and the snapshots fail until that frame is made.
+ *     With the mode on, spt_progressive_temporal_frame adds after its two launches: a SPT_AOV_EMISSION launch with the same camera, samps
+ *     and seed into a buffer of the loop; spt_demodulate of the frame in place with beauty_samples = aov_samples = 4 * samps; and runs
+ *     the temporal step with frame_samples = 1.  The history, its m2, out_var and out_len are then those of the illumination.  Every
+ *     snapshot ends with spt_remodulate under the last frame's albedo, coverage and emission sums, into scratch of the loop, never into
+ *     the history: spt_progressive_temporal_snapshot's out_rgb is the remodulated mean (out_var, out_len: the illumination's);
+ *     _display_snapshot is (filter ->) remodulate -> display; _denoised_var_snapshot and _display_var_snapshot are variance estimate ->
+ *     filter -> remodulate (-> display).  The radiance accumulator, its M2 and n, the feature accumulators and the chunk-order records
+ *     stay untouched, as without the mode; stats are the radiance launch's.  The mode adds 24 bytes per pixel, allocated when it is first
+ *     enabled and freed by spt_progressive_end, the next begin and spt_destroy; a failed allocation fails the call and leaves the loop
+ *     usable with the mode off.  Fails before spt_progressive_temporal_begin and for parameters spt_demodulate refuses.
+ *     Out of scope: the plain progressive loop and its M2 (moments of colour); the async lanes; the multi-GPU front. */
+typedef struct spt_demod_params {
+    float albedo_floor;   /* >= 0: a channel whose mean albedo is not above it passes through undivided */
+    float background[3];  /* >= 0: the environment radiance of escaped paths */
+} spt_demod_params;
+#if defined(__cplusplus)
+static_assert(sizeof(spt_demod_params) == 16, "spt_demod_params: 16 bytes");
+#else
+_Static_assert(sizeof(spt_demod_params) == 16, "spt_demod_params: 16 bytes");
+#endif
+/* Host-only: albedo_floor = 1/64 (0.015625f, exact in binary), background = (0, 0, 0). */
+void spt_demod_params_default(spt_demod_params* params);
+int  spt_demodulate_device(spt_ctx* ctx, const void* d_beauty, const void* d_albedo, const void* d_coverage, const void* d_emission,
+                           uint32_t w, uint32_t h, uint32_t beauty_samples, uint32_t aov_samples, const spt_demod_params* params,
+                           void* d_out_illum, void* hip_stream);
+int  spt_remodulate_device(spt_ctx* ctx, const void* d_illum, const void* d_albedo, const void* d_coverage, const void* d_emission,
+                           uint32_t w, uint32_t h, uint32_t aov_samples, const spt_demod_params* params, void* d_out_rgb, void* hip_stream);
+int  spt_demodulate(spt_ctx* ctx, const float* beauty, const float* albedo, const float* coverage, const float* emission, uint32_t w,
+                    uint32_t h, uint32_t beauty_samples, uint32_t aov_samples, const spt_demod_params* params, float* out_illum);
+int  spt_remodulate(spt_ctx* ctx, const float* illum, const float* albedo, const float* coverage, const float* emission, uint32_t w,
+                    uint32_t h, uint32_t aov_samples, const spt_demod_params* params, float* out_rgb);
+int  spt_progressive_temporal_demodulate(spt_ctx* ctx, const spt_demod_params* params);
 
 #ifdef __cplusplus
 }

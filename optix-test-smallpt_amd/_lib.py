@@ -58,7 +58,11 @@ class SptTemporalVarParams(C.Structure):  # spt_temporal_var_params: 12 bytes
     _fields_ = [("min_len", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
 
 
-class SptInstance(C.Structure):      # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
+class SptDemodParams(C.Structure):  # spt_demod_params: 16 bytes
+    _fields_ = [("albedo_floor", C.c_float), ("background", C.c_float * 3)]
+
+
+class SptInstance(C.Structure):     # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
     _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
 
 
@@ -159,6 +163,12 @@ SYMBOLS = {
     "spt_progressive_temporal_denoised_var_snapshot": (C.c_int, [_P, C.POINTER(SptTemporalVarParams), C.POINTER(SptDenoiseVarParams), _P, _P]),
     "spt_progressive_temporal_display_var_snapshot": (C.c_int, [_P, C.POINTER(SptTemporalVarParams), C.POINTER(SptDenoiseVarParams),
                                                                 C.POINTER(SptDisplayParams), _P]),
+    "spt_demod_params_default": (None, [C.POINTER(SptDemodParams)]),
+    "spt_demodulate_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDemodParams), _P, _P]),
+    "spt_remodulate_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDemodParams), _P, _P]),
+    "spt_demodulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDemodParams), _P]),
+    "spt_remodulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDemodParams), _P]),
+    "spt_progressive_temporal_demodulate": (C.c_int, [_P, C.POINTER(SptDemodParams)]),
 }
 
 # test / tuning hooks declared in csrc/spt_internal.h (not part of the drop-in boundary)

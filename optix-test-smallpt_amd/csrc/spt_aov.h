@@ -140,7 +140,8 @@ __device__ __forceinline__ void aov_store(float4* cells, uint32_t task, uint32_t
 
 // Launchers (spt_grid.hip, spt_mesh.hip).  K: camera, band, D9 layout, seed hashes, sphere table (geom / mat / n), cells; the task queue
 // and counters are not used.  kind: SPT_AOV_* (0 .. 3) writes K.cells[0 .. K.ntasks); spt_aov_set | mask (a SPT_AOVSET_* mask, not 0) writes
-// popcount(mask) planes of K.ntasks cells each.  Nothing else is written.
+// popcount(mask) planes of K.ntasks cells each.  Nothing else is written.  SPT_AOV_EMISSION never reaches a kernel: spt_api.cpp launches
+// ALBEDO with K.mat / M.mats one row earlier, so that "row 3 i + 1" is material i's emission.
 namespace spt { struct MParams; struct GridParams; }
 constexpr uint32_t spt_aov_set = 0x80000000u;
 extern "C" hipError_t spt_aov_exhaustive_launch(const spt::KParams* K, uint32_t kind, int guard_all, hipStream_t stream);

@@ -16,6 +16,8 @@
 #include "spt_temporal_host.h"
 #include "spt_temporal_var.h"
 #include "spt_temporal_var_host.h"
+#include "spt_demod.h"
+#include "spt_demod_host.h"
 #include "spt_devbuf.h"
 
 #include <chrono>
@@ -103,12 +105,15 @@ struct DenoiseScratch {
 // spt_progressive_temporal_*: the parameters of the begin, two histories (hist[cur] holds the last frame's), the loop's own radiance
 // frame, its NORMAL / ALBEDO / POSITION / COVERAGE frames (one allocation), the {mean rgb | var | len} image of the last frame, that
 // frame's camera and 4 * samps, and whether hist[cur] is a history yet; var = the w*h floats of the variance estimate the *_var_snapshot
-// entries filter under (spt_temporal_var.hip), grown by their first call
+// entries filter under (spt_temporal_var.hip), grown by their first call.  demod (spt_progressive_temporal_demodulate): the loop runs over
+// illumination; dm = {the last frame's EMISSION sums | the remodulated picture of a snapshot}, two padded images, allocated when the mode
+// is first enabled
 struct Temporal {
     bool on = false; spt_temporal_params params{};
     DevBuf<float4> hist[2]; int cur = 0; bool have = false;
     DevBuf<float> frame, guides, out, var;
     spt_camera cam{}; uint32_t samples = 0;
+    bool demod = false; spt_demod_params dparams{}; DevBuf<float> dm;
 };
 
 struct spt_ctx {
@@ -1997,7 +2002,7 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
     if (set) {
         if (aov == 0 || aov > SPT_AOVSET_ALL) return c->fail("%s: bad mask 0x%x (one or more of SPT_AOVSET_NORMAL .. SPT_AOVSET_COVERAGE)", who, aov);
         nplanes = (uint32_t)__builtin_popcount(aov);
-    } else if (aov > SPT_AOV_DIST) return c->fail("%s: unknown aov %u (SPT_AOV_NORMAL, _ALBEDO, _UV or _DIST)", who, aov);
+    } else if (aov > SPT_AOV_DIST && aov != SPT_AOV_EMISSION) return c->fail("%s: unknown aov %u (SPT_AOV_NORMAL, _ALBEDO, _UV, _DIST or _EMISSION)", who, aov);
     for (uint32_t j = 0; j < nplanes; ++j) if (!d_out[j]) return c->fail("%s: NULL argument", who);
     if (!c->d_geom && !c->mesh_scene) return c->fail("%s: no scene set (call spt_set_scene or spt_set_meshes)", who);
     if (w == 0 || h == 0 || samps == 0) return c->fail("%s: empty image or samps == 0", who);
@@ -2039,6 +2044,14 @@ static int render_aov_impl(spt_ctx* c, const char* who, const spt_camera* cam, u
         return c->fail("%s: %u spheres > SPT_MAX_SPHERES (%u) and no structure over them", who, c->n, SPT_MAX_SPHERES);
     }
     if (path != 1) blocks = (uint32_t)((qend + 255u) / 256u);
+    if (aov == SPT_AOV_EMISSION) {
+        // EMISSION is the ALBEDO launch over a material table that begins one row earlier: a material is the three rows {emission, colour,
+        // colour / pmax} and the AOV kernels read nothing of it but row 3 i + 1, which is then material i's emission.  The kernels stay
+        // as they are (spt_aov.h: they have no register to spare for a choice of the row); the pointers are only ever indexed from 1 up.
+        aov = SPT_AOV_ALBEDO;
+        if (P.mat) P.mat -= 1;
+        if (M.mats) M.mats -= 1;
+    }
     SPT_HIP(c, hipEventRecord(c->ev_start, st));
     if (path == 0) SPT_HIP(c, spt_aov_exhaustive_launch(&P, aov, c->needs_guard ? 1 : 0, st));
     else if (path == 1) SPT_HIP(c, spt_aov_grid_launch(&P, &c->grid, c->d_grid_cells, c->d_grid_refs, c->d_grid_always, c->grid_global, aov, blocks, st));
@@ -2877,10 +2890,18 @@ int spt_progressive_temporal_frame(spt_ctx* c, const spt_camera* cam, uint32_t s
     void* const guides[4] = {g, g + pitch, g + 2 * pitch, g + 3 * pitch};       // NORMAL, ALBEDO, POSITION, COVERAGE: ascending bit order
     const uint32_t mask = SPT_AOVSET_NORMAL | SPT_AOVSET_ALBEDO | SPT_AOVSET_POSITION | SPT_AOVSET_COVERAGE;
     if (int rc = render_aov_impl(c, who, cam, w, h, 0, h, samps, seed, true, mask, 0u, guides, nullptr)) return rc;
+    if (c->tp.demod) {
+        // the loop over illumination: the same samples' first-hit emission, then the frame becomes the MEAN illumination in place
+        void* const emission = c->tp.dm;
+        if (int rc = render_aov_impl(c, who, cam, w, h, 0, h, samps, seed, false, SPT_AOV_EMISSION, 0u, &emission, nullptr)) return rc;
+        const float wgt = 1.0f / (float)(4u * samps);
+        SPT_HIP(c, spt_demod_launch(0, c->tp.frame, g + pitch, g + 3 * pitch, c->tp.dm, w, h, wgt, wgt, c->tp.dparams.albedo_floor, c->tp.dparams.background,
+                                    c->tp.frame, c->stream));
+    }
     const bool have = c->tp.have && !reset;
     const int next = c->tp.cur ^ 1;
     const spt::TemporalCall k{c->tp.frame, g, g + 2 * pitch, g + 3 * pitch, have ? c->tp.hist[c->tp.cur] : nullptr, c->tp.hist[next], c->tp.out,
-                              c->tp.out + pitch, c->tp.out + pitch + plane, w, h, 4u * samps, cam, have ? &c->tp.cam : nullptr, &c->tp.params, true};
+                              c->tp.out + pitch, c->tp.out + pitch + plane, w, h, c->tp.demod ? 1u : 4u * samps, cam, have ? &c->tp.cam : nullptr, &c->tp.params, true};
     const int rc = temporal_enqueue(c, who, k, c->stream);
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     if (int src = spt_sync(c, nullptr)) return src;                             // the feature launch's completion
@@ -2889,6 +2910,42 @@ int spt_progressive_temporal_frame(spt_ctx* c, const spt_camera* cam, uint32_t s
     c->tp.have = true;
     c->tp.cam = *cam;
     c->tp.samples = 4u * samps;
+    return 0;
+}
+
+// The loop over illumination (spt_progressive_temporal_demodulate).  params == NULL switches the mode off.  Either way the history is
+// dropped: it holds moments of the other quantity.
+int spt_progressive_temporal_demodulate(spt_ctx* c, const spt_demod_params* p)
+{
+    if (!c) return 1;
+    const char* const who = "spt_progressive_temporal_demodulate";
+    if (!c->tp.on) return c->fail("%s: call spt_progressive_temporal_begin first", who);
+    if (p) {
+        char msg[256];
+        if (spt::demod_params_check(p, who, msg, sizeof msg)) return c->fail("%s", msg);
+        if (!c->tp.dm) {
+            SPT_HIP(c, hipSetDevice(c->device));
+            const hipError_t e = c->tp.dm.grow(2 * temporal_pitch(c));
+            if (e != hipSuccess) { (void)hipGetLastError(); return c->fail("%s: %s", who, hipGetErrorString(e)); }   // (the mode stays as it was: off)
+        }
+        c->tp.dparams = *p;
+    }
+    c->tp.demod = p != nullptr;
+    c->tp.have = false;
+    return 0;
+}
+
+// With the mode on, every snapshot ends here: *src (the loop's mean illumination, or a filter's result) times the last frame's albedo plus
+// its unmodulated part, into the loop's scratch -- never into the history --, enqueued on the context's stream; *src then names the picture.
+static int temporal_remodulate(spt_ctx* c, const float** src)
+{
+    if (!c->tp.demod) return 0;
+    const size_t pitch = temporal_pitch(c);
+    const float* const g = c->tp.guides;
+    float* const out = c->tp.dm + pitch;
+    SPT_HIP(c, spt_demod_launch(1, *src, g + pitch, g + 3 * pitch, c->tp.dm, c->prog_w, c->prog_h, 1.0f, 1.0f / (float)c->tp.samples, c->tp.dparams.albedo_floor,
+                                c->tp.dparams.background, out, c->stream));
+    *src = out;
     return 0;
 }
 
@@ -2901,7 +2958,9 @@ int spt_progressive_temporal_snapshot(spt_ctx* c, float* out_rgb, float* out_var
     if (!c->tp.have) return c->fail("%s: no spt_progressive_temporal_frame has been made since the begin", who);
     SPT_HIP(c, hipSetDevice(c->device));
     const size_t npix = (size_t)c->prog_w * c->prog_h, pitch = temporal_pitch(c), plane = temporal_plane(c);
-    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->tp.out, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    const float* rgb = c->tp.out;
+    if (int rc = temporal_remodulate(c, &rgb)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, rgb, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (out_var) SPT_HIP(c, hipMemcpyAsync(out_var, c->tp.out + pitch, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (out_len) SPT_HIP(c, hipMemcpyAsync(out_len, c->tp.out + pitch + plane, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
@@ -2931,6 +2990,7 @@ int spt_progressive_temporal_display_snapshot(spt_ctx* c, const spt_denoise_para
         if (int rc = denoise_enqueue(c, who, c->tp.out, g, g + pitch, g + 2 * pitch, g + 3 * pitch, c->prog_w, c->prog_h, c->tp.samples, dp, c->dn.out, c->stream)) return rc;
         src = c->dn.out;
     }
+    if (int rc = temporal_remodulate(c, &src)) return rc;
     return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);
 }
 
@@ -3017,7 +3077,9 @@ int spt_progressive_temporal_denoised_var_snapshot(spt_ctx* c, const spt_tempora
     SPT_HIP(c, hipSetDevice(c->device));
     if (int rc = temporal_denoised_var_enqueue(c, who, vp, &four, dp->sigma_colour)) return rc;
     const size_t npix = (size_t)c->prog_w * c->prog_h;
-    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->dn.out, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    const float* rgb = c->dn.out;
+    if (int rc = temporal_remodulate(c, &rgb)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, rgb, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (out_var_mean) SPT_HIP(c, hipMemcpyAsync(out_var_mean, c->tp.var, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -3034,7 +3096,82 @@ int spt_progressive_temporal_display_var_snapshot(spt_ctx* c, const spt_temporal
     SPT_HIP(c, hipSetDevice(c->device));
     if (int rc = display_table(c, who)) return rc;
     if (int rc = temporal_denoised_var_enqueue(c, who, vp, &four, dp->sigma_colour)) return rc;
-    return display_to_host(c, who, c->dn.out, c->prog_w, c->prog_h, p, out8);
+    const float* src = c->dn.out;
+    if (int rc = temporal_remodulate(c, &src)) return rc;
+    return display_to_host(c, who, src, c->prog_w, c->prog_h, p, out8);
+}
+
+// ---- albedo demodulation around the filters (spt_demod.hip; the contract is stated in include/smallpt_mi355x.h) ----
+void spt_demod_params_default(spt_demod_params* p)
+{
+    if (!p) return;
+    p->albedo_floor = 1.0f / 64.0f;
+    p->background[0] = p->background[1] = p->background[2] = 0.0f;
+}
+
+// remod = false: colour is the beauty sum (beauty_samples > 0); true: the illumination (beauty_samples is passed as 1 and not used)
+static int demod_device(spt_ctx* c, const char* who, bool remod, const void* d_colour, const void* d_albedo, const void* d_coverage, const void* d_emission,
+                        uint32_t w, uint32_t h, uint32_t beauty_samples, uint32_t aov_samples, const spt_demod_params* p, void* d_out, void* hip_stream)
+{
+    const spt::DemodCall k{d_colour, d_albedo, d_coverage, d_emission, d_out, w, h, beauty_samples, aov_samples, p, true};
+    char msg[256];
+    if (spt::demod_validate(k, who, msg, sizeof msg)) return c->fail("%s", msg);
+    SPT_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    SPT_HIP(c, spt_demod_launch(remod ? 1 : 0, static_cast<const float*>(d_colour), static_cast<const float*>(d_albedo), static_cast<const float*>(d_coverage),
+                                static_cast<const float*>(d_emission), w, h, 1.0f / (float)beauty_samples, 1.0f / (float)aov_samples, p->albedo_floor,
+                                p->background, static_cast<float*>(d_out), st));
+    return 0;
+}
+
+static int demod_host(spt_ctx* c, const char* who, bool remod, const float* colour, const float* albedo, const float* coverage, const float* emission,
+                      uint32_t w, uint32_t h, uint32_t beauty_samples, uint32_t aov_samples, const spt_demod_params* p, float* out)
+{
+    const spt::DemodCall k{colour, albedo, coverage, emission, out, w, h, beauty_samples, aov_samples, p, false};
+    char msg[256];
+    if (spt::demod_validate(k, who, msg, sizeof msg)) return c->fail("%s", msg);
+    SPT_HIP(c, hipSetDevice(c->device));
+    // staging, in floats, every image 16-byte aligned: colour (the kernel runs in place over it) | albedo | coverage | emission
+    const size_t nfl = (size_t)w * h * 3, pitch = (nfl + 3) & ~(size_t)3;
+    if (grow_out(c, pitch * (emission ? 4 : 3))) return 1;
+    float* const d = c->d_out;
+    SPT_HIP(c, hipMemcpyAsync(d, colour, nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(d + pitch, albedo, nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(d + 2 * pitch, coverage, nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (emission) SPT_HIP(c, hipMemcpyAsync(d + 3 * pitch, emission, nfl * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, spt_demod_launch(remod ? 1 : 0, d, d + pitch, d + 2 * pitch, emission ? d + 3 * pitch : nullptr, w, h, 1.0f / (float)beauty_samples,
+                                1.0f / (float)aov_samples, p->albedo_floor, p->background, d, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(out, d, nfl * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int spt_demodulate_device(spt_ctx* c, const void* d_beauty, const void* d_albedo, const void* d_coverage, const void* d_emission, uint32_t w, uint32_t h,
+                          uint32_t beauty_samples, uint32_t aov_samples, const spt_demod_params* p, void* d_out_illum, void* hip_stream)
+{
+    if (!c) return 1;
+    return demod_device(c, "spt_demodulate_device", false, d_beauty, d_albedo, d_coverage, d_emission, w, h, beauty_samples, aov_samples, p, d_out_illum, hip_stream);
+}
+
+int spt_remodulate_device(spt_ctx* c, const void* d_illum, const void* d_albedo, const void* d_coverage, const void* d_emission, uint32_t w, uint32_t h,
+                          uint32_t aov_samples, const spt_demod_params* p, void* d_out_rgb, void* hip_stream)
+{
+    if (!c) return 1;
+    return demod_device(c, "spt_remodulate_device", true, d_illum, d_albedo, d_coverage, d_emission, w, h, 1u, aov_samples, p, d_out_rgb, hip_stream);
+}
+
+int spt_demodulate(spt_ctx* c, const float* beauty, const float* albedo, const float* coverage, const float* emission, uint32_t w, uint32_t h,
+                   uint32_t beauty_samples, uint32_t aov_samples, const spt_demod_params* p, float* out_illum)
+{
+    if (!c) return 1;
+    return demod_host(c, "spt_demodulate", false, beauty, albedo, coverage, emission, w, h, beauty_samples, aov_samples, p, out_illum);
+}
+
+int spt_remodulate(spt_ctx* c, const float* illum, const float* albedo, const float* coverage, const float* emission, uint32_t w, uint32_t h,
+                   uint32_t aov_samples, const spt_demod_params* p, float* out_rgb)
+{
+    if (!c) return 1;
+    return demod_host(c, "spt_remodulate", true, illum, albedo, coverage, emission, w, h, 1u, aov_samples, p, out_rgb);
 }
 
 // Test / measurement hook (spt_internal.h)

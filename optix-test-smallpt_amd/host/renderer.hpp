@@ -46,7 +46,7 @@ public:
         return out;
     }
 
-    // First-hit feature buffer (spt_render_aov; SPT_AOV_NORMAL / _ALBEDO / _UV / _DIST): the closest hit of every camera sample of render()
+    // First-hit feature buffer (spt_render_aov; SPT_AOV_NORMAL / _ALBEDO / _UV / _DIST / _EMISSION): the closest hit of every camera sample of render()
     // with the same arguments, folded in its order -- with SPT_AOV_NORMAL the image shadePaths draws as shipped (smallpt.cpp:179-183).
     std::vector<float3> renderAov(const spt_camera& camera, size_t imageWidth, size_t imageHeight, size_t sampleCountPerJitterCell,
                                   size_t seed, uint32_t aov, bool normalise = false)
@@ -256,6 +256,61 @@ public:
                                 void* dOutVar = nullptr, void* hipStream = nullptr)
     {
         check(spt_temporal_variance_device(ctx_, dHist, (uint32_t)imageWidth, (uint32_t)imageHeight, &params, dOutVarMean, dOutVar, hipStream));
+    }
+    // Albedo demodulation around the filters (spt_demodulate / spt_remodulate): beauty, albedo, coverage and emission (or empty: no light in
+    // view) as UN-NORMALISED sums -- render(), renderAovSet(... SPT_AOVSET_ALBEDO | _COVERAGE) and renderAov(... SPT_AOV_EMISSION) --; the
+    // illumination and the remodulated colour are MEANS.  params = nullptr: spt_demod_params_default (pass the environment as background).
+    std::vector<float3> demodulate(const std::vector<float3>& beauty, const std::vector<float3>& albedo, const std::vector<float3>& coverage,
+                                   const std::vector<float3>& emission, size_t imageWidth, size_t imageHeight, size_t beautySamples, size_t aovSamples,
+                                   const spt_demod_params* params = nullptr)
+    {
+        const size_t n = imageWidth * imageHeight;
+        if (beauty.size() != n || albedo.size() != n || coverage.size() != n || (!emission.empty() && emission.size() != n))
+            throw std::runtime_error("demodulate: images of imageWidth * imageHeight pixels (the emission may be empty)");
+        spt_demod_params p;
+        if (params) p = *params; else spt_demod_params_default(&p);
+        std::vector<float3> out(n);
+        auto f = [](const std::vector<float3>& v) { return v.empty() ? nullptr : reinterpret_cast<const float*>(v.data()); };
+        check(spt_demodulate(ctx_, f(beauty), f(albedo), f(coverage), f(emission), (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)beautySamples,
+                             (uint32_t)aovSamples, &p, reinterpret_cast<float*>(out.data())));
+        return out;
+    }
+    std::vector<float3> remodulate(const std::vector<float3>& illumination, const std::vector<float3>& albedo, const std::vector<float3>& coverage,
+                                   const std::vector<float3>& emission, size_t imageWidth, size_t imageHeight, size_t aovSamples,
+                                   const spt_demod_params* params = nullptr)
+    {
+        const size_t n = imageWidth * imageHeight;
+        if (illumination.size() != n || albedo.size() != n || coverage.size() != n || (!emission.empty() && emission.size() != n))
+            throw std::runtime_error("remodulate: images of imageWidth * imageHeight pixels (the emission may be empty)");
+        spt_demod_params p;
+        if (params) p = *params; else spt_demod_params_default(&p);
+        std::vector<float3> out(n);
+        auto f = [](const std::vector<float3>& v) { return v.empty() ? nullptr : reinterpret_cast<const float*>(v.data()); };
+        check(spt_remodulate(ctx_, f(illumination), f(albedo), f(coverage), f(emission), (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)aovSamples, &p,
+                             reinterpret_cast<float*>(out.data())));
+        return out;
+    }
+    void demodulateDevice(const void* dBeauty, const void* dAlbedo, const void* dCoverage, const void* dEmission, size_t imageWidth, size_t imageHeight,
+                          size_t beautySamples, size_t aovSamples, const spt_demod_params& params, void* dOutIllum, void* hipStream = nullptr)
+    {
+        check(spt_demodulate_device(ctx_, dBeauty, dAlbedo, dCoverage, dEmission, (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)beautySamples,
+                                    (uint32_t)aovSamples, &params, dOutIllum, hipStream));
+    }
+    void remodulateDevice(const void* dIllum, const void* dAlbedo, const void* dCoverage, const void* dEmission, size_t imageWidth, size_t imageHeight,
+                          size_t aovSamples, const spt_demod_params& params, void* dOutRgb, void* hipStream = nullptr)
+    {
+        check(spt_remodulate_device(ctx_, dIllum, dAlbedo, dCoverage, dEmission, (uint32_t)imageWidth, (uint32_t)imageHeight, (uint32_t)aovSamples, &params,
+                                    dOutRgb, hipStream));
+    }
+    // The temporal loop over illumination (spt_progressive_temporal_demodulate): on = false switches the mode off; either way the history
+    // is dropped.  params = nullptr: the defaults with the context's environment as background.
+    void progressiveTemporalDemodulate(bool on, const spt_demod_params* params = nullptr)
+    {
+        if (!on) { check(spt_progressive_temporal_demodulate(ctx_, nullptr)); return; }
+        spt_demod_params p;
+        if (params) p = *params;
+        else { spt_demod_params_default(&p); check(spt_get_environment(ctx_, p.background)); }
+        check(spt_progressive_temporal_demodulate(ctx_, &p));
     }
     void denoisePvarDevice(const void* dBeauty, const void* dNormal, const void* dAlbedo, const void* dPosition, const void* dCoverage, const void* dVariance,
                            size_t imageWidth, size_t imageHeight, size_t aovSamples, const spt_denoise_var_params& params, void* dOut, void* hipStream = nullptr)

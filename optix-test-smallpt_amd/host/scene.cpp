@@ -320,6 +320,7 @@ static bool request_flag(const std::string& text, const char* name, bool* value)
 bool parse_request_temporal(const std::string& text, bool* temporal) { return request_flag(text, "temporal", temporal); }
 
 bool parse_request_temporal_denoise(const std::string& text, bool* denoise) { return request_flag(text, "temporal_denoise", denoise); }
+bool parse_request_temporal_demodulate(const std::string& text, bool* demodulate) { return request_flag(text, "temporal_demodulate", demodulate); }
 
 Scene load_scene_file(const std::string& path)
 {

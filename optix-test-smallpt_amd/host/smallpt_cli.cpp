@@ -86,14 +86,16 @@ int main(int argc, char* argv[])
         else if (a == "--parse-request") {   // host-only: one message of the viewer's request queue through the JSON reader
             try {
                 float3 o3;
-                bool temporal = false, denoise = false;
+                bool temporal = false, denoise = false, demodulate = false;
                 const std::string msg = next();
                 const bool has_temporal = parse_request_temporal(msg, &temporal);
                 const bool has_denoise = parse_request_temporal_denoise(msg, &denoise);
+                const bool has_demodulate = parse_request_temporal_demodulate(msg, &demodulate);
                 if (parse_update_camera_request(msg, &o3)) std::printf("update_camera %.9g %.9g %.9g", o3.x, o3.y, o3.z);
                 else std::printf("ignored");
                 if (has_temporal) std::printf(" temporal %s", temporal ? "on" : "off");     // the opt-in fields of the viewer's render thread
                 if (has_denoise) std::printf(" temporal_denoise %s", denoise ? "on" : "off");
+                if (has_demodulate) std::printf(" temporal_demodulate %s", demodulate ? "on" : "off");
                 std::printf("\n");
                 return 0;
             } catch (const std::exception& e) { std::fprintf(stderr, "error: %s\n", e.what()); return 1; }

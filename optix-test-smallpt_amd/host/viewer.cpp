@@ -88,6 +88,7 @@ void ProgressiveRenderer::postRequest(const std::string& json)
     (void)parseUpdateCamera(json, &ignored);         // malformed text is refused HERE, on the caller's thread, not in the render thread
     (void)parse_request_temporal(json, &ignoredFlag);
     (void)parse_request_temporal_denoise(json, &ignoredFlag);
+    (void)parse_request_temporal_demodulate(json, &ignoredFlag);
     std::unique_lock<std::mutex> l{requestsMutex_};  // :980
     requests_.emplace_back(json);
 }
@@ -103,7 +104,7 @@ void ProgressiveRenderer::moveCamera(float dy)
 void ProgressiveRenderer::stepOnce()
 {
     bool needClearBuffer = false;                    // :903
-    bool temporal = false, temporalGiven = false, denoise = false, denoiseGiven = false;
+    bool temporal = false, temporalGiven = false, denoise = false, denoiseGiven = false, demod = false, demodGiven = false;
     {
         std::unique_lock<std::mutex> l{requestsMutex_};   // :906
         for (const std::string& request : requests_) {    // :909
@@ -115,6 +116,7 @@ void ProgressiveRenderer::stepOnce()
             bool t;
             if (parse_request_temporal(request, &t)) { temporal = t; temporalGiven = true; }
             if (parse_request_temporal_denoise(request, &t)) { denoise = t; denoiseGiven = true; }
+            if (parse_request_temporal_demodulate(request, &t)) { demod = t; demodGiven = true; }
         }
         requests_.clear();                           // :918
     }
@@ -126,6 +128,7 @@ void ProgressiveRenderer::stepOnce()
     // :922 render + :927-937 accumulate, both on the device; the lock keeps a snapshot from reading a half-added frame
     std::unique_lock<std::mutex> l{accumMutex_};     // :925
     if (denoiseGiven) temporalDenoise_ = denoise;    // changes the snapshots only
+    if (demodGiven) temporalDemodulate_ = demod;     // reaches the loop below, before its next frame
     if (temporalGiven && temporal != temporal_) {
         for (size_t i = 0; i < lanes_.size(); ++i)   // the two loops take turns on this context: drain what is in flight
             if (inFlight_[i]) { inFlight_[i] = 0; lanes_[i]->progressiveWait(); }
@@ -136,6 +139,12 @@ void ProgressiveRenderer::stepOnce()
     if (temporal_) {
         // a camera change does NOT clear: the history is reprojected from the previous frame's camera (spt_progressive_temporal_frame)
         if (!temporalBegun_) { renderer_.progressiveTemporalBegin(); temporalBegun_ = true; }
+        if (temporalDemodulate_ != temporalDemodulateSet_) {
+            // the loop over illumination, background = the context's environment; the switch drops the history and the frame below starts
+            // the new one, under the lock, so no snapshot falls between the two
+            renderer_.progressiveTemporalDemodulate(temporalDemodulate_);
+            temporalDemodulateSet_ = temporalDemodulate_;
+        }
         renderer_.progressiveTemporalFrame(camera_.abi(), samps_, seed, temporalReset_);
         temporalReset_ = false;
         ++sampleCount_;
@@ -213,6 +222,12 @@ bool ProgressiveRenderer::temporal()
 {
     std::unique_lock<std::mutex> l{accumMutex_};
     return temporal_;
+}
+
+bool ProgressiveRenderer::temporalDemodulate()
+{
+    std::unique_lock<std::mutex> l{accumMutex_};
+    return temporalDemodulate_;
 }
 
 bool ProgressiveRenderer::temporalDenoise()

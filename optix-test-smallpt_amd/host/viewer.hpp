@@ -13,7 +13,9 @@
 //                                                                       then on a frame goes through spt_progressive_temporal_frame and a
 //                                                                       camera change keeps the reprojected history instead of clearing;
 //                                                                       "temporal_denoise": true (opt-in, default off) shows that loop's
-//                                                                       mean under the variance-guided filter, default parameters
+//                                                                       mean under the variance-guided filter, default parameters;
+//                                                                       "temporal_demodulate": true (opt-in, default off) runs that
+//                                                                       loop over illumination (spt_progressive_temporal_demodulate)
 //   exit: accumBuffer /= sampleCount*spp, flipY, writeImage (:995-1004)  finalImage()
 //
 // accumBuffer lives in HBM (spt_progressive_*); the mutex guards the frame counter and the request queue like the
@@ -77,8 +79,11 @@ public:
     // While it is on, snapshot() returns the loop's MEAN image with weight 1 and snapshotDisplay() its 8-bit form; extra lanes idle.
     // With the last "temporal_denoise" field on as well, both return that mean under the variance-guided filter
     // (spt_progressive_temporal_denoised_var_snapshot / _display_var_snapshot with the default parameters).
+    // With the last "temporal_demodulate" field on, the temporal loop accumulates illumination and every picture is remodulated
+    // (spt_progressive_temporal_demodulate with the default floor and the context's environment as background).
     bool temporal();
     bool temporalDenoise();
+    bool temporalDemodulate();
     size_t framesRendered() const { return framesRendered_; }
 
 private:
@@ -96,6 +101,7 @@ private:
     size_t sampleCount_ = 0;   // :893
     bool temporal_ = false, temporalBegun_ = false, temporalReset_ = true;   // guarded by accumMutex_
     bool temporalDenoise_ = false;                                           // guarded by accumMutex_
+    bool temporalDemodulate_ = false, temporalDemodulateSet_ = false;        // requested / what the loop runs with; guarded by accumMutex_
     std::atomic<size_t> framesRendered_{0};
     std::atomic<bool> renderDone_{false};      // the reference uses a plain float here (:894), a data race
     std::thread thread_;

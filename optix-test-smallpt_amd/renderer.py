@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SptCamera, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, SptTemporalParams, SptTemporalVarParams, load_library, load_multi_library
+from ._lib import SptCamera, SptDemodParams, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, SptTemporalParams, SptTemporalVarParams, load_library, load_multi_library
 from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
@@ -151,9 +151,15 @@ def _aov_set(kinds):
     return sum(1 << AOV_SET_KINDS[k] for k in names), names
 
 
+# SPT_AOV_EMISSION: a kind of the single-kind entries only (no set bit), so it is in neither table above
+AOV_EMISSION = 6
+
+
 def _aov_kind(aov):
+    if aov == "emission":
+        return AOV_EMISSION
     if not isinstance(aov, str) or aov not in AOV_KINDS:
-        raise ValueError(f"unknown aov {aov!r}: one of {', '.join(AOV_KINDS)}")
+        raise ValueError(f"unknown aov {aov!r}: one of {', '.join(AOV_KINDS)}, emission")
     return AOV_KINDS[aov]
 
 
@@ -305,6 +311,37 @@ class TemporalVarParams:
 
 def _temporal_var_params(params):
     return (params if params is not None else TemporalVarParams()).as_c()
+
+
+class DemodParams:
+    """Parameters of albedo demodulation (spt_demod_params): ``albedo_floor`` >= 0, the mean albedo at or below which a channel passes
+    through undivided, and ``background`` (one number or three, >= 0), the environment radiance of escaped paths -- pass
+    ``Renderer.environment()``.  Anything left None takes the library's default (spt_demod_params_default: 1/64 and 0)."""
+
+    def __init__(self, albedo_floor=None, background=None):
+        c = SptDemodParams()
+        load_library().spt_demod_params_default(C.byref(c))
+        self.albedo_floor = float(c.albedo_floor) if albedo_floor is None else float(albedo_floor)
+        if background is None:
+            self.background = tuple(float(v) for v in c.background)
+        else:
+            bg = np.atleast_1d(np.asarray(background, dtype=np.float32))
+            if bg.shape not in ((1,), (3,)):
+                raise ValueError("DemodParams: background is one number or three")
+            self.background = tuple(float(v) for v in np.broadcast_to(bg, (3,)))
+
+    def as_c(self):
+        c = SptDemodParams()
+        c.albedo_floor = self.albedo_floor
+        c.background[:] = self.background
+        return c
+
+    def __repr__(self):
+        return f"DemodParams(albedo_floor={self.albedo_floor!r}, background={self.background!r})"
+
+
+def _demod_params(params):
+    return (params if params is not None else DemodParams()).as_c()
 
 
 def temporal_history_bytes(w, h):
@@ -677,7 +714,7 @@ class Renderer:
             C.c_void_p(stream) if stream else None))
 
     def render_aov(self, w, h, samps_per_cell, aov="normal", seed=0, normalise=False, camera=None):
-        """First-hit feature buffer (spt_render_aov): 'normal', 'albedo', 'uv' or 'dist' of the closest hit of every camera sample of
+        """First-hit feature buffer (spt_render_aov): 'normal', 'albedo', 'uv', 'dist' or 'emission' of the closest hit of every camera sample of
         ``render`` with the same arguments, folded in its order.  Returns ((h, w, 3) float32, stats)."""
         kind = _aov_kind(aov)
         cam = camera if camera is not None else smallpt_camera(w, h)
@@ -894,6 +931,51 @@ class Renderer:
                                                            C.c_void_p(out_var_t.data_ptr()) if out_var_t is not None else None,
                                                            C.c_void_p(stream) if stream else None))
 
+    def _demod_host(self, who, fn, colour, albedo, coverage, emission, counts, params):
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (colour, albedo, coverage) + ((emission,) if emission is not None else ())]
+        if imgs[0].ndim != 3 or imgs[0].shape[2] != 3 or any(a.shape != imgs[0].shape for a in imgs):
+            raise ValueError(f"{who}: (h, w, 3) images of one size")
+        h, w, _ = imgs[0].shape
+        out = np.empty((h, w, 3), dtype=np.float32)
+        p = _demod_params(params)
+        ptr = [a.ctypes.data_as(C.c_void_p) for a in imgs] + ([None] if emission is None else [])
+        self._check(getattr(self._lib, fn)(self._h, *ptr, w, h, *[int(n) for n in counts], C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def demodulate(self, beauty, albedo, coverage, emission, beauty_samples, aov_samples, params=None):
+        """Colour to illumination (spt_demodulate): ``beauty`` the un-normalised (h, w, 3) sum over ``beauty_samples`` samples per pixel,
+        ``albedo`` / ``coverage`` / ``emission`` (or None) the un-normalised sums over ``aov_samples`` as ``render_aov_set`` and
+        ``render_aov(aov='emission')`` return them.  Returns the (h, w, 3) float32 MEAN illumination: what the filters take as their
+        beauty."""
+        return self._demod_host("demodulate", "spt_demodulate", beauty, albedo, coverage, emission, (beauty_samples, aov_samples), params)
+
+    def remodulate(self, illum, albedo, coverage, emission, aov_samples, params=None):
+        """The way back (spt_remodulate): the (filtered) mean illumination times the albedo plus the unmodulated part; returns the
+        (h, w, 3) float32 mean colour (``display`` takes it with weight 1)."""
+        return self._demod_host("remodulate", "spt_remodulate", illum, albedo, coverage, emission, (aov_samples,), params)
+
+    def _demod_device(self, who, fn, colour_t, albedo_t, coverage_t, emission_t, out_t, w, h, counts, params, stream):
+        for t in (colour_t, albedo_t, coverage_t, emission_t, out_t):
+            if t is not None and (t.numel() != w * h * 3 or not t.is_contiguous() or str(t.dtype) != "torch.float32" or t.device.type != "cuda"):
+                raise ValueError(f"{who}: contiguous float32 tensors on the GPU of w*h*3 elements")
+        if colour_t is None or albedo_t is None or coverage_t is None or out_t is None:
+            raise ValueError(f"{who}: only the emission may be None")
+        p = _demod_params(params)
+        self._check(getattr(self._lib, fn)(self._h, C.c_void_p(colour_t.data_ptr()), C.c_void_p(albedo_t.data_ptr()), C.c_void_p(coverage_t.data_ptr()),
+                       C.c_void_p(emission_t.data_ptr()) if emission_t is not None else None, w, h, *[int(n) for n in counts], C.byref(p),
+                       C.c_void_p(out_t.data_ptr()), C.c_void_p(stream) if stream else None))
+
+    def demodulate_device(self, beauty_t, albedo_t, coverage_t, emission_t, out_t, w, h, beauty_samples, aov_samples, params=None, stream=None):
+        """``demodulate`` on float32 CUDA tensors of w*h*3 elements (spt_demodulate_device), asynchronous on ``stream`` (a raw hipStream_t,
+        None = the context's stream).  ``out_t`` may be ``beauty_t`` itself; it may overlap nothing else."""
+        self._demod_device("demodulate_device", "spt_demodulate_device", beauty_t, albedo_t, coverage_t, emission_t, out_t, w, h,
+                           (beauty_samples, aov_samples), params, stream)
+
+    def remodulate_device(self, illum_t, albedo_t, coverage_t, emission_t, out_t, w, h, aov_samples, params=None, stream=None):
+        """``remodulate`` on float32 CUDA tensors (spt_remodulate_device); ``out_t`` may be ``illum_t`` itself."""
+        self._demod_device("remodulate_device", "spt_remodulate_device", illum_t, albedo_t, coverage_t, emission_t, out_t, w, h,
+                           (aov_samples,), params, stream)
+
     def denoise_pvar(self, beauty, normal, albedo, position, coverage, variance, aov_samples, params=None):
         """Variance-guided filter with a caller's per-pixel variance (spt_denoise_pvar): ``denoise_var`` with ``variance`` = (h, w)
         float32, >= 0, the variance of the luminance of ``beauty`` as given (a sum or a mean) in place of ``m2`` and ``frames``.
@@ -1026,6 +1108,20 @@ class Renderer:
         self._prog_size("progressive_temporal_begin")
         p = _temporal_params(params)
         self._check(self._lib.spt_progressive_temporal_begin(self._h, C.byref(p)))
+
+    def progressive_temporal_demodulate(self, params=True):
+        """Runs the temporal loop over illumination (spt_progressive_temporal_demodulate): ``params`` a ``DemodParams``, True for the
+        default floor with the context's environment as background (as the C++ host's wrapper), or None / False to switch the mode off again.  Either way the history is dropped: the next frame starts a new one and
+        the snapshots fail until it is made.  With the mode on every snapshot is remodulated under the last frame's albedo, coverage and
+        emission."""
+        self._prog_size("progressive_temporal_demodulate")
+        if params is None or params is False:
+            self._check(self._lib.spt_progressive_temporal_demodulate(self._h, None))
+            return
+        if params is True:                                   # the defaults, with the context's environment as the background
+            params = DemodParams(background=self.environment())
+        p = _demod_params(params)
+        self._check(self._lib.spt_progressive_temporal_demodulate(self._h, C.byref(p)))
 
     def progressive_temporal_frame(self, samps_per_cell, seed, reset=False, camera=None):
         """One frame of the temporal loop (spt_progressive_temporal_frame): the radiance launch of ``progressive_frame`` and the feature
