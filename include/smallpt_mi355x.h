@@ -16,6 +16,9 @@
  *   Intersector::traceRays + shadePaths per bounce              inside the kernels; the triangle seam itself
  *     (smallpt.cpp:553-587,154-267)                               (addTriangleMesh/build/traceRays, :427-473) is
  *                                                                 spt_set_meshes() / spt_trace_rays()
+ *   shadePaths(materials, paths, n, hits, nextPaths, outColor,   spt_wavefront_shade() / _device, between
+ *     rng) as a step of its own (smallpt.cpp:154-267) and the     spt_wavefront_generate(), a spt_trace_* query and
+ *     loop round it (:692-814), for a caller who owns the loop    spt_wavefront_accumulate(); spt_wavefront_render()
  *   shadePaths' debug views as shipped: the first hit's normal  spt_render_aov()       (host image)
  *     added and `continue` (smallpt.cpp:179-183; uv and          spt_render_aov_rows_device() (row band, async)
  *     triangle id one comment away)
@@ -950,6 +953,85 @@ int  spt_demodulate(spt_ctx* ctx, const float* beauty, const float* albedo, cons
 int  spt_remodulate(spt_ctx* ctx, const float* illum, const float* albedo, const float* coverage, const float* emission, uint32_t w,
                     uint32_t h, uint32_t aov_samples, const spt_demod_params* params, float* out_rgb);
 int  spt_progressive_temporal_demodulate(spt_ctx* ctx, const spt_demod_params* params);
+
+/* ---- the wavefront seam (csrc/spt_wavefront.hip): camera paths, one shadePaths step, accumulation ----
+ * The reference's GPU renderer keeps one buffer of PathContrib, calls Intersector::traceRays on it (smallpt.cpp:553-587), then
+ * shadePaths(materials, paths, n, hits, nextPaths, outColor, rng) (:154-267), until no path is left (Renderer::render, :692-814).  The
+ * queries above are the first half; these entry points are the other one, for a caller who owns the loop (its own intersector, a custom
+ * integrator, hit buffers merged from two scenes, shadow rays through spt_occluded_*):
+ *     generate -> [ trace (spt_trace_spheres_device / spt_trace_rays_device / the caller's own) -> shade -> accumulate ] until 0 children.
+ * The arithmetic is the render kernels' (camera sampling, D7 keys, D17 sin / cos, the glass split, roulette, D18, D19), so the events the
+ * loop emits, summed on the host in the D9 order, are the image of spt_render bit for bit, and the counters are spt_render's
+ * (tests/test_gpu_wavefront.py; tests/wavefront_expected.py fold_d9).
+ *
+ * spt_path: PathContrib without its ray (smallpt.cpp:106-118) + the D7 address of the sample.  The ray of path i is rays[i] of a parallel
+ * spt_ray array, so that array goes to spt_trace_*_device unchanged.  16-byte aligned on the device. */
+typedef struct spt_path {
+    float    weight[3];  uint32_t depth;          /* PathContrib::weight, ::depth */
+    uint32_t pixel;      /* PathContrib::pixelIdx: GLOBAL index py * w + px (row 0 = bottom) */
+    uint32_t sample;     /* index in pixel = cell * samps + s (smallpt.cpp:306) */
+    uint32_t k0, k1;     /* D7 keys of that sample */
+    uint32_t branch;     /* D7 branch bits: bit k = transmitted child of the split at depth k */
+    uint32_t pad[3];     /* written 0, ignored on input */
+} spt_path;
+#if defined(__cplusplus)
+static_assert(sizeof(spt_path) == 48, "spt_path: 48 bytes");
+#else
+_Static_assert(sizeof(spt_path) == 48, "spt_path: 48 bytes");
+#endif
+/* Every entry has a device form (asynchronous on hip_stream, NULL = the context's stream; device buffers) and a blocking host-buffer form
+ * without `_device`, staged through the context's scratch.  On failure the message is in spt_last_error, nothing is launched, nothing is
+ * written and the context stays usable: a NULL required pointer; w, h or samps of 0; a band outside the image; first + count beyond the
+ * band's path count; an unknown sampler; misalignment (device forms: 16 bytes for paths, 8 for counts, 4 for the rest); an output that
+ * overlaps an input or another output; next_capacity < 2 n; n > 2^30; no current scene (shade and render).
+ *
+ * 1. generate: camera paths first .. first + count of the band [row_begin, row_begin + row_count) in the order
+ *    i = (local_pixel * 4 + cell) * samps + s, local_pixel = ry * w + px: ray, keys and sample exactly what spt_render and spt_render_aov
+ *    trace for the same arguments; weight = (1,1,1), depth = 0, branch = 0.  Needs no scene.  spt_wavefront_path_count (host-only) =
+ *    4 * w * row_count * samps, the paths of a band. */
+uint64_t spt_wavefront_path_count(uint32_t w, uint32_t row_count, uint32_t samps_per_cell);
+int  spt_wavefront_generate_device(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                                   uint32_t samps_per_cell, uint64_t seed, uint64_t first, uint64_t count, void* d_rays, void* d_paths,
+                                   void* hip_stream);
+int  spt_wavefront_generate(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count,
+                            uint32_t samps_per_cell, uint64_t seed, uint64_t first, uint64_t count, spt_ray* rays, spt_path* paths);
+/* 2. shade: one call of shadePaths over n paths and their Hit records, with the materials of the current scene (sphere hit.instId of a
+ *    sphere table, materials[hit.instId] of meshes and instances) and the context's environment E.  Per path i:
+ *      miss -- !(hit.dist < 1e20f), or instId at or past the material count (never dereferenced) --: events[i] = E set ? weight * E : 0,
+ *        no child;
+ *      hit: events[i] = weight * emission, then roulette at depth > 5, the DIFF / SPEC / REFR branches, the split while depth <= 2, and
+ *        per child extend, the depth cap (a child whose depth reaches SPT_MAX_DEPTH is dropped and counted as a kill) and the zero-weight
+ *        cut (a child of weight exactly (0,0,0) is dropped).  hit.x and hit.n are used as given; hit.n may have any length.
+ *    A child copies pixel, sample, k0, k1; the transmitted child of a split sets branch |= 1 << depth.
+ *    Children are written to d_next_rays / d_next_paths in the order of the reference's nextPaths[currentNextPathIdx++]: ascending parent
+ *    index, the reflected child before the transmitted one of a split (a stable compaction; no atomic decides a position).
+ *    d_counts: two uint64_t, written {children, depth-cap kills of this call} (not accumulated).  next_capacity (in paths) >= 2 n is
+ *    demanded up front; n <= 2^30; n == 0 succeeds and writes {0, 0}.  d_events: n packed float3.  The compaction's staging belongs to the
+ *    context, grows on demand and goes with spt_destroy; the shade calls of one context run one after another whatever their streams
+ *    (they share it), like the filters.  A call changes no render state. */
+int  spt_wavefront_shade_device(spt_ctx* ctx, const void* d_rays, const void* d_paths, const void* d_hits, uint64_t n, void* d_next_rays,
+                                void* d_next_paths, uint64_t next_capacity, void* d_events, void* d_counts, void* hip_stream);
+int  spt_wavefront_shade(spt_ctx* ctx, const spt_ray* rays, const spt_path* paths, const spt_hit* hits, uint64_t n, spt_ray* next_rays,
+                         spt_path* next_paths, uint64_t next_capacity, float* events, uint64_t* counts);
+/* 3. accumulate: for every pixel p of [pixel_first, pixel_first + pixel_count), starting from acc = image[p - pixel_first]: for ascending
+ *    i with paths[i].pixel == p, acc += events[i] (float32, per component, sequential); then image[p - pixel_first] = acc.  Paths of other
+ *    pixels are skipped and their pixels never written.  Precondition: the paths of one pixel form ONE contiguous run of the array --
+ *    generate writes them so, and a stable compaction keeps the children of a run in a run, in their parents' order --; otherwise that
+ *    pixel's sum is unspecified (nothing faults).  d_image: pixel_count packed float3. */
+int  spt_wavefront_accumulate_device(spt_ctx* ctx, const void* d_paths, const void* d_events, uint64_t n, uint64_t pixel_first,
+                                     uint64_t pixel_count, void* d_image, void* hip_stream);
+int  spt_wavefront_accumulate(spt_ctx* ctx, const spt_path* paths, const float* events, uint64_t n, uint64_t pixel_first,
+                              uint64_t pixel_count, float* image);
+/* 4. Renderer::render's loop (smallpt.cpp:692-814) behind the boundary: generate, the scene's own closest-hit query (the code path of
+ *    spt_trace_spheres_device / spt_trace_rays_device: every scene kind and accel mode), shade, accumulate, until no child is left, in
+ *    chunks of whole pixels.  SPT_FLAG_NORMALISE multiplies by 1.f / spp.  stats: samples = camera paths, bounces = rays traced,
+ *    max_depth_kills = the sum of the kills; they equal spt_render's.  The image is, bit for bit, what driving 1-3 from outside gives and
+ *    does not depend on the chunk size (pixels are independent).  It is NOT the D9 order of spt_render: a pixel's events are added bounce
+ *    by bounce instead of sample by sample -- the same terms in another order, within DESIGN.md D9's bound on reordering.  Tens of
+ *    times slower than spt_render (launches and a host read per bounce, every path through memory): a seam, not a
+ *    replacement.  Fails with the query's message when no scene is current. */
+int  spt_wavefront_render(spt_ctx* ctx, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps_per_cell, uint64_t seed,
+                          uint32_t flags, float* out_rgb, spt_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,11 @@ class SptDemodParams(C.Structure):  # spt_demod_params: 16 bytes
     _fields_ = [("albedo_floor", C.c_float), ("background", C.c_float * 3)]
 
 
+class SptPath(C.Structure):         # spt_path: PathContrib without its ray + the D7 address of the sample; 48 bytes
+    _fields_ = [("weight", C.c_float * 3), ("depth", C.c_uint32), ("pixel", C.c_uint32), ("sample", C.c_uint32), ("k0", C.c_uint32),
+                ("k1", C.c_uint32), ("branch", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
 class SptInstance(C.Structure):     # RTP_BUFFER_FORMAT_TRANSFORM_FLOAT4x3 + INSTANCE_MODEL, smallpt.cpp:514-529
     _fields_ = [("transform", C.c_float * 12), ("model", C.c_uint32), ("pad", C.c_uint32)]
 
@@ -169,6 +174,17 @@ SYMBOLS = {
     "spt_demodulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDemodParams), _P]),
     "spt_remodulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SptDemodParams), _P]),
     "spt_progressive_temporal_demodulate": (C.c_int, [_P, C.POINTER(SptDemodParams)]),
+    "spt_wavefront_path_count": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "spt_wavefront_generate_device": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "spt_wavefront_generate": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                         C.c_uint64, C.c_uint64, _P, _P]),
+    "spt_wavefront_shade_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P]),
+    "spt_wavefront_shade": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P]),
+    "spt_wavefront_accumulate_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P]),
+    "spt_wavefront_accumulate": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P]),
+    "spt_wavefront_render": (C.c_int, [_P, C.POINTER(SptCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _P,
+                                       C.POINTER(SptStats)]),
 }
 
 # test / tuning hooks declared in csrc/spt_internal.h (not part of the drop-in boundary)
@@ -196,6 +212,7 @@ INTERNAL_SYMBOLS = {
     "spt_set_denoise_form": (C.c_int, [_P, C.c_int]),
     "spt_set_denoise_timing": (C.c_int, [_P, C.c_int]),
     "spt_denoise_last_ms": (C.c_int, [_P, C.POINTER(C.c_float * 6)]),
+    "spt_set_wavefront_chunk": (C.c_int, [_P, C.c_uint32]),
 }
 
 class SptMultiStats(C.Structure):

@@ -18,6 +18,8 @@
 #include "spt_temporal_var_host.h"
 #include "spt_demod.h"
 #include "spt_demod_host.h"
+#include "spt_wavefront.h"
+#include "spt_wavefront_host.h"
 #include "spt_devbuf.h"
 
 #include <chrono>
@@ -184,6 +186,13 @@ struct spt_ctx {
     DevBuf<float> d_disp_table;
     DevBuf<uint8_t> d_disp8;
     Temporal tp;
+    // spt_wavefront_*: the staging of a shade call's compaction (512 children per workgroup of 256 paths; {children, kills} | offset per
+    // workgroup), the completion of the last shade call (the next one, on any stream, waits for it: they share the staging), and the loop
+    // buffers of spt_wavefront_render and the host forms: rays / paths ping-pong, hits, events, the image, the two counts
+    DevBuf<float> wf_st_rays; DevBuf<uint4> wf_st_paths; DevBuf<uint32_t> wf_totals;
+    hipEvent_t ev_wf = nullptr; bool wf_pending = false;
+    DevBuf<float> wf_rays[2], wf_hits, wf_events, wf_image; DevBuf<uint4> wf_paths[2]; DevBuf<unsigned long long> wf_counts;
+    uint32_t wf_chunk = 0;         // spt_set_wavefront_chunk: pixels per chunk of spt_wavefront_render (0 = default)
     hipEvent_t ev_acc = nullptr;   // owner of an accumBuffer: completion of the most recent accumulation (any lane's stream)
     bool acc_recorded = false;
     bool frame_in_flight = false;  // a spt_progressive_frame_async of this lane has not been waited for
@@ -300,6 +309,7 @@ void spt_destroy(spt_ctx* c)
     if (c->ev_denoise) (void)hipEventDestroy(c->ev_denoise);
     for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
     if (c->ev_query) (void)hipEventDestroy(c->ev_query);
+    if (c->ev_wf) (void)hipEventDestroy(c->ev_wf);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_mid) (void)hipEventDestroy(c->ev_mid);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
@@ -3172,6 +3182,223 @@ int spt_remodulate(spt_ctx* c, const float* illum, const float* albedo, const fl
 {
     if (!c) return 1;
     return demod_host(c, "spt_remodulate", true, illum, albedo, coverage, emission, w, h, 1u, aov_samples, p, out_rgb);
+}
+
+// ---- the wavefront seam (spt_wavefront.hip; the contract is stated in include/smallpt_mi355x.h, the checks are spt_wavefront_host.h) ----
+uint64_t spt_wavefront_path_count(uint32_t w, uint32_t row_count, uint32_t samps_per_cell) { return spt::wf_path_count(w, row_count, samps_per_cell); }
+
+static int wf_generate_enqueue(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count, uint32_t samps,
+                               uint64_t seed, uint64_t first, uint64_t count, float* d_rays, uint4* d_paths, hipStream_t st)
+{
+    spt::KParams P{};
+    fill_kparams(c, cam, w, h, row_begin, row_count, samps, seed, P);
+    SPT_HIP(c, spt_wf_generate_launch(&P, first, (uint32_t)count, d_rays, d_paths, st));
+    return 0;
+}
+
+int spt_wavefront_generate_device(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count, uint32_t samps,
+                                  uint64_t seed, uint64_t first, uint64_t count, void* d_rays, void* d_paths, void* hip_stream)
+{
+    if (!c) return 1;
+    const spt::WfGenerateCall k{cam, w, h, row_begin, row_count, samps, first, count, d_rays, d_paths, true};
+    char msg[256];
+    if (spt::wf_generate_validate(k, "spt_wavefront_generate_device", msg, sizeof msg)) return c->fail("%s", msg);
+    SPT_HIP(c, hipSetDevice(c->device));
+    return wf_generate_enqueue(c, cam, w, h, row_begin, row_count, samps, seed, first, count, static_cast<float*>(d_rays), static_cast<uint4*>(d_paths),
+                               hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int spt_wavefront_generate(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_count, uint32_t samps,
+                           uint64_t seed, uint64_t first, uint64_t count, spt_ray* rays, spt_path* paths)
+{
+    if (!c) return 1;
+    const spt::WfGenerateCall k{cam, w, h, row_begin, row_count, samps, first, count, rays, paths, false};
+    char msg[256];
+    if (spt::wf_generate_validate(k, "spt_wavefront_generate", msg, sizeof msg)) return c->fail("%s", msg);
+    if (count == 0) return 0;
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, c->wf_rays[0].grow(count * 6));
+    SPT_HIP(c, c->wf_paths[0].grow(count * 3));
+    if (int rc = wf_generate_enqueue(c, cam, w, h, row_begin, row_count, samps, seed, first, count, c->wf_rays[0], c->wf_paths[0], c->stream)) return rc;
+    SPT_HIP(c, hipMemcpyAsync(rays, c->wf_rays[0], count * sizeof(spt_ray), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(paths, c->wf_paths[0], count * sizeof(spt_path), hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static int wf_scene_check(spt_ctx* c, const char* who)
+{
+    if (!c->d_geom && !c->mesh_scene) return c->fail("%s: no scene set (call spt_set_scene, spt_set_meshes or spt_set_instances)", who);
+    return 0;
+}
+
+// Validated arguments, device set, a current scene.  Enqueues one shadePaths step on `st` behind the context's previous one.
+static int wf_shade_enqueue(spt_ctx* c, const float* d_rays, const uint4* d_paths, const uint32_t* d_hits, uint64_t n, float* d_next_rays,
+                            uint4* d_next_paths, float* d_events, unsigned long long* d_counts, hipStream_t st)
+{
+    if (n == 0) { SPT_HIP(c, hipMemsetAsync(d_counts, 0, 16, st)); return 0; }
+    const float4* mats = c->d_mat;
+    uint32_t nmat = c->n;
+    if (c->mesh_scene) {
+        mats = c->inst_scene ? c->inst.d_mats : c->d_mesh_mats;
+        nmat = c->inst_scene ? c->inst.ninst : c->ninst;
+    }
+    const size_t blocks = spt::wf_blocks(n), slots = blocks * 2 * spt::kWfBlock;
+    if (!c->ev_wf) SPT_HIP(c, hipEventCreateWithFlags(&c->ev_wf, hipEventDisableTiming));
+    SPT_HIP(c, c->wf_st_rays.grow(slots * 6));           // (hipFree waits for the device: no earlier call still uses the old staging)
+    SPT_HIP(c, c->wf_st_paths.grow(slots * 3));
+    SPT_HIP(c, c->wf_totals.grow(blocks * 3));
+    if (c->wf_pending) SPT_HIP(c, hipStreamWaitEvent(st, c->ev_wf, 0));
+    SPT_HIP(c, spt_wf_shade_launch(d_rays, d_paths, d_hits, (uint32_t)n, mats, nmat, env_on(c) ? c->env : nullptr, d_events, d_next_rays, d_next_paths,
+                                   c->wf_st_rays, c->wf_st_paths, reinterpret_cast<uint2*>(c->wf_totals.ptr), c->wf_totals.ptr + 2 * blocks, d_counts, st));
+    SPT_HIP(c, hipEventRecord(c->ev_wf, st));
+    c->wf_pending = true;
+    return 0;
+}
+
+int spt_wavefront_shade_device(spt_ctx* c, const void* d_rays, const void* d_paths, const void* d_hits, uint64_t n, void* d_next_rays, void* d_next_paths,
+                               uint64_t next_capacity, void* d_events, void* d_counts, void* hip_stream)
+{
+    if (!c) return 1;
+    const spt::WfShadeCall k{d_rays, d_paths, d_hits, n, d_next_rays, d_next_paths, next_capacity, d_events, d_counts, true};
+    char msg[256];
+    if (spt::wf_shade_validate(k, "spt_wavefront_shade_device", msg, sizeof msg)) return c->fail("%s", msg);
+    if (wf_scene_check(c, "spt_wavefront_shade_device")) return 1;
+    SPT_HIP(c, hipSetDevice(c->device));
+    return wf_shade_enqueue(c, static_cast<const float*>(d_rays), static_cast<const uint4*>(d_paths), static_cast<const uint32_t*>(d_hits), n,
+                            static_cast<float*>(d_next_rays), static_cast<uint4*>(d_next_paths), static_cast<float*>(d_events),
+                            static_cast<unsigned long long*>(d_counts), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int spt_wavefront_shade(spt_ctx* c, const spt_ray* rays, const spt_path* paths, const spt_hit* hits, uint64_t n, spt_ray* next_rays, spt_path* next_paths,
+                        uint64_t next_capacity, float* events, uint64_t* counts)
+{
+    if (!c) return 1;
+    const spt::WfShadeCall k{rays, paths, hits, n, next_rays, next_paths, next_capacity, events, counts, false};
+    char msg[256];
+    if (spt::wf_shade_validate(k, "spt_wavefront_shade", msg, sizeof msg)) return c->fail("%s", msg);
+    if (wf_scene_check(c, "spt_wavefront_shade")) return 1;
+    if (n == 0) { counts[0] = counts[1] = 0; return 0; }
+    SPT_HIP(c, hipSetDevice(c->device));
+    // staging: rays / paths [0] in, [1] out (2 n), hits, events, counts
+    SPT_HIP(c, c->wf_rays[0].grow(n * 6)); SPT_HIP(c, c->wf_paths[0].grow(n * 3));
+    SPT_HIP(c, c->wf_rays[1].grow(2 * n * 6)); SPT_HIP(c, c->wf_paths[1].grow(2 * n * 3));
+    SPT_HIP(c, c->wf_hits.grow(n * 11)); SPT_HIP(c, c->wf_events.grow(n * 3)); SPT_HIP(c, c->wf_counts.grow(2));
+    SPT_HIP(c, hipMemcpyAsync(c->wf_rays[0], rays, n * sizeof(spt_ray), hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(c->wf_paths[0], paths, n * sizeof(spt_path), hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(c->wf_hits, hits, n * sizeof(spt_hit), hipMemcpyHostToDevice, c->stream));
+    if (int rc = wf_shade_enqueue(c, c->wf_rays[0], c->wf_paths[0], reinterpret_cast<const uint32_t*>(c->wf_hits.ptr), n, c->wf_rays[1], c->wf_paths[1],
+                                  c->wf_events, c->wf_counts, c->stream)) return rc;
+    unsigned long long ctr[2] = {0, 0};
+    SPT_HIP(c, hipMemcpyAsync(ctr, c->wf_counts, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(events, c->wf_events, n * 12u, hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (ctr[0]) {
+        SPT_HIP(c, hipMemcpyAsync(next_rays, c->wf_rays[1], ctr[0] * sizeof(spt_ray), hipMemcpyDeviceToHost, c->stream));
+        SPT_HIP(c, hipMemcpyAsync(next_paths, c->wf_paths[1], ctr[0] * sizeof(spt_path), hipMemcpyDeviceToHost, c->stream));
+        SPT_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    counts[0] = ctr[0]; counts[1] = ctr[1];
+    return 0;
+}
+
+int spt_wavefront_accumulate_device(spt_ctx* c, const void* d_paths, const void* d_events, uint64_t n, uint64_t pixel_first, uint64_t pixel_count,
+                                    void* d_image, void* hip_stream)
+{
+    if (!c) return 1;
+    const spt::WfAccumulateCall k{d_paths, d_events, n, pixel_first, pixel_count, d_image, true};
+    char msg[256];
+    if (spt::wf_accumulate_validate(k, "spt_wavefront_accumulate_device", msg, sizeof msg)) return c->fail("%s", msg);
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, spt_wf_accumulate_launch(static_cast<const uint4*>(d_paths), static_cast<const float*>(d_events), (uint32_t)n, pixel_first, pixel_count,
+                                        static_cast<float*>(d_image), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream));
+    return 0;
+}
+
+int spt_wavefront_accumulate(spt_ctx* c, const spt_path* paths, const float* events, uint64_t n, uint64_t pixel_first, uint64_t pixel_count, float* image)
+{
+    if (!c) return 1;
+    const spt::WfAccumulateCall k{paths, events, n, pixel_first, pixel_count, image, false};
+    char msg[256];
+    if (spt::wf_accumulate_validate(k, "spt_wavefront_accumulate", msg, sizeof msg)) return c->fail("%s", msg);
+    if (n == 0 || pixel_count == 0) return 0;
+    SPT_HIP(c, hipSetDevice(c->device));
+    SPT_HIP(c, c->wf_paths[0].grow(n * 3)); SPT_HIP(c, c->wf_events.grow(n * 3)); SPT_HIP(c, c->wf_image.grow(pixel_count * 3));
+    SPT_HIP(c, hipMemcpyAsync(c->wf_paths[0], paths, n * sizeof(spt_path), hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(c->wf_events, events, n * 12u, hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(c->wf_image, image, pixel_count * 12u, hipMemcpyHostToDevice, c->stream));
+    SPT_HIP(c, spt_wf_accumulate_launch(c->wf_paths[0], c->wf_events, (uint32_t)n, pixel_first, pixel_count, c->wf_image, c->stream));
+    SPT_HIP(c, hipMemcpyAsync(image, c->wf_image, pixel_count * 12u, hipMemcpyDeviceToHost, c->stream));
+    SPT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Test hook (spt_internal.h): pixels per chunk of spt_wavefront_render, 0 = the default (about 2^22 camera paths)
+int spt_set_wavefront_chunk(spt_ctx* c, uint32_t pixels)
+{
+    if (!c) return 1;
+    c->wf_chunk = pixels;
+    return 0;
+}
+
+// Renderer::render's loop (smallpt.cpp:692-814) over the entry points above and the scene's own closest-hit query, on the context's
+// stream, in chunks of whole pixels.  The host reads the two counts after every bounce (a device-side loop is out of scope).
+int spt_wavefront_render(spt_ctx* c, const spt_camera* cam, uint32_t w, uint32_t h, uint32_t samps, uint64_t seed, uint32_t flags, float* out_rgb,
+                         spt_stats* stats)
+{
+    if (!c) return 1;
+    const char* const who = "spt_wavefront_render";
+    if (!cam || !out_rgb) return c->fail("%s: NULL argument", who);
+    if (w == 0 || h == 0 || samps == 0) return c->fail("%s: empty image or samps == 0", who);
+    if ((uint64_t)w * h > 0xFFFFFFFFull) return c->fail("%s: w*h exceeds 2^32-1 pixels", who);
+    if ((uint64_t)samps * 4 > spt::kWfMaxPaths) return c->fail("%s: more than 2^30 samples per pixel", who);
+    if (cam->sampler > SPT_SAMPLER_PINHOLE) return c->fail("%s: unknown camera sampler %u", who, cam->sampler);
+    if (!c->mesh_scene && trace_spheres_check(c, who, cam, 1, out_rgb)) return 1;       // the query's message
+    const auto t0 = std::chrono::steady_clock::now();
+    SPT_HIP(c, hipSetDevice(c->device));
+    if (c->pending) SPT_HIP(c, hipEventSynchronize(c->ev_stop));
+    const uint64_t npix = (uint64_t)w * h, per_pixel = 4ull * samps;
+    uint64_t chunk = c->wf_chunk ? c->wf_chunk : (1ull << 22) / per_pixel;
+    if (chunk * per_pixel > spt::kWfMaxPaths) chunk = spt::kWfMaxPaths / per_pixel;
+    if (chunk == 0) chunk = 1;
+    hipStream_t st = c->stream;
+    SPT_HIP(c, c->wf_image.grow(npix * 3));
+    SPT_HIP(c, c->wf_counts.grow(2));
+    SPT_HIP(c, hipMemsetAsync(c->wf_image, 0, npix * 12u, st));
+    uint64_t bounces = 0, kills = 0;
+    for (uint64_t pix0 = 0; pix0 < npix; pix0 += chunk) {
+        uint64_t n = (npix - pix0 < chunk ? npix - pix0 : chunk) * per_pixel;
+        int cur = 0;
+        SPT_HIP(c, c->wf_rays[0].grow(n * 6)); SPT_HIP(c, c->wf_paths[0].grow(n * 3));
+        if (int rc = wf_generate_enqueue(c, cam, w, h, 0, h, samps, seed, pix0 * per_pixel, n, c->wf_rays[0], c->wf_paths[0], st)) return rc;
+        while (n != 0) {
+            if (n > spt::kWfMaxPaths) return c->fail("%s: a bounce of more than 2^30 paths; lower the chunk", who);
+            // only the outputs of this bounce are grown (a grown buffer loses its contents)
+            SPT_HIP(c, c->wf_rays[cur ^ 1].grow(2 * n * 6)); SPT_HIP(c, c->wf_paths[cur ^ 1].grow(2 * n * 3));
+            SPT_HIP(c, c->wf_hits.grow(n * 11)); SPT_HIP(c, c->wf_events.grow(n * 3));
+            if (int rc = c->mesh_scene ? spt_trace_rays_device(c, c->wf_rays[cur], n, c->wf_hits, st) : spt_trace_spheres_device(c, c->wf_rays[cur], n, c->wf_hits, st)) return rc;
+            if (int rc = wf_shade_enqueue(c, c->wf_rays[cur], c->wf_paths[cur], reinterpret_cast<const uint32_t*>(c->wf_hits.ptr), n, c->wf_rays[cur ^ 1],
+                                          c->wf_paths[cur ^ 1], c->wf_events, c->wf_counts, st)) return rc;
+            SPT_HIP(c, spt_wf_accumulate_launch(c->wf_paths[cur], c->wf_events, (uint32_t)n, 0, npix, c->wf_image, st));
+            unsigned long long ctr[2] = {0, 0};
+            SPT_HIP(c, hipMemcpyAsync(ctr, c->wf_counts, sizeof ctr, hipMemcpyDeviceToHost, st));
+            SPT_HIP(c, hipStreamSynchronize(st));
+            bounces += n; kills += ctr[1];
+            n = ctr[0];
+            cur ^= 1;
+        }
+    }
+    if (flags & SPT_FLAG_NORMALISE) SPT_HIP(c, spt_wf_scale_launch(c->wf_image, npix * 3, 1.f / (float)(4u * samps), st));
+    SPT_HIP(c, hipMemcpyAsync(out_rgb, c->wf_image, npix * 12u, hipMemcpyDeviceToHost, st));
+    SPT_HIP(c, hipStreamSynchronize(st));
+    if (stats) {
+        *stats = spt_stats{};
+        stats->samples = npix * per_pixel;
+        stats->bounces = bounces;
+        stats->max_depth_kills = kills;
+        stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return 0;
 }
 
 // Test / measurement hook (spt_internal.h)

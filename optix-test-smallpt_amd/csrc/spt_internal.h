@@ -153,6 +153,10 @@ int  spt_set_denoise_form(spt_ctx* ctx, int form);
 int  spt_set_denoise_timing(spt_ctx* ctx, int on);
 int  spt_denoise_last_ms(spt_ctx* ctx, float* ms6);
 
+/* spt_wavefront_render: pixels per chunk of its loop (0 = the default, about 2^22 camera paths per chunk).  Chunks are whole pixels and
+ * pixels are independent: results never depend on it (tests/test_gpu_wavefront.py renders at 7 pixels per chunk). */
+int  spt_set_wavefront_chunk(spt_ctx* ctx, uint32_t pixels);
+
 /* libsmallpt_mi355x_multi.so: kernel watchdog (spt_set_watchdog) of ONE rank's context, so that a test can make exactly one
  * device's render fail and check that spt_multi_render returns its error instead of hanging in the exchange. */
 struct spt_multi;

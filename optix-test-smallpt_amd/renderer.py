@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import SptCamera, SptDemodParams, SptDenoiseParams, SptDenoiseVarParams, SptDisplayParams, SptInstance, SptMaterial, SptMesh, SptMultiStats, SptStats, SptTemporalParams, SptTemporalVarParams, load_library, load_multi_library
-from .scene import HIT_DTYPE, INSTANCE_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
+from .scene import HIT_DTYPE, INSTANCE_DTYPE, PATH_DTYPE, RAY_DTYPE, RAY_RANGE_DTYPE, SPHERE_DTYPE
 
 FLAG_NORMALISE = 1
 FLAG_ONE_SHOT = 2          # scheduling only: no dispatch order used or recorded for this launch (include/smallpt_mi355x.h)
@@ -122,6 +122,13 @@ def _occluded_device(r, who, name, rays_t, tmax_t, out_t, stream):
         return out_t
     r._check(fn(r._h, C.c_void_p(rays_t.data_ptr()), tp, n, C.c_void_p(out_t.data_ptr()), C.c_void_p(stream.cuda_stream)))
     return out_t
+
+
+def _wf_tensor(who, t, dtype, rows, cols):
+    """A device tensor of the wavefront entries: contiguous, of ``dtype``, shape (>= rows, cols)."""
+    if not (hasattr(t, "data_ptr") and t.device.type == "cuda" and str(t.dtype) == dtype and t.is_contiguous() and t.dim() == 2
+            and t.shape[1] == cols and t.shape[0] >= rows):
+        raise ValueError(f"{who}: expected a contiguous {dtype} device tensor of shape (>= {rows}, {cols})")
 
 
 # spt_render_aov kinds (include/smallpt_mi355x.h SPT_AOV_*)
@@ -975,6 +982,155 @@ class Renderer:
         """``remodulate`` on float32 CUDA tensors (spt_remodulate_device); ``out_t`` may be ``illum_t`` itself."""
         self._demod_device("remodulate_device", "spt_remodulate_device", illum_t, albedo_t, coverage_t, emission_t, out_t, w, h,
                            (aov_samples,), params, stream)
+
+    # ---- the wavefront seam (spt_wavefront_*): camera paths, one shadePaths step, accumulation ----
+    @staticmethod
+    def wavefront_path_count(w, row_count, samps_per_cell):
+        """spt_wavefront_path_count: the camera paths of a band, 4 * w * row_count * samps."""
+        return int(load_library().spt_wavefront_path_count(int(w), int(row_count), int(samps_per_cell)))
+
+    def _wf_window(self, w, h, samps, row_begin, row_count, first, count):
+        row_count = h - row_begin if row_count is None else row_count
+        if count is None:
+            count = max(0, self.wavefront_path_count(w, row_count, samps) - first)
+        return int(row_count), int(count)
+
+    def wavefront_generate(self, w, h, samps_per_cell, seed=0, camera=None, row_begin=0, row_count=None, first=0, count=None):
+        """Camera paths first .. first + count of a band (spt_wavefront_generate), in the order ((local pixel * 4 + cell) * samps + s): the
+        rays and keys ``render`` traces for the same arguments.  Returns (RAY_DTYPE[count], PATH_DTYPE[count])."""
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        row_count, count = self._wf_window(w, h, samps_per_cell, row_begin, row_count, first, count)
+        rays, paths = np.zeros(count, dtype=RAY_DTYPE), np.zeros(count, dtype=PATH_DTYPE)
+        self._check(self._lib.spt_wavefront_generate(self._h, C.byref(cam), w, h, row_begin, row_count, samps_per_cell, seed, first, count,
+                                                     rays.ctypes.data_as(C.c_void_p), paths.ctypes.data_as(C.c_void_p)))
+        return rays, paths
+
+    def wavefront_generate_device(self, rays_t, paths_t, w, h, samps_per_cell, seed=0, camera=None, row_begin=0, row_count=None, first=0,
+                                  count=None, stream=None):
+        """The same into device tensors (spt_wavefront_generate_device): ``rays_t`` float32 (>= count, 6), ``paths_t`` int32 (>= count, 12),
+        16-byte aligned (a path is 12 words, PATH_DTYPE).  Asynchronous on ``stream`` (a raw hipStream_t, None = the context's stream)."""
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        row_count, count = self._wf_window(w, h, samps_per_cell, row_begin, row_count, first, count)
+        _wf_tensor("wavefront_generate_device", rays_t, "torch.float32", count, 6)
+        _wf_tensor("wavefront_generate_device", paths_t, "torch.int32", count, 12)
+        self._check(self._lib.spt_wavefront_generate_device(self._h, C.byref(cam), w, h, row_begin, row_count, samps_per_cell, seed, first, count,
+                                                            C.c_void_p(rays_t.data_ptr()), C.c_void_p(paths_t.data_ptr()),
+                                                            C.c_void_p(stream) if stream else None))
+        return count
+
+    def wavefront_shade(self, rays, paths, hits):
+        """One shadePaths step (spt_wavefront_shade) over RAY_DTYPE / PATH_DTYPE / HIT_DTYPE arrays of one length, with the current scene's
+        materials and environment.  Returns (events (n, 3) float32, next rays, next paths, depth-cap kills): the children in the order of
+        the reference's nextPaths -- ascending parent, reflected before transmitted."""
+        rays = _ray_array(rays)
+        paths, hits = np.ascontiguousarray(paths, dtype=PATH_DTYPE), np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        n = len(rays)
+        if paths.shape != (n,) or hits.shape != (n,):
+            raise ValueError("wavefront_shade: rays, paths and hits of one length")
+        events = np.zeros((n, 3), dtype=np.float32)
+        nrays, npaths = np.zeros(2 * n, dtype=RAY_DTYPE), np.zeros(2 * n, dtype=PATH_DTYPE)
+        counts = (C.c_uint64 * 2)()
+        self._check(self._lib.spt_wavefront_shade(self._h, rays.ctypes.data_as(C.c_void_p), paths.ctypes.data_as(C.c_void_p),
+                                                  hits.ctypes.data_as(C.c_void_p), n, nrays.ctypes.data_as(C.c_void_p),
+                                                  npaths.ctypes.data_as(C.c_void_p), 2 * n, events.ctypes.data_as(C.c_void_p), counts))
+        m = int(counts[0])
+        return events, nrays[:m].copy(), npaths[:m].copy(), int(counts[1])
+
+    def wavefront_shade_device(self, rays_t, paths_t, hits_t, next_rays_t, next_paths_t, events_t, counts_t, n=None, stream=None):
+        """The same on device tensors (spt_wavefront_shade_device): float32 rays (>= n, 6), hits (>= n, 11) and events (>= n, 3), int32
+        paths (>= n, 12), the outputs ``next_rays_t`` / ``next_paths_t`` with room for 2 n children, ``counts_t`` int64 (2,) =
+        {children, depth-cap kills}.  n = None: the rays' length.  Asynchronous on ``stream`` (a raw hipStream_t, None = the context's)."""
+        who = "wavefront_shade_device"
+        n = int(rays_t.shape[0] if n is None else n)
+        _wf_tensor(who, rays_t, "torch.float32", n, 6)
+        _wf_tensor(who, paths_t, "torch.int32", n, 12)
+        _wf_tensor(who, hits_t, "torch.float32", n, 11)
+        _wf_tensor(who, events_t, "torch.float32", n, 3)
+        _wf_tensor(who, next_rays_t, "torch.float32", 0, 6)
+        _wf_tensor(who, next_paths_t, "torch.int32", 0, 12)
+        if str(counts_t.dtype) != "torch.int64" or counts_t.numel() != 2 or counts_t.device.type != "cuda":
+            raise ValueError(f"{who}: counts_t is an int64 device tensor of 2 elements")
+        cap = min(int(next_rays_t.shape[0]), int(next_paths_t.shape[0]))
+        self._check(self._lib.spt_wavefront_shade_device(self._h, C.c_void_p(rays_t.data_ptr()), C.c_void_p(paths_t.data_ptr()), C.c_void_p(hits_t.data_ptr()),
+                                                         n, C.c_void_p(next_rays_t.data_ptr()), C.c_void_p(next_paths_t.data_ptr()), cap,
+                                                         C.c_void_p(events_t.data_ptr()), C.c_void_p(counts_t.data_ptr()),
+                                                         C.c_void_p(stream) if stream else None))
+
+    def wavefront_accumulate(self, paths, events, image, pixel_first=0):
+        """image[p - pixel_first] += the events of the paths of pixel p, in order (spt_wavefront_accumulate): ``image`` (pixels, 3) float32 (any
+        shape of 3 * pixels elements); returns the new image, same shape.  The paths of one pixel must form one run of the array."""
+        paths = np.ascontiguousarray(paths, dtype=PATH_DTYPE)
+        events = np.ascontiguousarray(events, dtype=np.float32).reshape(-1, 3)
+        out = np.array(image, dtype=np.float32, order="C")
+        if len(events) != len(paths) or out.size % 3:
+            raise ValueError("wavefront_accumulate: one event per path, an image of float3 pixels")
+        self._check(self._lib.spt_wavefront_accumulate(self._h, paths.ctypes.data_as(C.c_void_p), events.ctypes.data_as(C.c_void_p), len(paths),
+                                                       int(pixel_first), out.size // 3, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def wavefront_accumulate_device(self, paths_t, events_t, image_t, n=None, pixel_first=0, stream=None):
+        """The same on device tensors (spt_wavefront_accumulate_device): ``image_t`` float32 of 3 * pixels elements, updated in place."""
+        who = "wavefront_accumulate_device"
+        n = int(paths_t.shape[0] if n is None else n)
+        _wf_tensor(who, paths_t, "torch.int32", n, 12)
+        _wf_tensor(who, events_t, "torch.float32", n, 3)
+        if str(image_t.dtype) != "torch.float32" or image_t.device.type != "cuda" or not image_t.is_contiguous() or image_t.numel() % 3:
+            raise ValueError(f"{who}: image_t is a contiguous float32 device tensor of float3 pixels")
+        self._check(self._lib.spt_wavefront_accumulate_device(self._h, C.c_void_p(paths_t.data_ptr()), C.c_void_p(events_t.data_ptr()), n, int(pixel_first),
+                                                              image_t.numel() // 3, C.c_void_p(image_t.data_ptr()), C.c_void_p(stream) if stream else None))
+
+    def wavefront_render(self, w, h, samps_per_cell, seed=0, normalise=False, camera=None):
+        """Renderer::render's loop behind the boundary (spt_wavefront_render): generate, the scene's closest-hit query, shade, accumulate,
+        until no path is left.  Returns ((h, w, 3) float32, stats) -- the stats of ``render``; the image adds a pixel's events bounce by
+        bounce, so it equals ``wavefront_loop``'s bit for bit and ``render``'s up to the order of the float32 additions."""
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        out = np.empty((h, w, 3), dtype=np.float32)
+        st = SptStats()
+        self._check(self._lib.spt_wavefront_render(self._h, C.byref(cam), w, h, samps_per_cell, seed, FLAG_NORMALISE if normalise else 0,
+                                                   out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return out, _stats_dict(st)
+
+    def set_wavefront_chunk(self, pixels=0):
+        """Pixels per chunk of ``wavefront_render`` (csrc/spt_internal.h; 0 = the default).  Results never depend on it."""
+        self._check(self._lib.spt_set_wavefront_chunk(self._h, int(pixels)))
+
+    def wavefront_loop(self, w, h, samps_per_cell, seed=0, camera=None, keep=False, stream=None):
+        """The loop ``wavefront_render`` runs, driven from outside: ``wavefront_generate_device``, then per bounce the scene's closest-hit
+        query (spt_trace_spheres_device or spt_trace_rays_device), ``wavefront_shade_device`` and ``wavefront_accumulate_device`` over torch
+        tensors, until no child is left.  ``stream``: a raw hipStream_t for every step (None = the context's stream).  Returns
+        (image (h, w, 3) float32 un-normalised, {"samples", "bounces", "max_depth_kills"}), and with ``keep`` a third value: the list of
+        (PATH_DTYPE paths, (n, 3) events, HIT_DTYPE hits) of every iteration."""
+        import torch
+        cam = camera if camera is not None else smallpt_camera(w, h)
+        dev = torch.device("cuda", self.device_id)
+        n = self.wavefront_path_count(w, h, samps_per_cell)
+        f32 = lambda rows, cols: torch.empty((max(1, rows), cols), dtype=torch.float32, device=dev)
+        i32 = lambda rows: torch.empty((max(1, rows), 12), dtype=torch.int32, device=dev)
+        rays, paths = f32(n, 6), i32(n)
+        image = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)                          # torch's fills are done before another stream writes the tensors
+        sp = C.c_void_p(stream) if stream else None
+        trace = self._lib.spt_trace_spheres_device if self._state["scene"][0] == "spheres" else self._lib.spt_trace_rays_device
+        self.wavefront_generate_device(rays, paths, w, h, samps_per_cell, seed=seed, camera=cam, stream=stream)
+        stats = {"samples": n, "bounces": 0, "max_depth_kills": 0}
+        kept = []
+        while n:
+            hits, events, nrays, npaths = f32(n, 11), f32(n, 3), f32(2 * n, 6), i32(2 * n)
+            torch.cuda.synchronize(dev)
+            self._check(trace(self._h, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr()), sp))
+            self.wavefront_shade_device(rays, paths, hits, nrays, npaths, events, counts, n=n, stream=stream)
+            self.wavefront_accumulate_device(paths, events, image, n=n, stream=stream)
+            torch.cuda.synchronize(dev)
+            if keep:
+                kept.append((paths[:n].cpu().numpy().view(PATH_DTYPE).reshape(-1), events[:n].cpu().numpy(),
+                             hits[:n].cpu().numpy().view(HIT_DTYPE).reshape(-1)))
+            children, kills = (int(v) for v in counts.cpu())
+            stats["bounces"] += n
+            stats["max_depth_kills"] += kills
+            rays, paths, n = nrays, npaths, children
+        out = image.cpu().numpy()
+        return (out, stats, kept) if keep else (out, stats)
 
     def denoise_pvar(self, beauty, normal, albedo, position, coverage, variance, aov_samples, params=None):
         """Variance-guided filter with a caller's per-pixel variance (spt_denoise_pvar): ``denoise_var`` with ``variance`` = (h, w)

@@ -123,6 +123,9 @@ RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3)])                        
 assert HIT_DTYPE.itemsize == 44 and RAY_DTYPE.itemsize == 24
 RAY_RANGE_DTYPE = np.dtype([("o", "<f4", 3), ("tmin", "<f4"), ("d", "<f4", 3), ("tmax", "<f4")])                                   # OptixRay, smallpt.cpp:395-403
 assert RAY_RANGE_DTYPE.itemsize == 32
+PATH_DTYPE = np.dtype([("weight", "<f4", 3), ("depth", "<u4"), ("pixel", "<u4"), ("sample", "<u4"), ("k0", "<u4"), ("k1", "<u4"),
+                       ("branch", "<u4"), ("pad", "<u4", 3)])                                                                          # spt_path
+assert PATH_DTYPE.itemsize == 48
 
 
 class TriMesh:
