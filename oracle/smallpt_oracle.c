@@ -582,17 +582,102 @@ typedef struct {
     uint64_t depth_kills;
 } trace_ctx;
 
+/* What one shadePaths step makes of one path that hit something. */
+typedef struct {
+    f3 event;            /* weight * emission, :179 */
+    int has_r;           /* the child that continues the path: the reflected child of a split, else the only child (DIFF, SPEC, total
+                            reflection, the picked side of glass below the split depth) */
+    int has_t;           /* the transmitted child of a split (depth <= 2) */
+    int capped;          /* children dropped by the depth cap (D18) */
+    path_t r, t;
+} shade_out;
+
 /* extend() smallpt.cpp:120-123 + D18 depth cap + zero-weight cut (SURVEY.md section 7,
  * "Zero-throughput waste": a path whose weight is exactly 0 can never contribute again). */
-static inline int make_child(trace_ctx* tc, const path_t* p, f3 o, f3 d, f3 factor, uint32_t branch, path_t* c)
+static inline int make_child(int zero_cut, const path_t* p, f3 o, f3 d, f3 factor, uint32_t branch, path_t* c, int* capped)
 {
     c->o = o; c->d = d;
     c->w = mul(p->w, factor);                                  /* :122 */
     c->depth = p->depth + 1;
     c->branch = branch;
-    if (c->depth >= ORC_MAX_DEPTH) { tc->depth_kills++; return 0; }
-    if (tc->zero_cut && c->w.x == 0.f && c->w.y == 0.f && c->w.z == 0.f) return 0;
+    if (c->depth >= ORC_MAX_DEPTH) { ++*capped; return 0; }
+    if (zero_cut && c->w.x == 0.f && c->w.y == 0.f && c->w.z == 0.f) return 0;
     return 1;
+}
+
+/* The shadePaths body, smallpt.cpp:170-263, of ONE path p (direction, weight, depth, branch; its origin is not read) with the D7 keys
+ * (k0, k1) that hit material m at hx with the normal n as the intersector gave it.  The only copy: trace_sample walks a sample's tree
+ * with it, orc_shade_paths runs it over an array. */
+static void shade_step(const path_t* p, uint32_t k0, uint32_t k1, f3 hx, f3 n, const orc_material* m, int zero_cut, shade_out* out)
+{
+    out->has_r = out->has_t = out->capped = 0;
+    f3 nl = dot(n, p->d) < 0 ? n : scl(n, -1.0f);      /* :174 with the flip (D2) */
+    f3 f = ld(m->color);                               /* :175 */
+    const float pmax = fmaxf(fmaxf(f.x, f.y), f.z);    /* :177 optix::fmaxf(float3) */
+    out->event = mul(p->w, ld(m->emission));           /* :179 (D4) */
+    const uint32_t depth = p->depth;                   /* :185 */
+    if (depth > 5) {                                   /* :188 (D5) */
+        if (orc_rng_uniform(k0, k1, ctr_of(p->branch, depth, J_RR)) < pmax)
+            f = scl(f, 1 / pmax);                      /* :192 */
+        else
+            return;                                    /* :196 */
+    }
+    /* D3: the new origin is offset 0.02 along the side the outgoing ray leaves on */
+    f3 off = scl(nl, 0.02f);                           /* :172 */
+    f3 x_out = add(hx, off);
+    if (m->refl == ORC_DIFF) {                         /* :208 */
+        float u1 = orc_rng_uniform(k0, k1, ctr_of(p->branch, depth, J_R1));
+        float r2 = orc_rng_uniform(k0, k1, ctr_of(p->branch, depth, J_R2));
+        float r2s = sqrtf(r2);                         /* :210 */
+        float sn, cs;
+        orc_sincos2pi(u1, &sn, &cs);                   /* :210,212 via D17 */
+        f3 w = nl;                                     /* :211 */
+        f3 u = normalize(cross(((double)fabsf(w.x) > .1 ? mk(0, 1, 0) : mk(1, 0, 0)), w));
+        f3 v = cross(w, u);
+        f3 d = normalize(add(add(scl(scl(u, cs), r2s), scl(scl(v, sn), r2s)),
+                             scl(w, sqrtf(1 - r2))));  /* :212 */
+        out->has_r = make_child(zero_cut, p, x_out, d, f, p->branch, &out->r, &out->capped); /* :214 */
+        return;
+    }
+    /* :218 reflRay(x, r.d - n*2*dot(n, r.d)) */
+    f3 rd = sub(p->d, scl(scl(n, 2.0f), dot(n, p->d)));
+    if (m->refl == ORC_SPEC) {                         /* :219 */
+        out->has_r = make_child(zero_cut, p, x_out, rd, f, p->branch, &out->r, &out->capped); /* :221 */
+        return;
+    }
+    const int into = dot(n, nl) > 0;                   /* :225 */
+    const float nc = 1;                                /* :226 */
+    const float nt = 1.5;                              /* :227 */
+    const float nnt = into ? nc / nt : nt / nc;        /* :228 */
+    const float ddn = dot(p->d, nl);                   /* :229 */
+    const float cos2t = 1 - nnt * nnt * (1 - ddn * ddn); /* :230 */
+    if (cos2t < 0) {                                   /* :232 total internal reflection */
+        out->has_r = make_child(zero_cut, p, x_out, rd, f, p->branch, &out->r, &out->capped); /* :234 */
+        return;
+    }
+    /* :238 */
+    f3 tdir = normalize(sub(scl(p->d, nnt), scl(n, (float)(into ? 1 : -1) * (ddn * nnt + sqrtf(cos2t)))));
+    const float a = nt - nc;                           /* :240 */
+    const float b = nt + nc;                           /* :241 */
+    const float R0 = a * a / (b * b);                  /* :242 */
+    const float cc = 1 - (into ? -ddn : dot(tdir, n)); /* :243 */
+    const float c2 = cc * cc;                          /* :244 */
+    const float Re = R0 + (1 - R0) * c2 * c2 * cc;     /* :245 */
+    const float Tr = 1 - Re;                           /* :246 */
+    f3 x_in = sub(hx, off);                            /* D3: transmitted ray leaves on the -nl side */
+    if (depth <= 2) {                                  /* :248 split (D6) */
+        out->has_t = make_child(zero_cut, p, x_in, tdir, scl(f, Tr), p->branch | (1u << depth), &out->t, &out->capped); /* :252 */
+        out->has_r = make_child(zero_cut, p, x_out, rd, scl(f, Re), p->branch, &out->r, &out->capped);                  /* :251 */
+        return;
+    }
+    const float P = (float)(.25 + .5 * Re);            /* :256 (double literals) */
+    if (orc_rng_uniform(k0, k1, ctr_of(p->branch, depth, J_R1)) < P) { /* :257 */
+        /* :259 f * Re / P ; optix operator/(float3,float) multiplies by 1.0f/P */
+        out->has_r = make_child(zero_cut, p, x_out, rd, scl(scl(f, Re), 1.0f / P), p->branch, &out->r, &out->capped);
+        return;
+    }
+    /* :263 f * Tr / (1.f - P) */
+    out->has_r = make_child(zero_cut, p, x_in, tdir, scl(scl(f, Tr), 1.0f / (1.f - P)), p->branch, &out->r, &out->capped);
 }
 
 /* Traces the whole path tree of one camera ray; emission events are added to *acc in DFS
@@ -625,85 +710,47 @@ static void trace_sample(trace_ctx* tc, path_t cam_path, uint32_t k0, uint32_t k
                 m = (const orc_material*)tc->sph[id].emission;
             }
             /* ---- shadePaths body, smallpt.cpp:170-263 ---- */
-            f3 nl = dot(n, p.d) < 0 ? n : scl(n, -1.0f);       /* :174 with the flip (D2) */
-            f3 f = ld(m->color);                               /* :175 */
-            const float pmax = fmaxf(fmaxf(f.x, f.y), f.z);    /* :177 optix::fmaxf(float3) */
-            *acc = add(*acc, mul(p.w, ld(m->emission)));       /* :179 (D4) */
-            const uint32_t depth = p.depth;                    /* :185 */
-            if (depth > 5) {                                   /* :188 (D5) */
-                if (orc_rng_uniform(k0, k1, ctr_of(p.branch, depth, J_RR)) < pmax)
-                    f = scl(f, 1 / pmax);                      /* :192 */
-                else
-                    break;                                     /* :196 */
-            }
-            /* D3: the new origin is offset 0.02 along the side the outgoing ray leaves on */
-            f3 off = scl(nl, 0.02f);                           /* :172 */
-            f3 x_out = add(hx, off);
-            path_t c;
-            if (m->refl == ORC_DIFF) {                         /* :208 */
-                float u1 = orc_rng_uniform(k0, k1, ctr_of(p.branch, depth, J_R1));
-                float r2 = orc_rng_uniform(k0, k1, ctr_of(p.branch, depth, J_R2));
-                float r2s = sqrtf(r2);                         /* :210 */
-                float sn, cs;
-                orc_sincos2pi(u1, &sn, &cs);                   /* :210,212 via D17 */
-                f3 w = nl;                                     /* :211 */
-                f3 u = normalize(cross(((double)fabsf(w.x) > .1 ? mk(0, 1, 0) : mk(1, 0, 0)), w));
-                f3 v = cross(w, u);
-                f3 d = normalize(add(add(scl(scl(u, cs), r2s), scl(scl(v, sn), r2s)),
-                                     scl(w, sqrtf(1 - r2))));  /* :212 */
-                if (!make_child(tc, &p, x_out, d, f, p.branch, &c)) break; /* :214 */
-                p = c;
-                continue;
-            }
-            /* :218 reflRay(x, r.d - n*2*dot(n, r.d)) */
-            f3 rd = sub(p.d, scl(scl(n, 2.0f), dot(n, p.d)));
-            if (m->refl == ORC_SPEC) {                         /* :219 */
-                if (!make_child(tc, &p, x_out, rd, f, p.branch, &c)) break; /* :221 */
-                p = c;
-                continue;
-            }
-            const int into = dot(n, nl) > 0;                   /* :225 */
-            const float nc = 1;                                /* :226 */
-            const float nt = 1.5;                              /* :227 */
-            const float nnt = into ? nc / nt : nt / nc;        /* :228 */
-            const float ddn = dot(p.d, nl);                    /* :229 */
-            const float cos2t = 1 - nnt * nnt * (1 - ddn * ddn); /* :230 */
-            if (cos2t < 0) {                                   /* :232 total internal reflection */
-                if (!make_child(tc, &p, x_out, rd, f, p.branch, &c)) break; /* :234 */
-                p = c;
-                continue;
-            }
-            /* :238 */
-            f3 tdir = normalize(sub(scl(p.d, nnt), scl(n, (float)(into ? 1 : -1) * (ddn * nnt + sqrtf(cos2t)))));
-            const float a = nt - nc;                           /* :240 */
-            const float b = nt + nc;                           /* :241 */
-            const float R0 = a * a / (b * b);                  /* :242 */
-            const float cc = 1 - (into ? -ddn : dot(tdir, n)); /* :243 */
-            const float c2 = cc * cc;                          /* :244 */
-            const float Re = R0 + (1 - R0) * c2 * c2 * cc;     /* :245 */
-            const float Tr = 1 - Re;                           /* :246 */
-            f3 x_in = sub(hx, off);                            /* D3: transmitted ray leaves on the -nl side */
-            if (depth <= 2) {                                  /* :248 split (D6) */
-                path_t ct;
-                int has_t = make_child(tc, &p, x_in, tdir, scl(f, Tr), p.branch | (1u << depth), &ct); /* :252 */
-                int has_r = make_child(tc, &p, x_out, rd, scl(f, Re), p.branch, &c);                    /* :251 */
-                if (has_t) stack[sp++] = ct;                   /* processed after the reflected subtree */
-                if (!has_r) break;
-                p = c;
-                continue;
-            }
-            const float P = (float)(.25 + .5 * Re);            /* :256 (double literals) */
-            if (orc_rng_uniform(k0, k1, ctr_of(p.branch, depth, J_R1)) < P) { /* :257 */
-                /* :259 f * Re / P ; optix operator/(float3,float) multiplies by 1.0f/P */
-                if (!make_child(tc, &p, x_out, rd, scl(scl(f, Re), 1.0f / P), p.branch, &c)) break;
-                p = c;
-                continue;
-            }
-            /* :263 f * Tr / (1.f - P) */
-            if (!make_child(tc, &p, x_in, tdir, scl(scl(f, Tr), 1.0f / (1.f - P)), p.branch, &c)) break;
-            p = c;
+            shade_out so;
+            shade_step(&p, k0, k1, hx, n, m, tc->zero_cut, &so);
+            *acc = add(*acc, so.event);
+            tc->depth_kills += (uint64_t)so.capped;
+            if (so.has_t) stack[sp++] = so.t;                  /* processed after the reflected subtree */
+            if (!so.has_r) break;
+            p = so.r;
         }
     }
+}
+
+/* One shadePaths call over n paths, with the contract of the product's spt_wavefront_shade (include/smallpt_mi355x.h) word for word: a
+ * plain loop over ascending i that writes children as the reference's nextPaths[currentNextPathIdx++] does, reflected before transmitted. */
+void orc_shade_paths(const orc_material* mats, uint32_t nmat, const float* env_or_null, const orc_ray* rays, const orc_path* paths,
+                     const orc_hit* hits, uint64_t n, float* events, orc_ray* next_rays, orc_path* next_paths, uint64_t counts[2])
+{
+    uint64_t children = 0, kills = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const orc_path* q = &paths[i];
+        const orc_hit* h = &hits[i];
+        if (!(h->dist < ORC_INF) || h->instId >= nmat) {       /* a miss: the material is never read */
+            st(events + 3 * i, env_or_null ? mul(ld(q->weight), ld(env_or_null)) : mk(0, 0, 0));
+            continue;
+        }
+        path_t p;
+        p.o = ld(rays[i].o); p.d = ld(rays[i].d); p.w = ld(q->weight); p.depth = q->depth; p.branch = q->branch;
+        shade_out so;
+        shade_step(&p, q->k0, q->k1, ld(h->x), ld(h->n), &mats[h->instId], 1, &so);
+        st(events + 3 * i, so.event);
+        kills += (uint64_t)so.capped;
+        const path_t* kid[2] = { so.has_r ? &so.r : NULL, so.has_t ? &so.t : NULL };
+        for (int j = 0; j < 2; ++j) {
+            if (!kid[j]) continue;
+            st(next_rays[children].o, kid[j]->o); st(next_rays[children].d, kid[j]->d);
+            orc_path* c = &next_paths[children++];
+            st(c->weight, kid[j]->w);
+            c->depth = kid[j]->depth; c->pixel = q->pixel; c->sample = q->sample; c->k0 = q->k0; c->k1 = q->k1; c->branch = kid[j]->branch;
+            c->pad[0] = c->pad[1] = c->pad[2] = 0;
+        }
+    }
+    counts[0] = children; counts[1] = kills;
 }
 
 /* ---------------------------------------------------------------- render ------------------ */

@@ -158,6 +158,23 @@ int orc_render_instances(const orc_mesh* models, uint32_t nmodels, const orc_ins
                          uint32_t samps_per_cell, uint64_t seed, uint32_t flags, int threads,
                          float* out, orc_stats* stats);
 
+/* --- one shadePaths step: the contract of spt_wavefront_shade (include/smallpt_mi355x.h) restated --- */
+/* Same 48-byte layout as spt_path: PathContrib without its ray + the D7 address of the sample. */
+typedef struct {
+    float    weight[3];  uint32_t depth;
+    uint32_t pixel, sample, k0, k1;
+    uint32_t branch;     /* bit k = transmitted child of the split at depth k */
+    uint32_t pad[3];     /* written 0, ignored on input */
+} orc_path;
+/* shadePaths (smallpt.cpp:154-267) over n paths, sequentially for ascending i -- the statements orc_render runs per bounce.  Path i is
+ * a miss when !(hits[i].dist < 1e20f) or hits[i].instId >= nmat (the material is never read): events[i] = weight * env, or 0 with
+ * env_or_null == NULL, no child.  A hit: events[i] = weight * emission of mats[instId], then roulette, the DIFF / SPEC / REFR branches, the
+ * split while depth <= 2, the depth cap and the zero-weight cut; hit.x and hit.n as given.  A child copies pixel, sample, k0, k1 and has
+ * pad = 0.  Children go to next_rays / next_paths (room for 2 n) as nextPaths[currentNextPathIdx++]: ascending parent, the reflected
+ * child before the transmitted one.  events: n packed float3.  counts = {children, depth-cap kills}. */
+void orc_shade_paths(const orc_material* mats, uint32_t nmat, const float* env_or_null, const orc_ray* rays, const orc_path* paths,
+                     const orc_hit* hits, uint64_t n, float* events, orc_ray* next_rays, orc_path* next_paths, uint64_t counts[2]);
+
 int orc_num_threads(void);
 
 #ifdef __cplusplus

@@ -32,6 +32,9 @@ class OrcMaterial(C.Structure):
 
 INSTANCE_DTYPE = np.dtype([("transform", "<f4", 12), ("model", "<u4"), ("pad", "<u4")])    # orc_instance = spt_instance, 56 bytes
 HIT_DTYPE = np.dtype([("dist", "<f4"), ("instId", "<u4"), ("triId", "<u4"), ("x", "<f4", 3), ("n", "<f4", 3), ("uv", "<f4", 2)])
+PATH_DTYPE = np.dtype([("weight", "<f4", 3), ("depth", "<u4"), ("pixel", "<u4"), ("sample", "<u4"), ("k0", "<u4"), ("k1", "<u4"),
+                       ("branch", "<u4"), ("pad", "<u4", 3)])                              # orc_path = spt_path, 48 bytes
+MATERIAL_DTYPE = np.dtype([("emission", "<f4", 3), ("color", "<f4", 3), ("refl", "<i4"), ("pad", "<u4")])   # orc_material, 32 bytes
 
 FLAG_NORMALISE = 1
 FLAG_NO_ZERO_WEIGHT_CUT = 2
@@ -82,6 +85,9 @@ def lib():
         L.orc_mesh_hits.argtypes = [C.POINTER(OrcMesh), C.c_void_p, C.c_uint64, C.c_void_p]
         L.orc_sphere_reports.restype = None
         L.orc_sphere_reports.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.orc_shade_paths.restype = None
+        L.orc_shade_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -253,3 +259,35 @@ def render_instances(models, instances, materials, w, h, samps, seed=0, normalis
     if rc:
         raise RuntimeError(f"orc_render_instances failed rc={rc}")
     return out, {"samples": int(st.samples), "bounces": int(st.bounces), "max_depth_kills": int(st.max_depth_kills)}
+
+
+# ---- one shadePaths step (the contract of spt_wavefront_shade restated in the oracle) ----
+def materials(rows):
+    """MATERIAL_DTYPE[n] from (emission, colour, refl) rows, or from a sphere table (its material fields)."""
+    if isinstance(rows, np.ndarray) and rows.dtype.names and "emission" in rows.dtype.names:
+        out = np.zeros(len(rows), dtype=MATERIAL_DTYPE)
+        out["emission"], out["color"], out["refl"] = rows["emission"], rows["color"], rows["refl"]
+        return out
+    out = np.zeros(len(rows), dtype=MATERIAL_DTYPE)
+    for i, (e, col, refl) in enumerate(rows):
+        out["emission"][i], out["color"][i], out["refl"][i] = e, col, int(refl)
+    return out
+
+
+def shade_paths(mats, rays, paths, hits, env=None):
+    """orc_shade_paths over (n, 6) float32 rays, PATH_DTYPE[n] and HIT_DTYPE[n] (any structured arrays of those layouts) with the
+    materials ``mats`` (see ``materials``) and the environment ``env`` (None = black).  Returns (events (n, 3) float32, next rays
+    (children, 6) float32, PATH_DTYPE[children], depth-cap kills)."""
+    mats = materials(mats)
+    rays = np.ascontiguousarray(rays).view(np.float32).reshape(-1, 6)
+    paths, hits = np.ascontiguousarray(paths), np.ascontiguousarray(hits)
+    n = len(rays)
+    assert paths.shape == (n,) and hits.shape == (n,) and paths.dtype.itemsize == 48 and hits.dtype.itemsize == 44
+    events = np.zeros((n, 3), dtype=np.float32)
+    nrays, npaths = np.zeros((2 * n, 6), dtype=np.float32), np.zeros(2 * n, dtype=PATH_DTYPE)
+    counts = np.zeros(2, dtype=np.uint64)
+    e = np.ascontiguousarray(env, dtype=np.float32) if env is not None else None
+    lib().orc_shade_paths(mats.ctypes.data, len(mats), e.ctypes.data if e is not None else None, rays.ctypes.data, paths.ctypes.data, hits.ctypes.data,
+                          n, events.ctypes.data, nrays.ctypes.data, npaths.ctypes.data, counts.ctypes.data)
+    m = int(counts[0])
+    return events, nrays[:m], npaths[:m], int(counts[1])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import oracle_binding as orc
 import wavefront_expected as wx
 
 pytestmark = pytest.mark.gpu
@@ -126,31 +127,7 @@ def test_generate_windows_and_a_band(pkg, cornell, dev, stream):
 
 
 # ---- shade and its compaction ---------------------------------------------------------------------------------------------------------------
-SIZES = (1, 63, 64, 65, 255, 256, 257, 1025)
-PATTERNS = ("all_miss", "all_split", "alternating", "one_dead", "mixed")
-
-
-def _pattern(name, n):
-    """(materials, depths, misses) of n paths"""
-    i = np.arange(n)
-    miss = [None] * n
-    if name == "all_miss":
-        mats, depths = i % 4, i % 6
-        miss = [wx.MISS_KINDS[k % len(wx.MISS_KINDS)] for k in range(n)]
-    elif name == "all_split":
-        mats, depths = np.full(n, wx.M_REFR), i % 3
-    elif name == "alternating":                                       # two children, none, two, none ...
-        mats, depths = np.where(i % 2 == 0, wx.M_REFR, wx.M_BLACK), i % 3
-    elif name == "one_dead":                                          # one child each, but every 257th path none
-        mats, depths = np.where(i % 257 == 0, wx.M_BLACK, wx.M_SPEC), np.where(i % 257 == 0, i % 6, (i * 7) % 4000)
-    else:
-        rng = np.random.default_rng(n)
-        mats = rng.integers(0, 4, n)
-        depths = rng.integers(0, 6, n)                                # glass: 0..2 split, 3..5 do not
-        deep = (mats == wx.M_SPEC) & (rng.uniform(size=n) < 0.5)      # the immune mirror below the roulette depth and at the cap
-        depths = np.where(deep, rng.choice([6, 100, wx.MAX_DEPTH - 2, wx.MAX_DEPTH - 1], n), depths)
-        miss = [wx.MISS_KINDS[k % len(wx.MISS_KINDS)] if rng.uniform() < 0.2 else None for k in range(n)]
-    return mats.astype(np.uint32), depths.astype(np.uint32), miss
+SIZES, PATTERNS, _pattern = wx.SIZES, wx.PATTERNS, wx.pattern      # shared with tests/test_oracle_shade.py
 
 
 def _run_shade(r, dev, rays, paths, hits, raw_stream):
@@ -186,6 +163,9 @@ def test_shade_children_order_counts_and_events(four, dev, pattern, n):
     ev, nrays, npaths, kills = _run_shade(four, dev, rays, paths, hits, st.cuda_stream if st is not None else None)
     rows, want_kills = wx.expected_children(paths, hits)
     assert kills == want_kills and len(npaths) == len(rows)
+    # the whole records against the oracle's step (orc_shade_paths), bit for bit
+    oev, orays, opaths, okills = orc.shade_paths(wx.MATERIALS, rays, paths, hits, env)
+    assert kills == okills and ev.tobytes() == oev.tobytes() and nrays.tobytes() == orays.tobytes() and npaths.tobytes() == opaths.tobytes()
     if pattern == "all_miss":
         assert len(rows) == 0
     if pattern == "all_split":
